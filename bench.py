@@ -6,19 +6,29 @@ per GPU.  One "step" = one AL work unit over one batch of synthetic images resid
 MyEpochBasedRunnerLambda.run_iter (main forward + backward + SGD, then MEH forward + backward + SGD) on 16 images PLUS the HUA scoring
 pass over 16 images of the same shape (forward + MEH forward + top-k + NMS + Dirichlet sampling + aggregation -> one score per image),
 i.e. the metric "images/sec train + HUA-score".  value = SURVEY 8(d)'s AL-cycle rate N / (T_train + T_score) = 16 * GPUs * steps / time
-(images through BOTH phases per second); `phase_rates` holds the two phases separately (>= 50 iterations each).
+(images through BOTH phases per second); with --full `phase_rates` holds the two phases separately (>= 50 iterations each).
 
 Arithmetic: --precision bf16x3 (default) is the REFERENCE-PRECISION mode -- the reference is fp32 end to end, so the headline is measured
 with fp32-grade products (bf16 head/tail pairs, three MFMAs per product, aod_meh_hua_amd/functional.py set_precision, csrc/conv.hip "X3"); --precision bf16 is the fast
-mode with plain bf16 operands.  The line carries the other mode's figures under precision.other_mode (N = 1).
+mode with plain bf16 operands.  With --full the line carries the other mode's figures under precision.other_mode (N = 1).
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --full                                   the headline plus everything measured beside it (see below)
     python bench.py --config r101coco                        BASELINE configs[4] at N = 1: R101, 80 classes, 8 x 800x1344 per GPU
     python bench.py --mode pool --pool 10000                 BASELINE configs[3]: the real pool loop over on-device Philox images
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live (HIP events on the launch stream around every conv launch of one extra
-instrumented step); `cpu_baseline` times the CPU oracle (a faithful port of the reference's CPU path, oracle/model.py) on a bounded
-sample on rank 0 at N == 1 only.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the line
+(`value`, `ms_per_step` = milliseconds per timed step).  --full adds, after the timed steps: the timed steps again with the scores read
+after every step, the per-phase rates, the HUA sampler statistics, the other precision mode, `roofline` (measured live: HIP events on the
+launch stream around every conv launch of one extra instrumented step; --shapes writes its per-shape listing), the measured peaks of
+this box and `cpu_baseline` (the CPU oracle, a faithful port of the reference's CPU path, oracle/model.py, timed on a bounded sample on
+rank 0 at N == 1 only).  Without --full those fields are null.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's share) as DIR/<name>.npy, float32: train_loss and
+train_<loss name> (the losses of the training iteration), train_params (the parameters it updated, concatenated in
+model.parameters() order), score_dets / score_labels (detections per image, zero-padded to max_per_img rows) and score_unc (the image
+scores); --mode pool writes pool_scores.  An array longer than DUMP_MAX elements is written as a fixed, seeded sample of DUMP_MAX
+elements.  Inputs and weights are seeded: the same arguments give the same inputs from run to run.
 """
 import argparse
 import copy
@@ -35,6 +45,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0       # HBM3E spec (6.29 TB/s measured with a float4 copy)
+DUMP_MAX = 1 << 22          # elements per --dump-outputs array: 16 MB of float32 (train_params reaches it, every other array is far smaller)
 
 CONFIGS = {
     'voc512': dict(depth=50, classes=20, H=512, W=512, batch=16, name='RetinaNet-R50-FPN + MEH/HUA, synthetic VOC 512x512',
@@ -67,7 +78,23 @@ def parse():
     ap.add_argument('--rotate', type=int, default=4, help='distinct resident train batches / pool batches the timed loop cycles through (1: one batch, '
                     'written straight into the graphs\' static input buffers)')
     ap.add_argument('--no-graph', action='store_true', help='enqueue every kernel from Python instead of replaying HIP graphs')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure everything beside the headline: serial-score '
+                    'timing, per-phase rates, HUA statistics, the other precision mode, roofline, measured peaks, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy (float32)')
+    args = ap.parse_args()
+    if args.shapes and not args.full:
+        ap.error('--shapes lists the instrumented step of --full: add --full')
+    return args
+
+
+def dump_outputs(outdir, arrays):
+    """arrays: name -> host array, written as float32 .npy; longer than DUMP_MAX elements: a fixed, seeded sample (sorted indices)"""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX))]
+        np.save(os.path.join(outdir, name + '.npy'), a)
 
 
 def synth_batch(B, H, W, device, seed, classes=20):
@@ -351,9 +378,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(precision, steps, warmup, use_graph, phase_iters):
-        """Everything the line says about ONE precision mode: the timed region (warm-up, barrier, `steps` steps, barrier; max over ranks), the
-        per-phase rates and one instrumented eager step for the roofline blocks."""
+    def measure(precision, steps, warmup, use_graph, phase_iters, full, want_outputs=False):
+        """Everything the line says about ONE precision mode: the timed region (warm-up, barrier, `steps` steps, barrier; max over ranks),
+        with full=True also the serial-score timing, the per-phase rates and one instrumented eager step for the roofline blocks.
+        want_outputs: host copies of what the last timed step handed its caller (`outputs`)."""
         AF.set_precision(precision)
         gstep = GraphedTrainStep(model, opt, opt_L, grad_sync=gsync if world > 1 else None, Labeled=True, Pseudo=False)
         gscore = GraphedScore(pool_model, **{k: v for k, v in SCORE_KW.items() if k != 'return_loss'})
@@ -378,7 +406,7 @@ def main():
                 if do_train:
                     # R > 1: batch k_ is copied into the graph's static input buffer (one 50 MB device copy) and its ground truth packed and
                     # uploaded, as for a loader's batch; R == 1: `data` IS the static buffer (see below)
-                    gstep(data if R == 1 else datas[k_])
+                    state['train'] = gstep(data if R == 1 else datas[k_])
                 if do_score:
                     ids = id_table(it)
                     # R == 1: the synthetic pool batch is resident in HBM (contract): it sits in the static input buffer of EACH of the scoring
@@ -391,7 +419,8 @@ def main():
                             si.copy_(img)
                             state['filled'].add(si.data_ptr())
                         img = si
-                    _, unc = gscore(img, pools[k_]['img_metas'], ids, defer=defer)
+                    state['score'] = gscore(img, pools[k_]['img_metas'], ids, defer=defer)
+                    unc = state['score'][1]
                     if world > 1 and not defer:
                         gather_scores(unc, B * world)
                     return unc
@@ -409,12 +438,14 @@ def main():
                 opt.step()
                 gsync.all_reduce_grads(opt_L.param_groups[0]['params'])
                 opt_L.step()
+                state['train'] = dict(loss=out['loss'].detach(), log_vars={**out['log_vars'], **lossL['log_vars']})     # (what GraphedTrainStep returns)
             if do_score:
                 pool_model.eval()
                 with torch.no_grad():
                     ids = id_table(it)
-                    _, unc = pool_model(img=[pools[k_]['img']], img_metas=[pools[k_]['img_metas']], image_ids=ids, **SCORE_KW)
+                    det, unc = pool_model(img=[pools[k_]['img']], img_metas=[pools[k_]['img_metas']], image_ids=ids, **SCORE_KW)
                     unc = torch.as_tensor(unc, device=dev, dtype=torch.float32)
+                    state['score'] = (det, unc)
                     if world > 1:
                         gather_scores(unc, B * world)
 
@@ -455,11 +486,24 @@ def main():
             barrier()
             return time.perf_counter() - t0
 
+        def last_outputs():
+            """the last step's losses and updated parameters, its detections and image scores (timed() has synchronised the device)"""
+            o = {}
+            if 'train' in state:
+                o['train_loss'] = state['train']['loss']
+                o.update(('train_' + k, v) for k, v in state['train']['log_vars'].items())
+                o['train_params'] = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+            if 'score' in state:
+                det, unc = state['score']
+                o.update(score_dets=torch.stack([d_ for d_, _ in det]), score_labels=torch.stack([l_ for _, l_ in det]), score_unc=unc)
+            return {k: v.float().cpu().numpy() for k, v in o.items()}
+
         for i in range(warmup):
             step(i)
         dt = timed(steps, warmup)
+        outputs = last_outputs() if want_outputs else None
         serial_ms = None
-        if deferred and world == 1:                   # the same steps with the scores read after every step, beside the line (not `value`)
+        if full and deferred and world == 1:          # the same steps with the scores read after every step, beside the line (not `value`)
             deferred = False
             serial_ms = round(timed(min(steps, 20), warmup + steps) / min(steps, 20) * 1e3, 3)
             deferred = True
@@ -468,6 +512,8 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t)
+        if not full:
+            return dict(dt=dt, steps=steps, phase=None, roof=None, use_graph=use_graph, deferred=deferred, serial_ms=None, outputs=outputs)
 
         # ---- per-phase rates (outside the timed region; SURVEY 8d: >= 50 iterations, train / score separately beside the combined rate)
         phase = {}
@@ -594,26 +640,29 @@ def main():
                         secondary={k: dict(bound='hbm', launches=v[0], us=round(v[1] * 1e6, 1), achieved=round(v[2] / v[1] / 1e9, 1), peak=PEAK_HBM_GBS,
                                            unit='GB/s', frac=round(v[2] / v[1] / 1e9 / PEAK_HBM_GBS, 4)) for k, v in sec.items() if v[1] > 0})
         del gstep, gscore
-        return dict(dt=dt, steps=steps, phase=phase, roof=roof, use_graph=use_graph, deferred=deferred, serial_ms=serial_ms)
+        return dict(dt=dt, steps=steps, phase=phase, roof=roof, use_graph=use_graph, deferred=deferred, serial_ms=serial_ms, outputs=outputs)
 
-    main_m = measure(args.precision, args.steps, args.warmup, not args.no_graph, args.phase_iters)
+    main_m = measure(args.precision, args.steps, args.warmup, not args.no_graph, args.phase_iters, args.full,
+                     want_outputs=bool(args.dump_outputs) and rank == 0)
     dt, use_graph = main_m['dt'], main_m['use_graph']
     # the combined figure is the AL-cycle rate N / (T_train + T_score) -- a step trains on B images per GPU and scores B (other)
     # images per GPU, i.e. B images per GPU pass through BOTH phases per step
     value = B * world * args.steps / dt
+    if main_m['outputs'] is not None:
+        dump_outputs(args.dump_outputs, main_m['outputs'])
 
     hua = None
-    if do_score:
+    if do_score and args.full:
         hua = hua_stats(pool_model, pool, SCORE_KW, dev)          # every rank (same launches); rank 0 reports its own batch
         hua.update(head_scale=round(cal_k, 3), fg_anchor_frac_at_calibration=round(cal_frac, 5))
         assert hua['pairs_per_img'] > 0, 'degenerate HUA phase: no (candidate, object) pair in the scoring batch'
 
     # ---- the other precision mode, same workload, same run (N = 1 only: a figure beside the line, not part of `value`)
     other = None
-    if world == 1 and not args.no_precision_check:
+    if args.full and world == 1 and not args.no_precision_check:
         om_ = 'bf16' if args.precision == 'bf16x3' else 'bf16x3'
         try:
-            m2 = measure(om_, 20, 3, not args.no_graph, 20)
+            m2 = measure(om_, 20, 3, not args.no_graph, 20, True)
             r2 = m2['roof'] or {}
             other = dict(mode=om_, arithmetic=PRECISIONS[om_][2], value=round(B * 20 / m2['dt'], 2), ms_per_step=round(m2['dt'] / 20 * 1e3, 3),
                          phase_rates=m2['phase'], launch='hip-graph replay' if m2['use_graph'] else 'eager',
@@ -628,7 +677,7 @@ def main():
     if x3:       # (the keys round 3's line carried for the reference-precision figure)
         prec.update(bf16x3_ms_per_step=x3['ms'], bf16x3_value=x3['v'], bf16x3_phases=args.mode)
 
-    peaks = measured_peaks(dev) if rank == 0 else None
+    peaks = measured_peaks(dev) if rank == 0 and args.full else None
     roof = main_m['roof']
     if roof is not None:
         roof['measured_peaks'] = peaks
@@ -644,7 +693,7 @@ def main():
                     tot_['frac_of_measured_mfma_loop'] = round(tot_['tflops'] * PRECISIONS[args.precision][1] / peaks['mfma_loop_tflops'], 4)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, cd, do_train, do_score)
 
     if rank == 0:
@@ -717,6 +766,8 @@ def pool_mode(args, cd, pool_model, dev, rank, world, B, H, W, cal_k, cal_frac, 
         dt = float(t)
     nb = -(-(hi - lo) // B)
     unc_h = unc.float().cpu()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(pool_scores=unc_h.numpy()))
     if rank == 0:
         sel = None
         try:

@@ -16,7 +16,7 @@ def test_two_rank_bench_on_one_gpu():
     env = dict(os.environ, AOD_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29541', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '2',
-           '--size', '128', '--no-cpu-baseline']
+           '--size', '128', '--no-cpu-baseline', '--full']
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')][-1]

@@ -6,7 +6,7 @@ for cfg in "pool:--mode pool --pool 2000" "r101coco:--config r101coco --steps 6 
   name=${cfg%%:*}; args=${cfg#*:}
   D=$R/gpurun_out/prof_cfg_$name
   mkdir -p $D
-  rocprofv3 --kernel-trace --stats -d $D -o out --output-format csv -- python3 $R/bench.py $args --no-precision-check --no-cpu-baseline > $D/bench.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats -d $D -o out --output-format csv -- python3 $R/bench.py $args --full --no-precision-check --no-cpu-baseline > $D/bench.json 2>/dev/null
   echo "== $name"; tail -1 $D/bench.json | cut -c1-300
   python3 - <<PY
 import csv

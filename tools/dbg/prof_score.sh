@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 D=$R/gpurun_out/prof_score
 mkdir -p $D
-rocprofv3 --kernel-trace --stats -d $D -o out --output-format csv -- python3 $R/bench.py --mode score --steps 20 --warmup 3 --no-cpu-baseline --no-precision-check > $D/bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $D -o out --output-format csv -- python3 $R/bench.py --full --mode score --steps 20 --warmup 3 --no-cpu-baseline --no-precision-check > $D/bench.json 2>/dev/null
 python3 - <<PY
 import csv
 rows = list(csv.DictReader(open('$D/out_kernel_stats.csv')))
