@@ -33,6 +33,11 @@ class ConvDesc(C.Structure):
                 ('out_f32', C.c_int32), ('nseg', C.c_int32), ('x3', C.c_int32), ('seg', ConvSeg * 8)]
 
 
+class ConvPlan(C.Structure):
+    """aod_conv_plan_t: the kernel a conv launch runs on (aod_conv2d_plan); kind 1 PW_STREAM, 2 SPLIT_K, 3 X3P, 4 IGEMM"""
+    _fields_ = [(n, C.c_int32) for n in ('kind', 'bm', 'bn', 'nt', 'ops', 'stages', 'x3', 'grouped', 'ksplit', 'taps', 'wide', 'pre', 'lat', 'grid')]
+
+
 P, I32, I64, F32, U64, SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     'aod_version': (C.c_int, []),
@@ -57,6 +62,7 @@ _SIGS = {
     'aod_conv2d': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P]),
     'aod_conv2d_ws_bytes': (SZ, [C.POINTER(ConvDesc)]),
     'aod_conv2d_ws': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    'aod_conv2d_plan': (C.c_int, [C.POINTER(ConvDesc), I32, C.c_uint, C.POINTER(ConvPlan)]),
     'aod_conv2d_grouped': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P]),
     'aod_halo_conv3x3_applies': (C.c_int, [C.POINTER(ConvDesc)]),
     'aod_halo_conv3x3': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P]),

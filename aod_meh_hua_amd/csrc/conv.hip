@@ -1034,43 +1034,73 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize_kernel(const ConvKPa
   }
 }
 
+// =====================================================================================
+// forward / dgrad dispatch:  conv_params -> conv_plan -> conv_launch   (DESIGN.md "How a conv picks its kernel")
+// =====================================================================================
+// The environment switches of the dispatch.  FIRST HALF: read once per process (the first launch or plan).  SECOND HALF: consulted by the plan
+// of every launch, because tests and parallel.GradSync change them in-process -- read lazily, at most once per launch and only by a rule
+// that gets as far as asking, so that a launch never calls getenv more often than the rule ladder it replaces did (plain-bf16 launches: never).
+struct ConvKnobs {
+  struct Once {
+    const char* ksplit_maxhw = getenv("AOD_KSPLIT_MAXHW");      // (debug: the largest per-image output that is still split)
+    const char* ksplit_steps = getenv("AOD_KSPLIT_STEPS");      // (debug: a fixed number of K-steps per slice, the rule of the earlier rounds at 16)
+    const char* stagger = getenv("AOD_STAGGER");
+    const char* x3_taps_inner = getenv("AOD_X3_TAPS_INNER");    // (debug: 0 = the plain K order)
+    const char* dgrad_lattice = getenv("AOD_DGRAD_LATTICE");
+    const char* dgrad_classes = getenv("AOD_DGRAD_CLASSES");
+    const char* tile_want = getenv("AOD_TILE_WANT");            // (debug: the tile count that counts as 'fills the device')
+    const char* tile_256 = getenv("AOD_TILE_256");              // (1 forces the plain 256 x 256 tile, 0 disables it in every form)
+    const char* x3_128_w8 = getenv("AOD_X3_128_W8");
+    const char* x3_128_st3 = getenv("AOD_X3_128_ST3");          // (debug / A-B: the 128 x 128 x3 tile on a three-stage ring, one workgroup per CU)
+    const char* tile_w8 = getenv("AOD_TILE_W8");
+    const char* ring3 = getenv("AOD_RING3");
+  };
+  static const Once& once() { static const Once k{}; return k; }
+
+  enum Call { X3P_OVER_256, X3_TILE_192, X3P_GROUPED, X3P, X3P_PRE, X3P_BN, X3P_DGRAD, X3P_LATTICE, X3P_MIN_STEPS, X3P_PRE_MIN_STEPS, X3P_MIN_TILES,
+              X3P_ROT, NCALL };
+  const char* val[NCALL];
+  unsigned seen = 0;
+  const char* call(Call k) {
+    static const char* const names[NCALL] = {"AOD_X3P_OVER_256", "AOD_X3_TILE_192", "AOD_X3P_GROUPED", "AOD_X3P", "AOD_X3P_PRE", "AOD_X3P_BN",
+                                             "AOD_X3P_DGRAD", "AOD_X3P_LATTICE", "AOD_X3P_MIN_STEPS", "AOD_X3P_PRE_MIN_STEPS", "AOD_X3P_MIN_TILES",
+                                             "AOD_X3P_ROT"};
+    if (!((seen >> k) & 1u)) { val[k] = getenv(names[k]); seen |= 1u << k; }
+    return val[k];
+  }
+  bool is(Call k, char c) { const char* v = call(k); return v && v[0] == c; }
+};
+static bool knob_is(const char* v, char c) { return v && v[0] == c; }
+
+// CU count of the current device, resolved once per device; 256 (the MI355X) when there is no device or the query fails
+static int xp_cus() {
+  static int cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;
+  if (!cus[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
 // Split-K pays when the output is so small that whole tiles cannot fill the device: few tiles x very many K-steps (pyramid level P6:
 // a stride-2 3x3 on the 2048-channel C5, 8 x 8 outputs per image; the 3x3 convs of the 16 x 16 backbone stage, K = 4608).  The decision and the slice boundaries depend on the PER-IMAGE
 // geometry and on K only, never on the batch size: the fp32 summation order of an output element -- and so the score of an image --
 // must not change with how the pool is batched.  Returns the number of K slices (1 = direct launch).
-// operands / geometry of a launch in the persistent kernel's terms (conv_x3p.hip)
-static void x3p_args(const ConvKParams& p, X3PArgs& a) {
-  memset(&a, 0, sizeof(a));
-  a.x = p.x; a.w = p.w; a.y = reinterpret_cast<bf16_t*>(p.y); a.pre_scale = p.pre_scale; a.pre_shift = p.pre_shift; a.res = p.res; a.mask = p.mask;
-  a.colsum = p.colsum; a.C = p.C; a.N = p.N; a.K = p.K; a.taps = p.R * p.S; a.S = p.S; a.stride = p.stride; a.pad = p.pad; a.dil = p.dil;
-  a.transposed = p.transposed; a.relu = p.relu; a.nseg = p.nseg; a.M = p.M; a.x_bytes = p.x_bytes; a.w_bytes = p.w_bytes;
-  a.tapin = (p.tap_inner && a.taps > 1 && p.C >= 256) ? 1 : 0;      // the general kernel's K order for this shape (see `tapin` there)
-  for (int i = 0; i < 8; ++i) {
-    a.segH[i] = p.segH[i]; a.segW[i] = p.segW[i]; a.segOH[i] = p.segOH[i]; a.segOW[i] = p.segOW[i]; a.segB[i] = p.segB[i];
-    a.seg_src0[i] = p.seg_src0[i]; a.seg_dst0[i] = p.seg_dst0[i]; a.seg_mend[i] = p.seg_mend[i];
-  }
-  if (p.ngroups > 1) {
-    a.ngroups = p.ngroups;
-    for (int g = 0; g < p.ngroups; ++g) {
-      a.grp[g].x = p.grp[g].x; a.grp[g].w = p.grp[g].w; a.grp[g].y = reinterpret_cast<bf16_t*>(p.grp[g].y); a.grp[g].shift = p.grp[g].pre_shift;
-      a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum;
-    }
-  }
-}
-
 static int choose_ksplit(const ConvKParams& p) {
+  const ConvKnobs::Once& k1 = ConvKnobs::once();
   const int nk = (p.K + 63) / 64;
   if (nk < 64) return 1;
-  static const char* dbg_hw = getenv("AOD_KSPLIT_MAXHW");      // (debug: the largest per-image output that is still split)
-  const long long maxhw = dbg_hw ? atoll(dbg_hw) : 256;
+  const long long maxhw = k1.ksplit_maxhw ? atoll(k1.ksplit_maxhw) : 256;
   long long rows16 = 0;                 // GEMM rows of a NOMINAL batch of 16 images (the batch size itself must not enter: see above)
   for (int i = 0; i < p.nseg; ++i) {
     if (p.segB[i] <= 0) continue;
     if ((long long)p.segOH[i] * p.segOW[i] > maxhw) return 1;
     rows16 += 16ll * p.segOH[i] * p.segOW[i];
   }
-  static const char* dbg_ks = getenv("AOD_KSPLIT_STEPS");      // (debug: a fixed number of K-steps per slice, the rule of the earlier rounds at 16)
-  if (dbg_ks) { const int per = atoi(dbg_ks); return nk / per > 1 ? nk / per : 1; }
+  if (k1.ksplit_steps) { const int per = atoi(k1.ksplit_steps); return nk / per > 1 ? nk / per : 1; }
   // as many slices as fill ONE round of two workgroups per CU with the split launch's 128-row tiles -- one slice more starts a second,
   // nearly empty round (P6 at 16 x 8 x 8: 36 slices 66.7 us, 24 slices 54.4 us) -- but no slice shorter than 8 K-steps
   const long long tiles = ((rows16 + 127) / 128) * ((p.N + 127) / 128);
@@ -1092,32 +1122,30 @@ static int conv_params(const aod_conv_desc_t* desc, const void* src, const void*
     AOD_CHECK_ARG(desc->out_f32 || desc->N % 32 == 0, "conv (x3): a bf16 (X-layout) destination needs N %% 32 == 0, got %d", desc->N);
     AOD_CHECK_ARG(!(desc->out_f32 && (res || mask)), "conv (x3): residual / mask operands need an X-layout destination");
   }
+  const ConvKnobs::Once& k1 = ConvKnobs::once();
   p.x = (const bf16_t*)src; p.w = (const bf16_t*)w_packed; p.y = dst;
   p.pre_scale = pre_scale; p.pre_shift = pre_shift; p.res = (const bf16_t*)res; p.mask = (const bf16_t*)mask;
   p.post_scale = post_scale; p.zraw = (bf16_t*)zraw; p.colsum = colsum;
   p.ksplit = 1;
-  { static const char* dbg_st = getenv("AOD_STAGGER"); p.stagger = (dbg_st && dbg_st[0] == '0') ? 0 : 1; }
-  { static const char* dbg_ti = getenv("AOD_X3_TAPS_INNER"); p.tap_inner = (dbg_ti && dbg_ti[0] == '0') ? 0 : 1; }     // (debug: 0 = the plain K order)
+  p.stagger = knob_is(k1.stagger, '0') ? 0 : 1;
+  p.tap_inner = knob_is(k1.x3_taps_inner, '0') ? 0 : 1;
   p.perm = (desc->transposed && desc->stride == 2 && desc->R * desc->S > 1 && desc->R * desc->S <= 64) ? 1 : 0;     // (no gain measured for 1x1)
   // The dgrad of a 1x1 / stride-2 conv ACCUMULATED IN PLACE (res == dst, nothing else in the epilogue: the running sum of a gradient
   // junction, functional.GradAcc) only changes the (even, even) pixels of the destination: dX[b, 2y, 2x] += dZ[b, y, x] . W.  As a general
   // transposed launch it walks K for all four pixel classes and rewrites 4 x the rows (206 us for the layer-3 entry at 16 x 64 x 64 x 512
   // in the reference-precision mode); as a LATTICE launch it is a plain GEMM over the dZ pixels whose rows are stored two apart.
   if (desc->transposed && desc->stride == 2 && desc->R == 1 && desc->S == 1 && desc->pad == 0 && desc->nseg == 1 && res && res == dst &&
-      !mask && !colsum && !pre_scale && !pre_shift && !post_scale && !zraw && !desc->relu && !desc->out_f32 && p.M > 0) {
-    static const char* dbg_lat = getenv("AOD_DGRAD_LATTICE");
-    if (!(dbg_lat && dbg_lat[0] == '0')) {
-      p.up_w = p.segOW[0]; p.up_hw = p.segOH[0] * p.segOW[0];
-      p.segOH[0] = p.segH[0]; p.segOW[0] = p.segW[0];
-      p.stride = 1;
-      const long long m = (long long)p.segB[0] * p.segH[0] * p.segW[0];
-      p.M = (int)m;
-      for (int i = 0; i < 8; ++i) p.seg_mend[i] = (int)m;
-      p.bigrows = m >= (1ll << 22) ? 1 : 0;
-    }
+      !mask && !colsum && !pre_scale && !pre_shift && !post_scale && !zraw && !desc->relu && !desc->out_f32 && p.M > 0 &&
+      !knob_is(k1.dgrad_lattice, '0')) {
+    p.up_w = p.segOW[0]; p.up_hw = p.segOH[0] * p.segOW[0];
+    p.segOH[0] = p.segH[0]; p.segOW[0] = p.segW[0];
+    p.stride = 1;
+    const long long m = (long long)p.segB[0] * p.segH[0] * p.segW[0];
+    p.M = (int)m;
+    for (int i = 0; i < 8; ++i) p.seg_mend[i] = (int)m;
+    p.bigrows = m >= (1ll << 22) ? 1 : 0;
   }
-  static const char* dbg_perm = getenv("AOD_DGRAD_CLASSES");
-  if (dbg_perm && dbg_perm[0] == '0') p.perm = 0;
+  if (knob_is(k1.dgrad_classes, '0')) p.perm = 0;
   long long xrows = 0;
   for (int i = 0; i < desc->nseg; ++i) {
     const aod_conv_seg_t& sg = desc->seg[i];
@@ -1131,6 +1159,27 @@ static int conv_params(const aod_conv_desc_t* desc, const void* src, const void*
   return 0;
 }
 
+// ... of a grouped launch (aod_conv2d_grouped): the descriptor with the operands of group 0, then grp[]
+static int conv_params_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
+                               const float* const* pre_shift, const void* const* mask, float* const* colsum, ConvKParams& p) {
+  AOD_CHECK_ARG(desc && src && w_packed && dst && ngroups >= 1 && ngroups <= 4, "conv_grouped: 1..4 groups");
+  AOD_CHECK_ARG(!desc->out_f32, "conv_grouped: bf16 destinations only");
+  AOD_CHECK_ARG(!desc->x3 || (desc->N % 256 == 0 && desc->R * desc->S * desc->C >= 2048), "conv_grouped (x3): N %% 256 == 0 and a deep K required");
+  int rc = conv_params(desc, src[0], w_packed[0], dst[0], nullptr, pre_shift ? pre_shift[0] : nullptr, nullptr, mask ? mask[0] : nullptr, nullptr,
+                       nullptr, colsum ? colsum[0] : nullptr, p);
+  if (rc) return rc;
+  AOD_CHECK_ARG(!p.perm, "conv_grouped: class-major stride-2 dgrad launches are not grouped");
+  p.ngroups = ngroups;
+  for (int g = 0; g < ngroups; ++g) {
+    AOD_CHECK_ARG(src[g] && w_packed[g] && dst[g], "conv_grouped: null operand in group %d", g);
+    p.grp[g].x = (const bf16_t*)src[g]; p.grp[g].w = (const bf16_t*)w_packed[g]; p.grp[g].y = dst[g];
+    p.grp[g].pre_shift = pre_shift ? pre_shift[g] : nullptr;
+    p.grp[g].mask = mask ? (const bf16_t*)mask[g] : nullptr;
+    p.grp[g].colsum = colsum ? colsum[g] : nullptr;
+  }
+  return 0;
+}
+
 extern "C" size_t aod_conv2d_ws_bytes(const aod_conv_desc_t* desc) {
   ConvKParams p;
   memset(&p, 0, sizeof(p));
@@ -1139,205 +1188,338 @@ extern "C" size_t aod_conv2d_ws_bytes(const aod_conv_desc_t* desc) {
   return ks > 1 ? (size_t)ks * p.M * p.N * 4 : 0;
 }
 
+// a 1x1 / stride-1 launch as the plain GEMM over consecutive rows that the streaming kernel (pointwise.hip) runs
+static void pw_args(const ConvKParams& p, PwArgs& a) {
+  const long long s0 = p.seg_src0[0], d0 = p.seg_dst0[0];
+  a.x = p.x + s0 * p.C; a.w = p.w; a.y = reinterpret_cast<bf16_t*>(p.y) + d0 * p.N;
+  a.pre_scale = p.pre_scale; a.pre_shift = p.pre_shift;
+  a.res = p.res ? p.res + d0 * p.N : nullptr; a.mask = p.mask ? p.mask + d0 * p.N : nullptr; a.colsum = p.colsum;
+  a.M = p.M; a.N = p.N; a.K = p.C; a.relu = p.relu;
+}
+
+// The persistent producer / consumer kernel's rules (conv_x3p.hip): true and out.taps / wide / pre / lat / grid filled when it takes the launch.
+// ngroups = 0: a plain launch; det_colsum: a column-sum operand in deterministic mode.
+static bool plan_x3p(const ConvKParams& p, int ngroups, bool det_colsum, ConvKnobs& kn, ConvPlan& out) {
+  if (kn.is(ConvKnobs::X3P, '0')) return false;                      // AOD_X3P=0 keeps every launch on the general kernel
+  const int taps = p.R * p.S, ng = ngroups > 1 ? ngroups : 1;
+  if (taps != 1 && taps != 9) return false;
+  if (taps == 9 && p.S != 3) return false;
+  if (p.N % 128 != 0 || p.C % 64 != 0 || p.M <= 0) return false;
+  // AOD_X3P_DGRAD=0 (parallel.GradSync sets it when gradients are all-reduced under the backward pass): backward launches stay with the general
+  // kernel.  A persistent grid of one 160-KB-LDS workgroup per CU assumes every CU is free; RCCL's channel workgroups hold some for milliseconds,
+  // and the workgroups that cannot start then run AFTER the others -- a one-round launch takes twice as long -- where the general kernel's many
+  // small workgroups just lose those CUs' share.  Forward and scoring launches never run beside a collective.
+  if (p.transposed && kn.is(ConvKnobs::X3P_DGRAD, '0')) return false;
+  // (the class-major stride-2 dgrad and the in-place 1x1 / stride-2 dgrad as lattice launches of the persistent kernel: X3PArgs.lat)
+  const int lat = ngroups ? 0 : (p.perm ? 1 : (p.up_w ? 2 : 0));
+  if (lat && kn.is(ConvKnobs::X3P_LATTICE, '0')) return false;
+  if (lat == 1) {
+    // class-major stride-2 dgrad: 3x3, pad 1, no dilation, one segment with an even map whose halves are the dZ map
+    if (!(p.transposed && p.stride == 2 && taps == 9 && p.pad == 1 && p.dil == 1 && p.nseg == 1)) return false;
+    if ((p.segOH[0] & 1) || (p.segOW[0] & 1) || p.segH[0] * 2 != p.segOH[0] || p.segW[0] * 2 != p.segOW[0]) return false;
+  } else if (lat == 2) {
+    if (!(p.transposed && p.stride == 1 && taps == 1 && p.pad == 0 && p.nseg == 1 && p.up_w > 0)) return false;
+  } else if (p.transposed && p.stride != 1) return false;
+  if (det_colsum) return false;                        // ordered column sums stay with the general kernel (determinism.hip)
+  if ((long long)p.K * 2 * p.N >= 0x7fffffffll) return false;
+  // GEMM rows the launch tiles: the destination pixels, or (class-major form) the pixels of ONE of the four classes
+  const long long rows = lat == 1 ? (long long)p.segB[0] * (p.segOH[0] / 2) * (p.segOW[0] / 2) : p.M;
+  const long long tiles_m = (rows + XP_BM - 1) / XP_BM, reps = (long long)ng * (lat == 1 ? 4 : 1);
+  // Operand-prefetch form (conv_x3p_kernel PRE): dense 1x1 launches with EXACTLY one of residual (-> 1) / ReLU mask (-> 2), else 0.
+  // AOD_X3P_PRE=0 disables.
+  int pre = 0;
+  if (taps == 1 && lat == 0 && ngroups <= 1 && p.stride == 1 && (p.res != nullptr) != (p.mask != nullptr) && !kn.is(ConvKnobs::X3P_PRE, '0'))
+    pre = p.res ? 1 : 2;
+  // 256-column tiles (half the pixel bytes per MFMA, twice the MFMAs per barrier) when they still give at least three quarters of the CUs a
+  // tile; AOD_X3P_BN=128 / 256 forces.  (Not with the prefetch form, which exists for the 128-column tile: 64 accumulators leave room for the operand)
+  const int ncu = xp_cus();
+  bool wide = false;
+  if (!pre && p.N % 256 == 0) {
+    const char* fbn = kn.call(ConvKnobs::X3P_BN);
+    wide = fbn ? atoi(fbn) == 256 : tiles_m * (p.N / 256) * reps >= (long long)ncu * 3 / 4;
+  }
+  // a tile needs a K loop long enough to amortise the one-workgroup-per-CU structure (its epilogue runs beside nothing but the loaders' next
+  // stages): from ~24 K-steps of a 128-column tile on the persistent form wins -- every 3x3 layer (36+ steps), the 1024 -> 256 reduce / lateral
+  // 1x1 convs (32 steps: 37.0 -> 28.7 us), retina_cls' dgrad (54: 243 -> 230 us) -- and a 256-column tile's K-step carries twice the matrix
+  // work per barrier, so 12 of those do (the 512 -> 256 lateral and the 512 -> 1024 stride-2 downsample conv: 57.7 -> 55.0, 57.0 -> 54.3 us).
+  // Below that the general kernel's two workgroups per CU win (the expand 1x1 convs with their residual, 4 - 16 steps: 45.5 vs 49.9,
+  // 34.0 vs 36.8 us; retina_reg / retina_L dgrads with 18 / 9 steps of a 128-column tile: 106 vs 116, 76 vs 88 us) -- a residual epilogue is
+  // only taken from 24 steps on.  The class-major form is judged by its average class (9 taps over 4 classes).
+  // profiles/r06_x3p_micro.txt; AOD_X3P_MIN_STEPS overrides the threshold.
+  {
+    const char* ms = kn.call(ConvKnobs::X3P_MIN_STEPS);
+    const int thr = ms ? atoi(ms) : 24;
+    const int steps = lat == 1 ? 9 * (p.C >> 6) / 4 : taps * (p.C >> 6);
+    // (the operand-prefetch form does not change this: with the residual requested before the K loop the 8-step expand conv of
+    // layer 3 still takes 49.5 us against the general kernel's 44.9 -- its K loop is bound by what 96 KB of ring can keep in flight against
+    // the memory latency under the residual / store traffic, 1.08 us per K-step by the stamps -- and only the 4-step layer-2 expand conv wins,
+    // 73.8 against 80.0 us; AOD_X3P_PRE_MIN_STEPS lowers the threshold for launches that qualify for the form)
+    const char* pms = kn.call(ConvKnobs::X3P_PRE_MIN_STEPS);
+    if (pms && pre) { if (steps < atoi(pms)) return false; }
+    else if (lat != 1 && (steps * (wide ? 2 : 1) < thr || (p.res && steps < thr))) return false;
+    if (lat == 1 && steps * (wide ? 2 : 1) < thr / 2) return false;          // (the general kernel's class-major launches are its slowest: 86 - 127 TFLOP/s)
+  }
+  long long prev = 0;
+  for (int i = 0; i < p.nseg; ++i) {
+    const long long r = p.seg_mend[i] - prev;
+    prev = p.seg_mend[i];
+    if (r >= (1ll << 22)) return false;                              // float-reciprocal row decode
+    if (i + 1 < p.nseg && r % XP_BM != 0) return false;              // a tile must not straddle two segments
+    if (p.seg_dst0[i] + r >= (1ll << 31)) return false;
+  }
+  // one 8-wave workgroup per CU: worth it from ~ a round of the chip on; below that the general kernel's smaller tiles fill more CUs
+  const char* mint = kn.call(ConvKnobs::X3P_MIN_TILES);
+  if (tiles_m * (p.N / 128) * reps < (mint ? atoll(mint) : 192)) return false;
+  const long long ntiles = tiles_m * (p.N / (wide ? 256 : 128)) * reps;
+  out.kind = AOD_CONV_PLAN_X3P;
+  out.taps = lat == 1 ? 4 : taps;          // (the kernel's TAPS: the most taps a class of the class-major form has)
+  out.wide = wide; out.pre = pre; out.lat = lat; out.x3 = 1; out.grouped = ngroups ? 1 : 0;
+  out.grid = (int)(ntiles < ncu ? ntiles : ncu);
+  return true;
+}
+
+// Which kernel a launch runs on.  Pure host logic: reads p (geometry, which operands are present, res == dst through up_w), the knobs, the
+// deterministic flag, the pointwise mode and the CU count; enqueues and allocates nothing.  ngroups = 0: aod_conv2d(_ws); 1 .. 4:
+// aod_conv2d_grouped (p.grp[] filled).
+static int conv_plan(const ConvKParams& p, int ngroups, bool has_workspace, ConvPlan& out) {
+  memset(&out, 0, sizeof(out));
+  const ConvKnobs::Once& k1 = ConvKnobs::once();
+  ConvKnobs kn;
+  bool any_mask = p.mask != nullptr, any_cs = p.colsum != nullptr;
+  for (int g = 0; g < ngroups; ++g) { any_mask = any_mask || p.grp[g].mask; any_cs = any_cs || p.grp[g].colsum; }
+  auto igemm = [&](int bm, int bn, int nt, int ops, int stages) {
+    out.kind = AOD_CONV_PLAN_IGEMM; out.bm = bm; out.bn = bn; out.nt = nt; out.ops = ops; out.stages = stages; out.x3 = p.x3; out.grouped = ngroups ? 1 : 0;
+    return 0;
+  };
+  auto w8 = [&](int bm, int bn) { return igemm(bm, bn, 512, any_mask ? 1 : 0, 2); };      // the 8-wave forms: no residual, own instance with the mask
+  auto ntiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
+  // The 256 x 256 tile (one 8-wave workgroup per CU, 128 FLOP per staged byte instead of 64, two epilogue passes) runs deep-K layers
+  // 15-18 % faster per tile (tools/dbg/tile256.py: 794 -> 934 TFLOP/s on the FPN P3 shape) but one workgroup per CU quantises hard: it
+  // is chosen only when its tiles fill whole rounds of the 256 CUs to >= 92 % (AOD_TILE_256=1 forces it in the plain form, =0 disables it).
+  // X3: a K-step of the 128 x 128 tile asks the L2 -> LDS path for 64 KB per 1 536 matrix-pipe cycles per CU -- more than it delivers --, the
+  // big tile for half of that.
+  const long long t256 = ntiles(256, 256);
+  const bool fits256 = t256 >= 240 && t256 * 100 >= ((t256 + 255) / 256) * 256 * 92;
+  const bool shape256 = !p.res && !p.out_f32 && p.N % 256 == 0 && p.K >= (p.x3 ? 2048 : 1024);
+  const long long want = k1.tile_want ? atoll(k1.tile_want) : 512;      // tiles that fill the device: >= 2 workgroups per CU (2 x 256)
+
+  if (ngroups) {
+    // the head towers' grouped launches CAN run on the persistent producer / consumer kernel (conv_x3p.hip, 128 x 256 tiles; identical bits):
+    // AOD_X3P_GROUPED=1.  Not the default -- launch by launch the two forms are level (671 vs 689 us forward, 729 vs 725 us dgrad for three
+    // groups at 16 x 512^2, profiles/r06_x3p_micro.txt; interleaved A/Bs: tools/dbg/x3p_grouped_micro.py) and inside the step the 256 x 256
+    // tile is 0.3 - 0.5 ms ahead
+    if (p.x3 && p.R == p.S && !p.bigrows && kn.is(ConvKnobs::X3P_GROUPED, '1') && plan_x3p(p, ngroups, any_cs && aod_get_deterministic(), kn, out)) return 0;
+    if (p.x3) return w8(256, 256);          // x3 groups take the big tile (the 4-wave forms have no grouped instances)
+    // the tile whose grouped tile count fills the CU rounds best: 256 x 256 at one workgroup per CU, else 128 x 128 on 8 waves at two
+    auto fill = [&](int bm, int bn, int slots) {
+      const long long t = ntiles(bm, bn) * ngroups;
+      return (double)t / (double)(((t + slots - 1) / slots) * slots);
+    };
+    const bool ok256 = !knob_is(k1.tile_256, '0') && p.N % 256 == 0 && p.K >= 1024;
+    if (ok256 && fill(256, 256, 256) * 1.12 >= fill(128, 128, 512)) return w8(256, 256);        // (the big tile is ~15 % faster per FLOP when its rounds are full)
+    AOD_CHECK_ARG(p.N >= 128, "conv_grouped: N >= 128 required");
+    return w8(128, 128);
+  }
+
+  // 1x1, stride 1: a plain GEMM over consecutive rows -- the persistent streaming kernel (pointwise.hip) when its launch heuristic wants it.
+  // (aod_pw_wants asks aod_det_scratch(1), not the deterministic FLAG: the two differ when the mode is on and the scratch could not be
+  // allocated -- the streaming kernel's atomics are then as good as the general kernel's fallback -- so the call stays as it is.)
+  if (!p.x3 && !p.up_w && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.nseg == 1 && !p.out_f32 && !p.zraw && !p.post_scale) {
+    PwArgs a;
+    pw_args(p, a);
+    if (aod_pw_wants(a)) { out.kind = AOD_CONV_PLAN_PW_STREAM; return 0; }
+  }
+  const int ks = (has_workspace && !p.perm && !p.up_w) ? choose_ksplit(p) : 1;
+  if (ks > 1) {
+    igemm(128, p.N > 64 ? 128 : 64, 256, 2, 2);
+    out.kind = AOD_CONV_PLAN_SPLIT_K; out.ksplit = ks;
+    return 0;
+  }
+  if (p.x3) {
+    // the persistent producer / consumer kernel (conv_x3p.hip) for the 128-column-tileable 1x1 / 3x3 layers that fill at least ~ a round of
+    // the CUs with 128 x 128 tiles and do NOT qualify for the 256 x 256 tile (the head towers, FPN P3): identical bits, AOD_X3P=0 disables
+    // (AOD_X3P_OVER_256=1, A/B: also take the launches of the 256 x 256 tile)
+    if (!p.out_f32 && !p.zraw && !p.post_scale && !p.bigrows && p.R == p.S && (!(shape256 && fits256) || kn.is(ConvKnobs::X3P_OVER_256, '1')) &&
+        plan_x3p(p, 0, any_cs && aod_get_deterministic(), kn, out)) return 0;
+    if (!knob_is(k1.tile_256, '0') && shape256 && fits256) return w8(256, 256);
+    // 129 .. 192 output columns without epilogue operands (retina_cls, 180 columns, fp32 destination): a 192 x 192 tile on eight waves, one
+    // workgroup per CU like the 256 x 256 tile (96 FLOP per staged byte; 64-wide tiles: 43, and the L2 -> LDS path bounds the 4-wave x3
+    // forms), same K order -> same bits.  AOD_X3_TILE_192=0: the 128 x 64 tile.
+    if (p.N > 128 && p.N <= 192 && !p.res && !p.mask && !p.zraw && p.K >= 2048 && ntiles(192, 192) >= 240 && !kn.is(ConvKnobs::X3_TILE_192, '0'))
+      return igemm(192, 192, 512, 0, 2);
+    // A/B knob (AOD_X3_128_W8=1): the 128 x 128 x3 tile on EIGHT waves for launches without a residual operand.  Back to back on warm operands
+    // it beats the 64 x 128 three-stage tile on the 16 384-row layers (80.0 -> 73.2 us for the stage-3 3 x 3, tools/dbg/x3_w8_ab.sh); INSIDE the
+    // step, on operands that come from HBM / the Infinity Cache, it loses 8 % (80.2 -> 86.3 us forward, 77.9 -> 89.3 us dgrad in the instrumented
+    // step, profiles/r05_conv_shapes_one_step.txt against the run before it): not taken.
+    if (knob_is(k1.x3_128_w8, '1') && !p.res && !p.out_f32 && p.N % 128 == 0 && ntiles(128, 128) >= 256) return w8(128, 128);
+  } else {
+    if (!knob_is(k1.tile_256, '0') && shape256 && ((knob_is(k1.tile_256, '1') && t256 >= 128) || fits256)) return w8(256, 256);
+    // deep convs without a residual operand (forward and dgrad of the head towers, the 3x3 of the backbone): the 128 x 128 tile on 8
+    // waves -- four waves per SIMD hide more of the K loop's waits than two (-4 % on the head-tower shape); with the residual's prefetch
+    // registers as well the 8-wave form spills and loses
+    if (!knob_is(k1.tile_w8, '0') && !p.res && p.N >= 128 && p.K >= 1024 && ntiles(128, 128) >= want) return w8(128, 128);
+  }
+  // the 4-wave forms: the largest tile that still fills the device; else the most workgroups
+  // a ragged last column tile (N = 180 -> 128 + 52) wastes MFMA work; 64-wide tiles trim it (192 instead of 256 columns)
+  const int pad128 = (p.N + 127) / 128 * 128, pad64 = (p.N + 63) / 64 * 64;
+  const bool ragged = p.N > 128 && (pad128 - pad64) * 5 >= pad128;
+  // (three LDS stages for the 64-row tiles -- x3: always; plain: when the K loop is long enough to matter, AOD_RING3=0 disables; the 128 x 64
+  // tile keeps two -- three stages cost it its third workgroup per CU: 61 -> 69 us on the narrow prediction convs; the 128 x 128 tile too --
+  // three stages = 96 KB = one workgroup per CU: measured +0.55 ms per step; 64 x 128 x 3 stages instead: +0.3 ms -- but for AOD_X3_128_ST3=1)
+  const int st64 = (p.x3 || (!knob_is(k1.ring3, '0') && p.K >= 256)) ? 3 : 2;
+  if (ragged && ntiles(128, 64) >= want) return igemm(128, 64, 256, 2, 2);
+  if (p.N > 64 && p.x3 && knob_is(k1.x3_128_st3, '1') && ntiles(128, 128) >= 256) return igemm(128, 128, 256, 2, 3);
+  if (p.N > 64 && ntiles(128, 128) >= want) return igemm(128, 128, 256, 2, 2);
+  if (p.N > 64 && ntiles(64, 128) >= want) return igemm(64, 128, 256, 2, st64);
+  if (p.N <= 64 && ntiles(128, 64) >= want) return igemm(128, 64, 256, 2, 2);
+  if (p.N > 64 && ntiles(128, 64) >= want && p.N % 128 != 0) return igemm(128, 64, 256, 2, 2);
+  return igemm(64, 64, 256, 2, st64);
+}
+
+// operands / geometry of a launch in the persistent kernel's terms (conv_x3p.hip)
+static void x3p_args(const ConvKParams& p, const ConvPlan& plan, X3PArgs& a) {
+  memset(&a, 0, sizeof(a));
+  a.x = p.x; a.w = p.w; a.y = reinterpret_cast<bf16_t*>(p.y); a.pre_scale = p.pre_scale; a.pre_shift = p.pre_shift; a.res = p.res; a.mask = p.mask;
+  a.colsum = p.colsum; a.C = p.C; a.N = p.N; a.K = p.K; a.taps = p.R * p.S; a.S = p.S; a.stride = p.stride; a.pad = p.pad; a.dil = p.dil;
+  a.transposed = p.transposed; a.relu = p.relu; a.nseg = p.nseg; a.M = p.M; a.x_bytes = p.x_bytes; a.w_bytes = p.w_bytes;
+  a.tapin = (p.tap_inner && a.taps > 1 && p.C >= 256) ? 1 : 0;      // the general kernel's K order for this shape (see `tapin` there)
+  for (int i = 0; i < 8; ++i) {
+    a.segH[i] = p.segH[i]; a.segW[i] = p.segW[i]; a.segOH[i] = p.segOH[i]; a.segOW[i] = p.segOW[i]; a.segB[i] = p.segB[i];
+    a.seg_src0[i] = p.seg_src0[i]; a.seg_dst0[i] = p.seg_dst0[i]; a.seg_mend[i] = p.seg_mend[i];
+  }
+  // the kernel reads its operands from grp[]: the groups of a grouped launch, else the one set above
+  a.ngroups = p.ngroups > 1 ? p.ngroups : 1;
+  a.grp[0].x = a.x; a.grp[0].w = a.w; a.grp[0].y = a.y; a.grp[0].shift = a.pre_shift; a.grp[0].mask = a.mask; a.grp[0].colsum = a.colsum;
+  for (int g = 0; g < p.ngroups; ++g) {
+    a.grp[g].x = p.grp[g].x; a.grp[g].w = p.grp[g].w; a.grp[g].y = reinterpret_cast<bf16_t*>(p.grp[g].y); a.grp[g].shift = p.grp[g].pre_shift;
+    a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum;
+  }
+  a.lat = plan.lat; a.up_w = p.up_w; a.up_hw = p.up_hw;
+  const long long rows = a.lat == 1 ? (long long)a.segB[0] * (a.segOH[0] / 2) * (a.segOW[0] / 2) : a.M;
+  a.tiles_m = (int)((rows + XP_BM - 1) / XP_BM);
+  a.tiles_n = a.N / (plan.wide ? 256 : 128);
+}
+
+// every instance of conv_igemm_kernel: (BM, BN, NT, OPS, GROUPED, ST, X3) -- the list is the launch switch
+#define CONV_IGEMM_INSTANCES(X)                                                                                                       \
+  X(256, 256, 512, 0, false, 2, false) X(256, 256, 512, 1, false, 2, false) X(128, 128, 512, 0, false, 2, false) X(128, 128, 512, 1, false, 2, false) \
+  X(128, 128, 256, 2, false, 2, false) X(128, 64, 256, 2, false, 2, false) X(64, 128, 256, 2, false, 2, false) X(64, 128, 256, 2, false, 3, false)   \
+  X(64, 64, 256, 2, false, 2, false) X(64, 64, 256, 2, false, 3, false)                                                               \
+  X(256, 256, 512, 0, true, 2, false) X(256, 256, 512, 1, true, 2, false) X(128, 128, 512, 0, true, 2, false) X(128, 128, 512, 1, true, 2, false)    \
+  X(256, 256, 512, 0, false, 2, true) X(256, 256, 512, 1, false, 2, true) X(192, 192, 512, 0, false, 2, true)                          \
+  X(128, 128, 512, 0, false, 2, true) X(128, 128, 512, 1, false, 2, true) X(128, 128, 256, 2, false, 2, true) X(128, 128, 256, 2, false, 3, true)    \
+  X(128, 64, 256, 2, false, 2, true) X(64, 128, 256, 2, false, 3, true) X(64, 64, 256, 2, false, 3, true)                              \
+  X(256, 256, 512, 0, true, 2, true) X(256, 256, 512, 1, true, 2, true)
+
+static int launch_igemm(const ConvPlan& pl, const ConvKParams& p, hipStream_t st) {
+#define X(BM, BN, NT, OPS, GROUPED, ST, X3)                                                                                           \
+  if (pl.bm == BM && pl.bn == BN && pl.nt == NT && pl.ops == OPS && (pl.grouped != 0) == GROUPED && pl.stages == ST && (pl.x3 != 0) == X3) \
+    return launch_conv<BM, BN, NT, OPS, GROUPED, ST, X3>(p, st);
+  CONV_IGEMM_INSTANCES(X)
+#undef X
+  AOD_CHECK_ARG(false, "conv: no kernel instance for the plan %d x %d, %d threads, ops %d, %d stages, x3 %d, grouped %d", pl.bm, pl.bn, pl.nt, pl.ops,
+                pl.stages, pl.x3, pl.grouped);
+  return -1;
+}
+
+// plan -> launch(es).  A plan without a kernel instance is an error, never another kernel.
+static int conv_launch(const ConvPlan& pl, ConvKParams& p, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  switch (pl.kind) {
+    case AOD_CONV_PLAN_PW_STREAM: {
+      PwArgs a;
+      pw_args(p, a);
+      return aod_pw_gemm(a, st);
+    }
+    case AOD_CONV_PLAN_X3P: {
+      X3PArgs a;
+      x3p_args(p, pl, a);
+      ConvKnobs kn;
+      const char* r = kn.call(ConvKnobs::X3P_ROT);
+      a.rot = r ? atoi(r) : 0;
+      return aod_conv_x3p_launch(a, pl, st);
+    }
+    case AOD_CONV_PLAN_SPLIT_K: {
+      const size_t need = (size_t)pl.ksplit * p.M * p.N * 4;
+      AOD_CHECK_ARG(workspace && workspace_bytes >= need, "conv: split-K workspace of %zu bytes, need %zu (aod_conv2d_ws_bytes)", workspace_bytes, need);
+      p.ksplit = pl.ksplit; p.ws = (float*)workspace;
+      int rc = launch_igemm(pl, p, st);
+      if (rc) return rc;
+      AOD_LAUNCH_CHECK();
+      p.cs_ws = p.colsum ? aod_det_scratch((size_t)((p.M + 7) / 8) * p.N) : nullptr;
+      hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((p.M + 7) / 8, (p.N + 255) / 256), dim3(256), 0, st, p);
+      AOD_LAUNCH_CHECK();
+      if (p.cs_ws) return aod_colsum_finalize(p.cs_ws, (p.M + 7) / 8, p.N, p.N, p.colsum, nullptr, 0, st);
+      return 0;
+    }
+    case AOD_CONV_PLAN_IGEMM: {
+      int rc = launch_igemm(pl, p, st);
+      if (rc) return rc;
+      AOD_LAUNCH_CHECK();
+      return 0;
+    }
+  }
+  AOD_CHECK_ARG(false, "conv: plan of unknown kind %d", pl.kind);
+  return -1;
+}
+
 extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
                              const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
                              const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
                              aod_stream_t stream) {
   ConvKParams p;
+  ConvPlan pl;
   int rc = conv_params(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, p);
   if (rc) return rc;
   if (p.M == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  // 1x1, stride 1: a plain GEMM over consecutive rows -- the persistent streaming kernel (pointwise.hip) when its launch heuristic wants it
-  if (!p.x3 && !p.up_w && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.nseg == 1 && !p.out_f32 && !p.zraw && !p.post_scale) {
-    PwArgs a;
-    const long long s0 = p.seg_src0[0], d0 = p.seg_dst0[0];
-    a.x = p.x + s0 * p.C; a.w = p.w; a.y = reinterpret_cast<bf16_t*>(p.y) + d0 * p.N;
-    a.pre_scale = p.pre_scale; a.pre_shift = p.pre_shift;
-    a.res = p.res ? p.res + d0 * p.N : nullptr; a.mask = p.mask ? p.mask + d0 * p.N : nullptr; a.colsum = p.colsum;
-    a.M = p.M; a.N = p.N; a.K = p.C; a.relu = p.relu;
-    if (aod_pw_wants(a)) return aod_pw_gemm(a, st);
-  }
-  const int ks = (workspace && !p.perm && !p.up_w) ? choose_ksplit(p) : 1;
-  if (ks > 1) {
-    const size_t need = (size_t)ks * p.M * p.N * 4;
-    AOD_CHECK_ARG(workspace_bytes >= need, "conv: split-K workspace of %zu bytes, need %zu (aod_conv2d_ws_bytes)", workspace_bytes, need);
-    p.ksplit = ks; p.ws = (float*)workspace;
-    if (p.x3) { if (p.N > 64) launch_conv<128, 128, 256, 2, false, 2, true>(p, st); else launch_conv<128, 64, 256, 2, false, 2, true>(p, st); }
-    else if (p.N > 64) launch_conv<128, 128>(p, st); else launch_conv<128, 64>(p, st);
-    AOD_LAUNCH_CHECK();
-    p.cs_ws = p.colsum ? aod_det_scratch((size_t)((p.M + 7) / 8) * p.N) : nullptr;
-    hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((p.M + 7) / 8, (p.N + 255) / 256), dim3(256), 0, st, p);
-    AOD_LAUNCH_CHECK();
-    if (p.cs_ws) return aod_colsum_finalize(p.cs_ws, (p.M + 7) / 8, p.N, p.N, p.colsum, nullptr, 0, st);
-    return 0;
-  }
-  // tile choice: the largest tile that still gives >= 2 workgroups per CU (2 x 256); else the most workgroups
-  auto ntiles = [&](int bm, int bn) { return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-  static const char* dbg_want = getenv("AOD_TILE_WANT");           // (debug: the tile count that counts as 'fills the device')
-  const long long want = dbg_want ? atoll(dbg_want) : 512;
-  // a ragged last column tile (N = 180 -> 128 + 52) wastes MFMA work; 64-wide tiles trim it (192 instead of 256 columns)
-  const int pad128 = (p.N + 127) / 128 * 128, pad64 = (p.N + 63) / 64 * 64;
-  const bool ragged = p.N > 128 && (pad128 - pad64) * 5 >= pad128;
-  if (p.x3 && !p.out_f32 && !p.zraw && !p.post_scale && !p.bigrows && p.R == p.S) {
-    // the persistent producer / consumer kernel (conv_x3p.hip) for the 128-column-tileable 1x1 / 3x3 layers that fill at least ~ a round of
-    // the CUs with 128 x 128 tiles and do NOT qualify for the 256 x 256 tile below (the head towers, FPN P3): identical bits, AOD_X3P=0 disables
-    const long long t256 = ntiles(256, 256);
-    const bool big = !p.res && p.N % 256 == 0 && p.K >= 2048 && t256 >= 240 && t256 * 100 >= ((t256 + 255) / 256) * 256 * 92;
-    const char* dbg_big = getenv("AOD_X3P_OVER_256");                  // (A/B, read per call: also take the launches of the 256 x 256 tile)
-    if (!big || (dbg_big && dbg_big[0] == '1')) {
-      X3PArgs a;
-      x3p_args(p, a);
-      // (the class-major stride-2 dgrad and the in-place 1x1 / stride-2 dgrad as lattice launches of the persistent kernel: X3PArgs.lat)
-      a.lat = p.perm ? 1 : (p.up_w ? 2 : 0);
-      a.up_w = p.up_w; a.up_hw = p.up_hw;
-      if (aod_conv_x3p_wants(a, p.colsum && aod_get_deterministic())) return aod_conv_x3p_launch(a, st);
-    }
-  }
-  if (p.x3) {
-    // X3: the 256 x 256 tile under the same fill rule as the plain form (a K-step of the 128 x 128 tile asks the L2 -> LDS path for 64 KB
-    // per 1 536 matrix-pipe cycles per CU -- more than it delivers --, the big tile for half of that), else the 4-wave forms
-    {
-      static const char* dbg_t256x = getenv("AOD_TILE_256");
-      const long long t256 = ntiles(256, 256);
-      const bool fits = t256 >= 240 && t256 * 100 >= ((t256 + 255) / 256) * 256 * 92;
-      if (!(dbg_t256x && dbg_t256x[0] == '0') && !p.res && !p.out_f32 && p.N % 256 == 0 && p.K >= 2048 && fits) {
-        if (!p.mask) launch_conv<256, 256, 512, 0, false, 2, true>(p, st); else launch_conv<256, 256, 512, 1, false, 2, true>(p, st);
-        AOD_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    // 129 .. 192 output columns without epilogue operands (retina_cls, 180 columns, fp32 destination): a 192 x 192 tile on eight waves, one
-    // workgroup per CU like the 256 x 256 tile (96 FLOP per staged byte; 64-wide tiles: 43, and the L2 -> LDS path bounds the 4-wave x3
-    // forms), same K order -> same bits.  AOD_X3_TILE_192=0: the 128 x 64 tile.
-    {
-      const char* dbg_t192 = getenv("AOD_X3_TILE_192");      // (read per call: tests switch it in-process)
-      const long long t192 = ntiles(192, 192);
-      if (!(dbg_t192 && dbg_t192[0] == '0') && p.N > 128 && p.N <= 192 && !p.res && !p.mask && !p.zraw && p.K >= 2048 && t192 >= 240) {
-        launch_conv<192, 192, 512, 0, false, 2, true>(p, st);
-        AOD_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    // A/B knob (AOD_X3_128_W8=1): the 128 x 128 x3 tile on EIGHT waves for launches without a residual operand.  Back to back on warm operands
-    // it beats the 64 x 128 three-stage tile on the 16 384-row layers (80.0 -> 73.2 us for the stage-3 3 x 3, tools/dbg/x3_w8_ab.sh); INSIDE the
-    // step, on operands that come from HBM / the Infinity Cache, it loses 8 % (80.2 -> 86.3 us forward, 77.9 -> 89.3 us dgrad in the instrumented
-    // step, profiles/r05_conv_shapes_one_step.txt against the run before it): not taken.
-    static const char* dbg_w8x = getenv("AOD_X3_128_W8");
-    const long long t128 = ntiles(128, 128);
-    const bool w8 = dbg_w8x && dbg_w8x[0] == '1' && !p.res && !p.out_f32 && p.N % 128 == 0 && t128 >= 256;
-    if (w8) {
-      if (!p.mask) launch_conv<128, 128, 512, 0, false, 2, true>(p, st); else launch_conv<128, 128, 512, 1, false, 2, true>(p, st);
-      AOD_LAUNCH_CHECK();
-      return 0;
-    }
-    static const char* dbg_st3 = getenv("AOD_X3_128_ST3");        // (debug / A-B: the 128 x 128 x3 tile on a three-stage ring, one workgroup per CU)
-    if (ragged && ntiles(128, 64) >= want) launch_conv<128, 64, 256, 2, false, 2, true>(p, st);
-    else if (p.N > 64 && dbg_st3 && dbg_st3[0] == '1' && ntiles(128, 128) >= 256) launch_conv<128, 128, 256, 2, false, 3, true>(p, st);
-    else if (p.N > 64 && ntiles(128, 128) >= want) launch_conv<128, 128, 256, 2, false, 2, true>(p, st);
-    else if (p.N > 64 && ntiles(64, 128) >= want) launch_conv<64, 128, 256, 2, false, 3, true>(p, st);
-    else if (p.N <= 64 && ntiles(128, 64) >= want) launch_conv<128, 64, 256, 2, false, 2, true>(p, st);
-    else if (p.N > 64 && ntiles(128, 64) >= want && p.N % 128 != 0) launch_conv<128, 64, 256, 2, false, 2, true>(p, st);
-    else launch_conv<64, 64, 256, 2, false, 3, true>(p, st);
-    AOD_LAUNCH_CHECK();
-    return 0;
-  }
-  // deep convs without a residual operand (forward and dgrad of the head towers, the 3x3 of the backbone): the 128 x 128 tile on 8
-  // waves -- four waves per SIMD hide more of the K loop's waits than two (-4 % on the head-tower shape); with the residual's prefetch
-  // registers as well the 8-wave form spills and loses
-  // The 256 x 256 tile (one 8-wave workgroup per CU, 128 FLOP per staged byte instead of 64, two epilogue passes) runs deep-K layers
-  // 15-18 % faster per tile (tools/dbg/tile256.py: 794 -> 934 TFLOP/s on the FPN P3 shape) but one workgroup per CU quantises hard: it
-  // is chosen only when its tiles fill whole rounds of the 256 CUs to >= 92 % (AOD_TILE_256=1 forces it, =0 disables it).
-  static const char* dbg_t256 = getenv("AOD_TILE_256");
-  const long long t256 = ntiles(256, 256);
-  const bool fits256 = t256 >= 240 && t256 * 100 >= ((t256 + 255) / 256) * 256 * 92;
-  if (!(dbg_t256 && dbg_t256[0] == '0') && !p.res && !p.out_f32 && p.N % 256 == 0 && p.K >= 1024 &&
-      ((dbg_t256 && dbg_t256[0] == '1' && t256 >= 128) || fits256)) {
-    if (!p.mask) launch_conv<256, 256, 512, 0>(p, st); else launch_conv<256, 256, 512, 1>(p, st);
-    AOD_LAUNCH_CHECK();
-    return 0;
-  }
-  static const char* dbg_w8 = getenv("AOD_TILE_W8");
-  if (!(dbg_w8 && dbg_w8[0] == '0') && !p.res && p.N >= 128 && p.K >= 1024 && ntiles(128, 128) >= want) {
-    if (!p.mask) launch_conv<128, 128, 512, 0>(p, st); else launch_conv<128, 128, 512, 1>(p, st);
-    AOD_LAUNCH_CHECK();
-    return 0;
-  }
-  // (three LDS stages for the 64-row 4-wave tiles when the K loop is long enough to matter: AOD_RING3=0 disables; the 128 x 64 tile keeps
-  // two -- three stages cost it its third workgroup per CU: 61 -> 69 us on the narrow prediction convs)
-  static const char* dbg_r3 = getenv("AOD_RING3");
-  const bool r3 = !(dbg_r3 && dbg_r3[0] == '0') && p.K >= 256;
-  if (ragged && ntiles(128, 64) >= want) launch_conv<128, 64>(p, st);
-  else if (p.N > 64 && ntiles(128, 128) >= want) launch_conv<128, 128>(p, st);      // (three stages = 96 KB = one workgroup per CU: measured +0.55 ms per step; 64 x 128 x 3 stages instead: +0.3 ms)
-  else if (p.N > 64 && ntiles(64, 128) >= want) { if (r3) launch_conv<64, 128, 256, 2, false, 3>(p, st); else launch_conv<64, 128>(p, st); }
-  else if (p.N <= 64 && ntiles(128, 64) >= want) launch_conv<128, 64>(p, st);
-  else if (p.N > 64 && ntiles(128, 64) >= want && p.N % 128 != 0) launch_conv<128, 64>(p, st);
-  else { if (r3) launch_conv<64, 64, 256, 2, false, 3>(p, st); else launch_conv<64, 64>(p, st); }
-  AOD_LAUNCH_CHECK();
-  return 0;
+  rc = conv_plan(p, 0, workspace != nullptr, pl);
+  if (rc) return rc;
+  return conv_launch(pl, p, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
                                   void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
                                   aod_stream_t stream) {
-  AOD_CHECK_ARG(desc && src && w_packed && dst && ngroups >= 1 && ngroups <= 4, "conv_grouped: 1..4 groups");
-  AOD_CHECK_ARG(!desc->out_f32, "conv_grouped: bf16 destinations only");
-  AOD_CHECK_ARG(!desc->x3 || (desc->N % 256 == 0 && desc->R * desc->S * desc->C >= 2048), "conv_grouped (x3): N %% 256 == 0 and a deep K required");
   ConvKParams p;
-  int rc = conv_params(desc, src[0], w_packed[0], dst[0], nullptr, pre_shift ? pre_shift[0] : nullptr, nullptr, mask ? mask[0] : nullptr, nullptr,
-                       nullptr, colsum ? colsum[0] : nullptr, p);
+  ConvPlan pl;
+  int rc = conv_params_grouped(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, p);
   if (rc) return rc;
   if (p.M == 0) return 0;
-  AOD_CHECK_ARG(!p.perm, "conv_grouped: class-major stride-2 dgrad launches are not grouped");
-  p.ngroups = ngroups;
-  bool any_mask = false;
-  for (int g = 0; g < ngroups; ++g) {
-    AOD_CHECK_ARG(src[g] && w_packed[g] && dst[g], "conv_grouped: null operand in group %d", g);
-    p.grp[g].x = (const bf16_t*)src[g]; p.grp[g].w = (const bf16_t*)w_packed[g]; p.grp[g].y = dst[g];
-    p.grp[g].pre_shift = pre_shift ? pre_shift[g] : nullptr;
-    p.grp[g].mask = mask ? (const bf16_t*)mask[g] : nullptr;
-    p.grp[g].colsum = colsum ? colsum[g] : nullptr;
-    any_mask = any_mask || p.grp[g].mask;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // the tile whose grouped tile count fills the CU rounds best: 256 x 256 at one workgroup per CU, else 128 x 128 on 8 waves at two
-  auto fill = [&](int bm, int bn, int slots) {
-    const long long t = (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * ngroups;
-    return (double)t / (double)(((t + slots - 1) / slots) * slots);
-  };
-  static const char* dbg_t256 = getenv("AOD_TILE_256");
-  const bool ok256 = !(dbg_t256 && dbg_t256[0] == '0') && p.N % 256 == 0 && p.K >= 1024;
-  if (p.x3 && p.R == p.S && !p.bigrows) {
-    // the head towers' grouped launches CAN run on the persistent producer / consumer kernel (conv_x3p.hip, 128 x 256 tiles; identical bits):
-    // AOD_X3P_GROUPED=1.  Not the default -- launch by launch the two forms are level (671 vs 689 us forward, 729 vs 725 us dgrad for three
-    // groups at 16 x 512^2, profiles/r06_x3p_micro.txt) and inside the step the 256 x 256 tile is 0.3 - 0.5 ms ahead
-    const char* dbg_g = getenv("AOD_X3P_GROUPED");                   // (read per call: tests / A-B scripts switch it in-process)
-    bool any_cs = false;
-    for (int g = 0; g < ngroups; ++g) any_cs = any_cs || p.grp[g].colsum;
-    if (dbg_g && dbg_g[0] == '1') {        // (opt-in: interleaved A/Bs put it level with the 256 x 256 tile, tools/dbg/x3p_grouped_micro.py)
-      X3PArgs a;
-      x3p_args(p, a);
-      if (ngroups == 1) { a.ngroups = 1; a.grp[0].x = p.grp[0].x; a.grp[0].w = p.grp[0].w; a.grp[0].y = reinterpret_cast<bf16_t*>(p.grp[0].y);
-                          a.grp[0].shift = p.grp[0].pre_shift; a.grp[0].mask = p.grp[0].mask; a.grp[0].colsum = p.grp[0].colsum; }
-      if (aod_conv_x3p_wants(a, any_cs && aod_get_deterministic())) return aod_conv_x3p_launch(a, st);
-    }
-  }
-  if (p.x3) {          // x3 groups take the big tile (the 4-wave forms have no grouped instances)
-    if (!any_mask) launch_conv<256, 256, 512, 0, true, 2, true>(p, st); else launch_conv<256, 256, 512, 1, true, 2, true>(p, st);
-  } else if (ok256 && fill(256, 256, 256) * 1.12 >= fill(128, 128, 512)) {        // (the big tile is ~15 % faster per FLOP when its rounds are full)
-    if (!any_mask) launch_conv<256, 256, 512, 0, true>(p, st); else launch_conv<256, 256, 512, 1, true>(p, st);
-  } else {
-    AOD_CHECK_ARG(p.N >= 128, "conv_grouped: N >= 128 required");
-    if (!any_mask) launch_conv<128, 128, 512, 0, true>(p, st); else launch_conv<128, 128, 512, 1, true>(p, st);
-  }
-  AOD_LAUNCH_CHECK();
-  return 0;
+  rc = conv_plan(p, ngroups, false, pl);
+  if (rc) return rc;
+  return conv_launch(pl, p, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int aod_conv2d(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
                           const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
                           const float* post_scale, void* zraw, float* colsum, aod_stream_t stream) {
   return aod_conv2d_ws(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, nullptr, 0, stream);
+}
+
+// The plan of aod_conv2d_ws (ngroups = 0) / aod_conv2d_grouped (1 .. 4) for this descriptor and these operands: host logic, no device needed
+extern "C" int aod_conv2d_plan(const aod_conv_desc_t* desc, int ngroups, unsigned operand_flags, aod_conv_plan_t* out) {
+  AOD_CHECK_ARG(desc && out && ngroups >= 0 && ngroups <= 4, "conv_plan: null pointer or ngroups outside 0..4");
+  static char operand[16];                      // stands for every operand that is present: the plan looks at pointers, never through them
+  char* const dst = operand + 8;
+  auto has = [&](unsigned f) { return (operand_flags & f) ? (void*)operand : nullptr; };
+  void* const res = (operand_flags & AOD_CONV_RES_IS_DST) ? (void*)dst : has(AOD_CONV_HAS_RES);
+  ConvKParams p;
+  int rc;
+  if (ngroups) {
+    const void* in[4] = {operand, operand, operand, operand};
+    void* outs[4] = {dst, dst, dst, dst};
+    const float* shift[4] = {};
+    const void* mask[4] = {has(AOD_CONV_HAS_MASK)};
+    float* colsum[4] = {(float*)has(AOD_CONV_HAS_COLSUM)};
+    shift[0] = (const float*)has(AOD_CONV_HAS_PRE_SHIFT);
+    rc = conv_params_grouped(desc, ngroups, in, in, outs, shift, mask, colsum, p);
+  } else {
+    rc = conv_params(desc, operand, operand, dst, (const float*)has(AOD_CONV_HAS_PRE_SCALE), (const float*)has(AOD_CONV_HAS_PRE_SHIFT), res,
+                     has(AOD_CONV_HAS_MASK), (const float*)has(AOD_CONV_HAS_POST_SCALE), has(AOD_CONV_HAS_ZRAW), (float*)has(AOD_CONV_HAS_COLSUM), p);
+  }
+  if (rc) return rc;
+  memset(out, 0, sizeof(*out));
+  if (p.M == 0) return 0;
+  return conv_plan(p, ngroups, (operand_flags & AOD_CONV_HAS_WORKSPACE) != 0, *out);
 }
 
 // =====================================================================================

@@ -1,7 +1,10 @@
-// Persistent producer / consumer form of the reference-precision (x3) convolution: csrc/conv_x3p.hip.  conv.hip's dispatcher fills X3PArgs
-// from its own parameter block and asks aod_conv_x3p_wants() whether the launch qualifies.
+// Persistent producer / consumer form of the reference-precision (x3) convolution: csrc/conv_x3p.hip.  conv.hip's conv_plan() decides whether
+// a launch takes it and in which form (ConvPlan: taps, wide, pre, lat, grid); conv_launch() fills X3PArgs from its own parameter block.
 #pragma once
 #include "common.h"
+
+typedef aod_conv_plan_t ConvPlan;      // what conv_plan() decides and conv_launch() follows (include/aod_hip.h: aod_conv2d_plan reports it)
+constexpr int XP_BM = 128;             // pixel rows of a tile of the persistent kernel
 
 struct X3PArgs {
   const bf16_t* x;          // source rows, X-layout, p.C physical columns
@@ -20,7 +23,7 @@ struct X3PArgs {
                             // taps that reach it; 2 the IN-PLACE 1x1 / stride-2 dgrad (conv.hip `up_w`): a plain GEMM over the dZ pixels whose row
                             // (b, y, x) is stored at destination row b * up_hw + 2y * up_w + 2x
   int up_w, up_hw;
-  int ngroups;              // >= 1: grp[] holds the operands (the launcher fills grp[0] from the fields above for a plain launch)
+  int ngroups;              // >= 1: grp[] holds the operands (grp[0] repeats the fields above for a plain launch)
   struct { const bf16_t* x; const bf16_t* w; bf16_t* y; const float* shift; const bf16_t* mask; float* colsum; } grp[4];
   long long x_bytes, w_bytes;
   int segH[8], segW[8], segOH[8], segOW[8], segB[8];
@@ -28,6 +31,5 @@ struct X3PArgs {
   int seg_mend[8];
 };
 
-// 1: this launch may take the persistent kernel (shape, operands, segment alignment, fill); 0: the general kernel keeps it
-int aod_conv_x3p_wants(const X3PArgs& a, int deterministic_colsum);
-int aod_conv_x3p_launch(const X3PArgs& a, hipStream_t st);
+// launches the instance plan.taps / wide / lat / pre name on plan.grid workgroups (a combination without an instance is an error)
+int aod_conv_x3p_launch(const X3PArgs& a, const ConvPlan& plan, hipStream_t st);

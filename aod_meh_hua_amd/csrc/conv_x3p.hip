@@ -30,7 +30,7 @@
 
 namespace {
 
-constexpr int XP_BM = 128, XP_XBYTES = 16384;
+constexpr int XP_XBYTES = 16384;
 constexpr unsigned XP_OOB = 0xf0000000u;
 
 __device__ __forceinline__ unsigned xp_udiv(unsigned n, unsigned d) {      // n / d for n < 2^22 (conv.hip udiv_small)
@@ -450,10 +450,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 #undef XP_GSEL
 
-int g_x3p_cus[64];
 long long g_x3p_count = 0;
 
-template <int TAPS, int NBW, int LAT = 0, int PRE = 0>
+template <int TAPS, int NBW, int LAT, int PRE>
 int xp_launch(const X3PArgs& a, int grid, hipStream_t st) {
   constexpr int STAGE = XP_XBYTES + 32 * NBW * 128, RING = NBW == 4 ? 5 : 3;
   const size_t lds = (size_t)RING * STAGE;
@@ -465,130 +464,23 @@ int xp_launch(const X3PArgs& a, int grid, hipStream_t st) {
 
 }  // namespace
 
-// GEMM rows a launch tiles: the destination pixels, or (class-major form) the pixels of ONE of the four classes
-static long long xp_rows(const X3PArgs& a) {
-  return a.lat == 1 ? (long long)a.segB[0] * (a.segOH[0] / 2) * (a.segOW[0] / 2) : a.M;
-}
+// every instance of conv_x3p_kernel: (TAPS, NBW, LAT, PRE) -- the list is the launch switch
+#define X3P_INSTANCES(X) \
+  X(1, 4, 0, 0) X(1, 4, 0, 1) X(1, 4, 0, 2) X(1, 8, 0, 0) X(9, 4, 0, 0) X(9, 8, 0, 0) X(4, 4, 1, 0) X(4, 8, 1, 0) X(1, 4, 2, 0) X(1, 8, 2, 0)
 
-// Operand-prefetch form (conv_x3p_kernel PRE): dense 1x1 launches with EXACTLY one of residual (-> 1) / ReLU mask (-> 2), else 0.
-// AOD_X3P_PRE=0 disables.
-static int xp_pre(const X3PArgs& a) {
-  const char* e = getenv("AOD_X3P_PRE");
-  if (e && e[0] == '0') return 0;
-  if (a.taps != 1 || a.lat != 0 || a.ngroups > 1 || a.stride != 1) return 0;
-  const bf16_t* mask = a.ngroups == 1 ? a.grp[0].mask : a.mask;
-  if ((a.res != nullptr) == (mask != nullptr)) return 0;
-  return a.res ? 1 : 2;
-}
-
-// 256-column tiles (half the pixel bytes per MFMA, twice the MFMAs per barrier) when they still give at least three quarters of the CUs a
-// tile; AOD_X3P_BN=128 / 256 forces
-static bool xp_wide(const X3PArgs& a) {
-  if (xp_pre(a)) return false;                  // (the prefetch form exists for the 128-column tile: 64 accumulators leave room for the operand)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  if (!g_x3p_cus[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    g_x3p_cus[dev] = n;
+int aod_conv_x3p_launch(const X3PArgs& a, const ConvPlan& plan, hipStream_t st) {
+  const int nbw = plan.wide ? 8 : 4;
+#define X(TAPS, NBW, LAT, PRE)                                                          \
+  if (plan.taps == TAPS && nbw == NBW && plan.lat == LAT && plan.pre == PRE) {          \
+    xp_launch<TAPS, NBW, LAT, PRE>(a, plan.grid, st);                                   \
+    AOD_LAUNCH_CHECK();                                                                 \
+    __atomic_add_fetch(&g_x3p_count, 1, __ATOMIC_RELAXED);                              \
+    return 0;                                                                           \
   }
-  if (a.N % 256 != 0) return false;
-  const char* fbn = getenv("AOD_X3P_BN");
-  if (fbn) return atoi(fbn) == 256;
-  const int ng = a.ngroups > 1 ? a.ngroups : 1;
-  return ((xp_rows(a) + XP_BM - 1) / XP_BM) * (a.N / 256) * ng * (a.lat == 1 ? 4 : 1) >= (long long)g_x3p_cus[dev] * 3 / 4;
-}
-
-int aod_conv_x3p_wants(const X3PArgs& a, int deterministic_colsum) {
-  const char* now = getenv("AOD_X3P");                 // (read per call: tests switch it in-process)
-  if (now && now[0] == '0') return 0;
-  if (a.taps != 1 && a.taps != 9) return 0;
-  if (a.taps == 9 && a.S != 3) return 0;
-  if (a.N % 128 != 0 || a.C % 64 != 0 || a.M <= 0) return 0;
-  // AOD_X3P_DGRAD=0 (parallel.GradSync sets it when gradients are all-reduced under the backward pass): backward launches stay with the general
-  // kernel.  A persistent grid of one 160-KB-LDS workgroup per CU assumes every CU is free; RCCL's channel workgroups hold some for milliseconds,
-  // and the workgroups that cannot start then run AFTER the others -- a one-round launch takes twice as long -- where the general kernel's many
-  // small workgroups just lose those CUs' share.  Forward and scoring launches never run beside a collective.
-  if (a.transposed) { const char* dg = getenv("AOD_X3P_DGRAD"); if (dg && dg[0] == '0') return 0; }
-  if (a.lat == 1) {
-    // class-major stride-2 dgrad: 3x3, pad 1, no dilation, one segment with an even map whose halves are the dZ map
-    const char* lt = getenv("AOD_X3P_LATTICE");
-    if (lt && lt[0] == '0') return 0;
-    if (!(a.transposed && a.stride == 2 && a.taps == 9 && a.pad == 1 && a.dil == 1 && a.nseg == 1 && a.ngroups <= 1)) return 0;
-    if ((a.segOH[0] & 1) || (a.segOW[0] & 1) || a.segH[0] * 2 != a.segOH[0] || a.segW[0] * 2 != a.segOW[0]) return 0;
-  } else if (a.lat == 2) {
-    const char* lt = getenv("AOD_X3P_LATTICE");
-    if (lt && lt[0] == '0') return 0;
-    if (!(a.transposed && a.stride == 1 && a.taps == 1 && a.pad == 0 && a.nseg == 1 && a.ngroups <= 1 && a.up_w > 0)) return 0;
-  } else if (a.transposed && a.stride != 1) return 0;
-  if (deterministic_colsum) return 0;                  // ordered column sums stay with the general kernel (determinism.hip)
-  if ((long long)a.K * 2 * a.N >= 0x7fffffffll) return 0;
-  // a tile needs a K loop long enough to amortise the one-workgroup-per-CU structure (its epilogue runs beside nothing but the loaders' next
-  // stages): from ~24 K-steps of a 128-column tile on the persistent form wins -- every 3x3 layer (36+ steps), the 1024 -> 256 reduce / lateral
-  // 1x1 convs (32 steps: 37.0 -> 28.7 us), retina_cls' dgrad (54: 243 -> 230 us) -- and a 256-column tile's K-step carries twice the matrix
-  // work per barrier, so 12 of those do (the 512 -> 256 lateral and the 512 -> 1024 stride-2 downsample conv: 57.7 -> 55.0, 57.0 -> 54.3 us).
-  // Below that the general kernel's two workgroups per CU win (the expand 1x1 convs with their residual, 4 - 16 steps: 45.5 vs 49.9,
-  // 34.0 vs 36.8 us; retina_reg / retina_L dgrads with 18 / 9 steps of a 128-column tile: 106 vs 116, 76 vs 88 us) -- a residual epilogue is
-  // only taken from 24 steps on.  The class-major form is judged by its average class (9 taps over 4 classes).
-  // profiles/r06_x3p_micro.txt; AOD_X3P_MIN_STEPS overrides the threshold.
-  {
-    const char* ms = getenv("AOD_X3P_MIN_STEPS");
-    const int thr = ms ? atoi(ms) : 24;
-    const int steps = a.lat == 1 ? 9 * (a.C >> 6) / 4 : a.taps * (a.C >> 6);
-    // (the operand-prefetch form, xp_pre, does not change this: with the residual requested before the K loop the 8-step expand conv of
-    // layer 3 still takes 49.5 us against the general kernel's 44.9 -- its K loop is bound by what 96 KB of ring can keep in flight against
-    // the memory latency under the residual / store traffic, 1.08 us per K-step by the stamps -- and only the 4-step layer-2 expand conv wins,
-    // 73.8 against 80.0 us; AOD_X3P_PRE_MIN_STEPS lowers the threshold for launches that qualify for the form)
-    const char* pms = getenv("AOD_X3P_PRE_MIN_STEPS");
-    if (pms && xp_pre(a)) { if (steps < atoi(pms)) return 0; }
-    else
-    if (a.lat != 1 && (steps * (xp_wide(a) ? 2 : 1) < thr || (a.res && steps < thr))) return 0;
-    if (a.lat == 1 && steps * (xp_wide(a) ? 2 : 1) < thr / 2) return 0;          // (the general kernel's class-major launches are its slowest: 86 - 127 TFLOP/s)
-  }
-  long long prev = 0;
-  for (int i = 0; i < a.nseg; ++i) {
-    const long long rows = a.seg_mend[i] - prev;
-    prev = a.seg_mend[i];
-    if (rows >= (1ll << 22)) return 0;                               // float-reciprocal row decode
-    if (i + 1 < a.nseg && rows % XP_BM != 0) return 0;               // a tile must not straddle two segments
-    if (a.seg_dst0[i] + rows >= (1ll << 31)) return 0;
-  }
-  // one 8-wave workgroup per CU: worth it from ~ a round of the chip on; below that the general kernel's smaller tiles fill more CUs
-  const char* mint = getenv("AOD_X3P_MIN_TILES");
-  const int ng = a.ngroups > 1 ? a.ngroups : 1;
-  const long long tiles = ((xp_rows(a) + XP_BM - 1) / XP_BM) * (a.N / 128) * ng * (a.lat == 1 ? 4 : 1);
-  if (tiles < (mint ? atoll(mint) : 192)) return 0;
-  return 1;
-}
-
-int aod_conv_x3p_launch(const X3PArgs& a0, hipStream_t st) {
-  X3PArgs a = a0;
-  if (a.ngroups < 1) {
-    a.ngroups = 1;
-    a.grp[0].x = a.x; a.grp[0].w = a.w; a.grp[0].y = a.y; a.grp[0].shift = a.pre_shift; a.grp[0].mask = a.mask; a.grp[0].colsum = a.colsum;
-  }
-  { const char* r = getenv("AOD_X3P_ROT"); a.rot = r ? atoi(r) : 0; }
-  const bool wide = xp_wide(a);                 // (also resolves the CU count of the current device)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  const int ncu = g_x3p_cus[dev] ? g_x3p_cus[dev] : 256;
-  a.tiles_m = (int)((xp_rows(a) + XP_BM - 1) / XP_BM);
-  a.tiles_n = a.N / (wide ? 256 : 128);
-  const long long ntiles = (long long)a.tiles_m * a.tiles_n * a.ngroups * (a.lat == 1 ? 4 : 1);
-  const int grid = (int)(ntiles < ncu ? ntiles : ncu);
-  if (a.lat == 1) { if (wide) xp_launch<4, 8, 1>(a, grid, st); else xp_launch<4, 4, 1>(a, grid, st); }
-  else if (a.lat == 2) { if (wide) xp_launch<1, 8, 2>(a, grid, st); else xp_launch<1, 4, 2>(a, grid, st); }
-  else if (a.taps == 1) {
-    const int pre = xp_pre(a);
-    if (wide) xp_launch<1, 8>(a, grid, st);
-    else if (pre == 1) xp_launch<1, 4, 0, 1>(a, grid, st);
-    else if (pre == 2) xp_launch<1, 4, 0, 2>(a, grid, st);
-    else xp_launch<1, 4>(a, grid, st);
-  }
-  else { if (wide) xp_launch<9, 8>(a, grid, st); else xp_launch<9, 4>(a, grid, st); }
-  AOD_LAUNCH_CHECK();
-  __atomic_add_fetch(&g_x3p_count, 1, __ATOMIC_RELAXED);
-  return 0;
+  X3P_INSTANCES(X)
+#undef X
+  AOD_CHECK_ARG(false, "conv (x3p): no kernel instance for taps %d, %d-column tiles, lattice %d, prefetch %d", plan.taps, 32 * nbw, plan.lat, plan.pre);
+  return -1;
 }
 
 extern "C" int64_t aod_conv_x3p_count(void) { return (int64_t)__atomic_load_n(&g_x3p_count, __ATOMIC_RELAXED); }

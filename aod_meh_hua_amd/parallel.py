@@ -77,7 +77,7 @@ class GradSync:
         self.bucket_elems = bucket_mb * (1 << 20) // 4
         self._ents = {}
         # the all-reduces of this object run on RCCL's stream BESIDE the backward pass: keep the backward launches off the persistent
-        # one-workgroup-per-CU conv kernel (csrc/conv_x3p.hip, aod_conv_x3p_wants: a grid that assumes every CU free doubles its time when RCCL's
+        # one-workgroup-per-CU conv kernel (csrc/conv_x3p.hip; the rule is in csrc/conv.hip plan_x3p: a grid that assumes every CU free doubles its time when RCCL's
         # channel workgroups hold a few); forward and scoring launches are not concerned.  An explicit AOD_X3P_DGRAD in the environment wins.
         if is_dist() and dist.get_world_size() > 1:
             import os

@@ -89,6 +89,26 @@ int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const void* w_pa
                   const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
                   aod_stream_t stream);
 
+/* Which kernel a launch would run on -- the decision aod_conv2d_ws (ngroups = 0) or aod_conv2d_grouped (ngroups = 1 .. 4, below) takes for
+ * this descriptor, as data.  Host logic only: nothing is enqueued and no device is needed (without one the CU count counts as 256).
+ * operand_flags: which optional operands the launch would carry (grouped: whether ANY group has the mask / column sum);
+ * AOD_CONV_RES_IS_DST: a residual that is the destination itself (the in-place gradient accumulation).  The plan follows the same
+ * environment switches, aod_set_deterministic and aod_set_pointwise_mode as the launch.  kind 0: an empty launch (no rows). */
+enum { AOD_CONV_PLAN_PW_STREAM = 1,   /* the streaming 1x1 GEMM (csrc/pointwise.hip); no further fields                                  */
+       AOD_CONV_PLAN_SPLIT_K = 2,     /* conv_igemm_kernel<bm, bn, nt, ops, grouped, stages, x3> over ksplit K slices + the finalize pass */
+       AOD_CONV_PLAN_X3P = 3,         /* conv_x3p_kernel<taps, wide ? 8 : 4, lat, pre> on grid workgroups (csrc/conv_x3p.hip)             */
+       AOD_CONV_PLAN_IGEMM = 4 };     /* conv_igemm_kernel<bm, bn, nt, ops, grouped, stages, x3>                                          */
+enum { AOD_CONV_HAS_PRE_SCALE = 1, AOD_CONV_HAS_PRE_SHIFT = 2, AOD_CONV_HAS_RES = 4, AOD_CONV_RES_IS_DST = 8, AOD_CONV_HAS_MASK = 16,
+       AOD_CONV_HAS_POST_SCALE = 32, AOD_CONV_HAS_ZRAW = 64, AOD_CONV_HAS_COLSUM = 128, AOD_CONV_HAS_WORKSPACE = 256 };
+typedef struct {
+  int32_t kind;
+  int32_t bm, bn, nt, ops, stages, x3, grouped;   /* tile rows x columns, threads, epilogue operands (0 none, 1 mask, 2 residual + mask), LDS stages */
+  int32_t ksplit;
+  int32_t taps, wide, pre, lat, grid;             /* the kernel's TAPS (4: class-major form), 256-column tiles, operand prefetch 0 / 1 (residual) /
+                                                     2 (mask), lattice 0 / 1 (class-major stride-2 dgrad) / 2 (in-place 1x1 stride-2 dgrad), workgroups */
+} aod_conv_plan_t;
+int aod_conv2d_plan(const aod_conv_desc_t* desc, int ngroups, unsigned operand_flags, aod_conv_plan_t* out);
+
 /* Reference-precision (x3) launches of aod_conv2d(_ws) with an X-layout destination, N % 128 == 0, a 1x1 or 3x3 filter (forward at any
  * stride, dgrad at stride 1), segments that are whole multiples of 128 rows (but the last), at least ~192 tiles of 128 x 128 and at least
  * 24 K-steps (of 32 channels x 1 tap) per tile -- the 3x3 convs and the deep reduce / lateral 1x1 convs of the trainable backbone stages and

@@ -328,3 +328,44 @@ def test_x3p_whole_training_step_equals_the_general_kernels(monkeypatch):
         g0 = out['0'][1][k]
         worst = max(worst, _err(g1, g0))
     assert worst < 2e-6, worst
+
+
+def test_the_reported_plan_is_the_plan_the_launcher_follows(monkeypatch):
+    """aod_conv2d_plan (the dispatcher's decision as data, tests/test_conv_plan.py) against aod_conv2d_ws itself on random operands: the
+    persistent kernel's launch counter advances exactly when the plan says X3P -- a persistent-kernel plan, a 128 x 128 four-wave plan (one
+    K-step: below the persistent kernel's threshold; 16 x 32 tiles fill the device) and a split-K plan (72 K-steps over 16 x 16 outputs)."""
+    import ctypes as C
+    from aod_meh_hua_amd import _C
+    lib = _C.lib
+    X3P_KIND, SPLIT_K, IGEMM = 3, 2, 4
+    g = torch.Generator(device='cuda').manual_seed(31)
+    shapes = [  # B, H, W, logical C, N, k, environment, workspace, expected kind / tile
+        (2, 32, 32, 256, 128, 3, {'AOD_X3P_MIN_TILES': '1', 'AOD_X3P_MIN_STEPS': '1'}, False, X3P_KIND, None),
+        (2, 32, 32, 32, 4096, 1, {}, False, IGEMM, (128, 128, 256, 2)),
+        (8, 16, 16, 256, 128, 3, {}, True, SPLIT_K, (128, 128, 256, 2)),
+    ]
+    for B, H, W, Cl, N, k, env, want_ws, kind, tile in shapes:
+        for key in ('AOD_X3P_MIN_TILES', 'AOD_X3P_MIN_STEPS'):
+            monkeypatch.delenv(key, raising=False)
+        for key, v in env.items():
+            monkeypatch.setenv(key, v)
+        M, Cp = B * H * W, 2 * Cl
+        d = _C.ConvDesc()
+        d.C, d.N, d.R, d.S, d.stride, d.pad, d.dil, d.nseg, d.x3 = Cp, N, k, k, 1, k // 2, 1, 1, 1
+        d.seg[0] = _C.ConvSeg(B, H, W, H, W, 0, 0)
+        x = torch.randn(M, Cp, device='cuda', generator=g).bfloat16()
+        w = (torch.randn(N, k * k * Cp, device='cuda', generator=g) / (k * k * Cl) ** 0.5).bfloat16()
+        y = torch.empty(M, 2 * N, device='cuda', dtype=torch.bfloat16)
+        nws = lib.aod_conv2d_ws_bytes(C.byref(d)) if want_ws else 0
+        assert (nws > 0) == want_ws
+        ws = torch.empty(max(nws // 4, 1), device='cuda') if want_ws else None
+        plan = _C.ConvPlan()
+        _C.call('aod_conv2d_plan', C.byref(d), 0, 256 if want_ws else 0, C.byref(plan))
+        assert plan.kind == kind, (plan.kind, kind)
+        if tile is not None:
+            assert (plan.bm, plan.bn, plan.nt, plan.stages) == tile and plan.x3 == 1
+        n0 = lib.aod_conv_x3p_count()
+        _C.call('aod_conv2d_ws', C.byref(d), _C.ptr(x), _C.ptr(w), _C.ptr(y), None, None, None, None, None, None, None, _C.ptr(ws), nws, _C.stream())
+        torch.cuda.synchronize()
+        assert lib.aod_conv_x3p_count() - n0 == (1 if plan.kind == X3P_KIND else 0)
+        assert bool(torch.isfinite(y.float()).all())
