@@ -138,6 +138,8 @@ _SIGS = {
     'aod_x3_l2norm_fwd': (C.c_int, [P, P, P, I64, I32, F32, P]),
     'aod_x3_l2norm_bwd': (C.c_int, [P, P, P, P, P, I64, I32, F32, P]),
     'aod_sgd_multi': (C.c_int, [P, P, P, P, I32, F32, P, F32, F32, I32, F32, P]),
+    'aod_sgd_multi_clipped': (C.c_int, [P, P, P, P, I32, F32, P, F32, F32, I32, F32, P, P]),
+    'aod_grad_norm_multi': (C.c_int, [P, P, I32, F32, F32, I32, P, I64, P, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -1,5 +1,6 @@
 """train_detector_SSL (mmdet/apis/train_Lambda.py:37-109): loaders, MMDataParallel wrap, the main SGD optimizer with
-the MEH parameters removed + `optimizer_L` for the MEH parameters, training hooks (OptimizerHook dropped), run_SSL."""
+the MEH parameters removed + `optimizer_L` for the MEH parameters, training hooks (OptimizerHook dropped: its one job, gradient
+clipping, happens inside FusedSGD.step()), run_SSL."""
 from operator import itemgetter
 
 import torch
@@ -19,6 +20,24 @@ def RemoveParamFromOptim(optimizer, model, param_name):
     optimizer.param_groups[0]['params'] = [p for p in params if id(p) not in targetIDs]
 
 
+def build_optimizers(model, cfg):
+    """The two optimizers of run_iter (train_Lambda.py:54-61): SGD over everything but the MEH parameters, and `optimizer_L` over those.
+    `optimizer_config.grad_clip` (mmcv OptimizerHook's argument; the hook itself is removed below, as in the reference) and
+    `optimizer_config.skip_nonfinite` go to BOTH: each clips the parameter set it steps -- the main and the MEH step follow separate
+    backward passes."""
+    oc = cfg.get('optimizer_config', None) or {}
+    clip = dict(grad_clip=oc.get('grad_clip'), skip_nonfinite=bool(oc.get('skip_nonfinite', False)))
+    module = model.module if hasattr(model, 'module') else model
+    optimizer = build_optimizer(model, cfg.optimizer, **clip)
+    head = module.bbox_head
+    meh_names = getattr(head, 'L_names', ['retina_L', 'L_convs'])      # train_Lambda.py:55-56 / train_SSD_L.py:42
+    for name in meh_names:
+        RemoveParamFromOptim(optimizer, module, name)
+    meh_params = [p for n in meh_names for p in getattr(head, n).parameters()]
+    optimizer_L = FusedSGD(meh_params, lr=cfg.optimizer.lr, momentum=cfg.optimizer.momentum, weight_decay=cfg.optimizer.weight_decay, **clip)
+    return optimizer, optimizer_L
+
+
 def train_detector_SSL(model, dataset, cfg, distributed=False, validate=False, timestamp=None, meta=None):
     logger = get_root_logger(cfg.log_level)
     from ..datasets import apply_device_transforms
@@ -29,15 +48,9 @@ def train_detector_SSL(model, dataset, cfg, distributed=False, validate=False, t
     dev = torch.device('cuda', torch.cuda.current_device())
     model = MMDataParallel(model.to(dev), device_ids=cfg.gpu_ids)
     broadcast_model(model.module)
-    optimizer = build_optimizer(model, cfg.optimizer)
-    head = model.module.bbox_head
-    meh_names = getattr(head, 'L_names', ['retina_L', 'L_convs'])      # train_Lambda.py:55-56 / train_SSD_L.py:42
-    for name in meh_names:
-        RemoveParamFromOptim(optimizer, model.module, name)
+    optimizer, optimizer_L = build_optimizers(model, cfg)
     runner = build_runner(cfg.runner, default_args=dict(model=model, optimizer=optimizer, work_dir=cfg.work_dir, logger=logger, meta=meta))
-    meh_params = [p for n in meh_names for p in getattr(head, n).parameters()]
-    runner.optimizer_L = FusedSGD(meh_params, lr=cfg.optimizer.lr,
-                                  momentum=cfg.optimizer.momentum, weight_decay=cfg.optimizer.weight_decay)
+    runner.optimizer_L = optimizer_L
     runner.timestamp = timestamp
     runner.register_training_hooks(cfg.lr_config, cfg.optimizer_config, cfg.checkpoint_config, cfg.log_config, cfg.get('momentum_config', None))
     for i, hook in enumerate(runner.hooks):

@@ -309,9 +309,18 @@ struct SgdChunk {
   long long n[48];
   int count;
 };
-__global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdChunk c, int blocks_per_tensor, float lr_arg, const float* __restrict__ lr_dev,
-                                                        float momentum, float wd, int first_step, float grad_scale) {
+// (four waves per SIMD asked for explicitly: with the coefficient argument the allocator otherwise settles at 130 VGPRs -- it was 126 -- and
+// 128 is where the fourth wave is lost)
+__global__ __launch_bounds__(256, 4) void sgd_multi_kernel(const SgdChunk c, int blocks_per_tensor, float lr_arg, const float* __restrict__ lr_dev,
+                                                        float momentum, float wd, int first_step, float grad_scale_arg,
+                                                        const float* __restrict__ coef_dev) {
   const float lr = lr_dev ? *lr_dev : lr_arg;      // device-resident learning rate: a captured launch follows the schedule
+  // device-resident clip coefficient (grad_clip_finalize_kernel): a captured launch clips by the norm of the gradients it is replayed on.
+  // Negative = the skip sentinel (non-finite norm with skip_nonfinite): p and the momentum buffer stay untouched.  Without a pointer the
+  // scale is grad_scale * 1.0f == grad_scale: the unclipped path keeps its bits.
+  const float coef = coef_dev ? *coef_dev : 1.0f;
+  if (coef < 0.f) return;
+  const float grad_scale = grad_scale_arg * coef;
   const int ti = blockIdx.x / blocks_per_tensor, bi = blockIdx.x % blocks_per_tensor;
   float* p = c.p[ti];
   const float* g = c.g[ti];
@@ -359,9 +368,9 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdChunk c, int bl
     p[i] = pv - lr * b;
   }
 }
-extern "C" int aod_sgd_multi(void* const* params, void* const* grads, void* const* moms, const int64_t* sizes, int ntensors,
-                             float lr, const float* lr_dev, float momentum, float weight_decay, int first_step, float grad_scale,
-                             aod_stream_t stream) {
+extern "C" int aod_sgd_multi_clipped(void* const* params, void* const* grads, void* const* moms, const int64_t* sizes, int ntensors,
+                                     float lr, const float* lr_dev, float momentum, float weight_decay, int first_step, float grad_scale,
+                                     const float* coef_dev, aod_stream_t stream) {
   AOD_CHECK_ARG(params && grads && moms && sizes && ntensors >= 0, "sgd_multi: bad args");
   for (int s0 = 0; s0 < ntensors; s0 += 48) {
     SgdChunk c;
@@ -375,8 +384,129 @@ extern "C" int aod_sgd_multi(void* const* params, void* const* grads, void* cons
     int bpt = (int)((mx + 256 * 16 - 1) / (256 * 16));
     if (bpt < 1) bpt = 1;
     if (bpt > 96) bpt = 96;
-    hipLaunchKernelGGL(sgd_multi_kernel, dim3(c.count * bpt), dim3(256), 0, (hipStream_t)stream, c, bpt, lr, lr_dev, momentum, weight_decay, first_step, grad_scale);
+    hipLaunchKernelGGL(sgd_multi_kernel, dim3(c.count * bpt), dim3(256), 0, (hipStream_t)stream, c, bpt, lr, lr_dev, momentum, weight_decay, first_step, grad_scale,
+                       coef_dev);
   }
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int aod_sgd_multi(void* const* params, void* const* grads, void* const* moms, const int64_t* sizes, int ntensors,
+                             float lr, const float* lr_dev, float momentum, float weight_decay, int first_step, float grad_scale,
+                             aod_stream_t stream) {
+  return aod_sgd_multi_clipped(params, grads, moms, sizes, ntensors, lr, lr_dev, momentum, weight_decay, first_step, grad_scale, nullptr, stream);
+}
+
+// ---------------------------------------------------------------- gradient-norm clipping (mmcv OptimizerHook.clip_grads = torch clip_grad_norm_, norm_type 2)
+// Two launches ahead of the SGD launches: per-block partial sums of (g * grad_scale)^2, then one workgroup that adds them in a fixed order
+// and leaves {total_norm, coef, skipped_steps, reserved} in device memory, where sgd_multi_kernel reads coef.  No atomics anywhere: the
+// coefficient is a pure function of the gradients (deterministic mode; every rank of a data-parallel run derives the same value).
+struct GradChunk {
+  const float* g[48];
+  long long n[48];
+  int count;
+};
+__global__ __launch_bounds__(256) void grad_sqsum_multi_kernel(const GradChunk c, int blocks_per_tensor, float grad_scale, float* __restrict__ partials) {
+  __shared__ float red[4];
+  const int ti = blockIdx.x / blocks_per_tensor, bi = blockIdx.x % blocks_per_tensor;
+  const float* g = c.g[ti];
+  const long long n = c.n[ti];
+  // the SGD kernel's access pattern: 16-B loads, four in flight per thread, the scalar path for a misaligned pointer and the n % 4 tail
+  const bool vec = (((size_t)g) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  const long long stride = (long long)blocks_per_tensor * 256;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (long long i0 = (long long)bi * 256 + threadIdx.x; i0 < n4; i0 += 4 * stride) {
+    f32x4 gv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long i = i0 + k * stride;
+      gv[k] = i < n4 ? reinterpret_cast<const f32x4*>(g)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float v = gv[k][u] * grad_scale;
+        acc[k] += v * v;
+      }
+    }
+  }
+  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  for (long long i = n4 * 4 + (long long)bi * 256 + threadIdx.x; i < n; i += stride) {
+    const float v = g[i] * grad_scale;
+    s += v * v;
+  }
+  s = wave_sum(s);                                   // (xor butterfly: the same tree in every lane, whatever the scheduling)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// state: [0] total_norm  [1] coef = min(1, max_norm / (total_norm + 1e-6)) (torch's formula)  [2] skipped_steps  [3] reserved
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const float* __restrict__ partials, int nparts, float max_norm, int skip_nonfinite,
+                                                                 float* __restrict__ state) {
+  __shared__ double red[256];
+  double s = 0.0;                                    // at most a few thousand values: double keeps the order-fixed sum's error out of the norm
+  for (int i = threadIdx.x; i < nparts; i += 256) s += (double)partials[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(red[0]);
+    float coef;
+    if (!(norm <= 3.402823466e38f)) {                // inf or NaN (fminf would drop a NaN and clip to 1)
+      if (skip_nonfinite) {
+        coef = -1.0f;                                // sgd_multi_kernel returns before touching p / momentum
+        state[2] += 1.0f;
+      } else {
+        coef = __builtin_nanf("");                   // the update is non-finite, like clip_grad_norm_(error_if_nonfinite=False)
+      }
+    } else {
+      coef = max_norm / (norm + 1e-6f);
+      if (coef > 1.0f) coef = 1.0f;
+    }
+    state[0] = norm;
+    state[1] = coef;
+  }
+}
+extern "C" int aod_grad_norm_multi(void* const* grads, const int64_t* sizes, int ntensors, float grad_scale, float max_norm, int flags,
+                                   float* partials_ws, int64_t ws_capacity, float* state, aod_stream_t stream) {
+  AOD_CHECK_ARG(grads && sizes && ntensors >= 0 && partials_ws && state && ws_capacity >= 0, "grad_norm_multi: bad args");
+  AOD_CHECK_ARG(max_norm > 0.f, "grad_norm_multi: max_norm must be positive");
+  // first pass, no launch: every pointer / size checked and the partials counted against the workspace
+  long long total = 0;
+  for (int s0 = 0; s0 < ntensors; s0 += 48) {
+    const int count = ntensors - s0 < 48 ? ntensors - s0 : 48;
+    long long mx = 0;
+    for (int i = 0; i < count; ++i) {
+      AOD_CHECK_ARG(grads[s0 + i], "grad_norm_multi: null tensor pointer");
+      AOD_CHECK_ARG(sizes[s0 + i] >= 0, "grad_norm_multi: negative size");
+      if (sizes[s0 + i] > mx) mx = sizes[s0 + i];
+    }
+    long long bpt = (mx + 256 * 16 - 1) / (256 * 16);
+    if (bpt < 1) bpt = 1;
+    if (bpt > 96) bpt = 96;
+    total += count * bpt;
+  }
+  AOD_CHECK_ARG(total <= ws_capacity, "grad_norm_multi: workspace too small (%lld partials, capacity %lld)", total, (long long)ws_capacity);
+  long long base = 0;
+  for (int s0 = 0; s0 < ntensors; s0 += 48) {
+    GradChunk c;
+    c.count = ntensors - s0 < 48 ? ntensors - s0 : 48;
+    long long mx = 0;
+    for (int i = 0; i < c.count; ++i) {
+      c.g[i] = (const float*)grads[s0 + i]; c.n[i] = sizes[s0 + i];
+      if (c.n[i] > mx) mx = c.n[i];
+    }
+    int bpt = (int)((mx + 256 * 16 - 1) / (256 * 16));
+    if (bpt < 1) bpt = 1;
+    if (bpt > 96) bpt = 96;
+    hipLaunchKernelGGL(grad_sqsum_multi_kernel, dim3(c.count * bpt), dim3(256), 0, (hipStream_t)stream, c, bpt, grad_scale, partials_ws + base);
+    base += (long long)c.count * bpt;
+  }
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials_ws, (int)total, max_norm, flags & 1, state);
   AOD_LAUNCH_CHECK();
   return 0;
 }

@@ -68,9 +68,19 @@ class MyEpochBasedRunnerLambda(BaseRunner):
             outputs = loss
         else:
             outputs = self.model.val_step(data_batch, self.optimizer, **kwargs)
+        if train_mode and self.batch_processor is None and 'log_vars' in outputs:
+            self._log_grad_norms(outputs['log_vars'])
         if 'log_vars' in outputs:
             self.log_buffer.update(outputs['log_vars'], outputs['num_samples'])
         self.outputs = outputs
+
+    def _log_grad_norms(self, log_vars):
+        """optimizer_config.grad_clip: the total gradient norms the two steps of this iteration (eager or replayed) clipped by, as 0-d
+        device copies of FusedSGD.clip_state() -- LogBuffer syncs at the logging interval.  No keys when clipping is off."""
+        for key, opt in (('grad_norm', self.optimizer), ('grad_norm_L', getattr(self, 'optimizer_L', None))):
+            state = opt.clip_state() if hasattr(opt, 'clip_state') else None
+            if state is not None:
+                log_vars[key] = state[0].clone()
 
     def _graphed_iter(self, data_batch, kwargs):
         """HIP-graph replay of the iteration (graphs.GraphedTrainStep) once the input shape repeats; False -> run it eagerly.

@@ -500,6 +500,21 @@ int aod_image_xform(const void* src_pack, const aod_image_xform_item_t* items_de
 int aod_sgd_multi(void* const* params, void* const* grads, void* const* moms, const int64_t* sizes, int ntensors,
                   float lr, const float* lr_dev, float momentum, float weight_decay, int first_step, float grad_scale,
                   aod_stream_t stream);
+/* aod_sgd_multi with a device-resident clip coefficient (nullable; state + 1 of aod_grad_norm_multi): the effective gradient scale is
+ * grad_scale * *coef_dev.  A negative coefficient is the skip sentinel: the launch leaves params and momentum buffers untouched.
+ * coef_dev == NULL is aod_sgd_multi, bit for bit. */
+int aod_sgd_multi_clipped(void* const* params, void* const* grads, void* const* moms, const int64_t* sizes, int ntensors,
+                          float lr, const float* lr_dev, float momentum, float weight_decay, int first_step, float grad_scale,
+                          const float* coef_dev, aod_stream_t stream);
+/* Gradient-norm clipping (mmcv OptimizerHook.clip_grads -> torch.nn.utils.clip_grad_norm_, norm_type 2) without a host round trip:
+ * total_norm = sqrt(sum over all tensors of (g * grad_scale)^2), coef = min(1, max_norm / (total_norm + 1e-6)).  One launch per <= 48
+ * tensors writes per-block fp32 partial sums to partials_ws (ws_capacity floats; 96 * ntensors always suffices), one workgroup adds them in
+ * a fixed order in double: no atomics, the result does not depend on scheduling.  state (device, 4 fp32, zeroed once by the caller):
+ * {total_norm, coef, skipped_steps, reserved}.  A non-finite norm gives coef = NaN (the update is non-finite, as with
+ * clip_grad_norm_(error_if_nonfinite=False)) or, with flags bit 0 (skip_nonfinite), coef = -1 (aod_sgd_multi_clipped skips the update) and
+ * skipped_steps += 1.  The gradients themselves are not modified. */
+int aod_grad_norm_multi(void* const* grads, const int64_t* sizes, int ntensors, float grad_scale, float max_norm, int flags,
+                        float* partials_ws, int64_t ws_capacity, float* state, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
