@@ -24,6 +24,12 @@ class Uncertainty_fns:
     def Entropy_NMS(cfg, *args, **kwargs):
         model, dataloader = args
         model.eval()
+        # test_cfg.hua_estimator ('mc' | 'closed'): forwarded only when it selects something else than the default, so that a default run
+        # keeps its kwargs -- and with them the key of its captured scoring graph
+        tc = getattr(getattr(model, 'module', model), 'test_cfg', None)
+        est = tc.get('hua_estimator') if hasattr(tc, 'get') else getattr(tc, 'hua_estimator', None)
+        if est and est != 'mc' and 'hua_estimator' not in kwargs:
+            kwargs['hua_estimator'] = est
         unc = single_gpu_uncertainty(model, dataloader, isUnc=cfg.uncertainty_type, uPool=cfg.uncertainty_pool,
                                      uPool2=cfg.uncertainty_pool2, **kwargs)
         return unc.cpu() if torch.is_tensor(unc) else [u.cpu() if torch.is_tensor(u) else u for u in unc]
@@ -177,12 +183,18 @@ def single_gpu_uncertainty(model, data_loader, **kwargs):
 
 @torch.no_grad()
 def single_gpu_test(model, data_loader, show=False, out_dir=None, show_score_thr=0.3, **kwargs):
-    """test.py:138-195 (detection results for evaluation; isEval=True)."""
+    """test.py:138-195 (detection results for evaluation; isEval=True).  detUnc=True: returns (results, unc_results) where
+    unc_results[i][c] is a (k, 2) float32 array (aleatoric, epistemic), row-aligned with results[i][c]; the box arrays keep five columns
+    (eval_map reads the score from column -1)."""
     model.eval()
-    results = []
+    results, unc_results = [], []
     for data in data_loader:
         data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
         kw = dict(kwargs)
         kw.setdefault('isUnc', False)              # EvalHook forwards the whole `evaluation` dict (interval popped): isUnc, metric, ...
-        results.extend(model(return_loss=False, rescale=True, isEval=True, **data, **kw))
-    return results
+        out = model(return_loss=False, rescale=True, isEval=True, **data, **kw)
+        if kw.get('detUnc'):
+            results.extend(out[0]), unc_results.extend(out[1])
+        else:
+            results.extend(out)
+    return (results, unc_results) if kwargs.get('detUnc') else results

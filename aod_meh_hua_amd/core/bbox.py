@@ -192,3 +192,13 @@ def bbox2result(bboxes, labels, num_classes):
     if isinstance(bboxes, torch.Tensor):
         bboxes, labels = bboxes.detach().cpu().numpy(), labels.detach().cpu().numpy()
     return [bboxes[labels == i, :] for i in range(num_classes)]
+
+
+def unc2result(det_unc, labels, num_classes):
+    """Per-detection (aleatoric, epistemic) rows split by class exactly as bbox2result splits the boxes: entry c is (k_c, 2) float32,
+    row-aligned with bbox2result(...)[c]."""
+    if det_unc.shape[0] == 0:
+        return [np.zeros((0, 2), dtype=np.float32) for _ in range(num_classes)]
+    if isinstance(det_unc, torch.Tensor):
+        det_unc, labels = det_unc.detach().cpu().numpy(), labels.detach().cpu().numpy()
+    return [det_unc[labels == i, :] for i in range(num_classes)]

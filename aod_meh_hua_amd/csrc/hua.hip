@@ -11,6 +11,9 @@
 // The RNG stream is keyed by (seed, image id, anchor id, object id, sample, class, attempt): results do not
 // depend on batch composition or on how the pool is sharded over GPUs.  The same algorithm is restated in
 // numpy in oracle/hua.py (philox_*), which the tests compare against value by value.
+// Opt-in alternatives (aod_hua_score_ex): H2' hua_closed_kernel replaces the sampler by the closed form of the Monte-Carlo limit (one wave per
+// pair, ~20 digammas instead of ~10^4 gamma variates, no seed); H3' a second instance of the reduce kernel also writes, per detection row,
+// the (aleatoric, epistemic) pair the object fold consumes and the number of pairs the object owns.
 #include "common.h"
 
 #define FLT_MIN_F 1.17549435e-38f
@@ -33,6 +36,9 @@ struct HuaArgs {
   float* unc; float* pair_out; int max_pairs; int* pair_count;
   // workspace
   int* pair_cand; int* pair_obj; int* pair_cls; float* pair_epi; float* pair_ale; int* lvl_pair_start; float* lam_mean; int* nobj;
+  // per-object outputs (null unless requested): obj_row [B, HMAXO] workspace = detection row of each compacted object,
+  // obj_out [B, max_num, 2] = (aleatoric, epistemic) per detection row, obj_pairs [B, max_num] = pairs the row's object owns
+  int* obj_row; float* obj_out; int* obj_pairs;
 };
 
 __device__ __forceinline__ int level_of(const HuaArgs& p, int cand) {
@@ -83,6 +89,7 @@ __global__ __launch_bounds__(1024) void hua_pairs_kernel(const HuaArgs p) {
         const int o = off + within;
         for (int u = 0; u < 4; ++u) obox[o][u] = d5[u];
         obox[o][4] = (d5[2] - d5[0]) * (d5[3] - d5[1]);
+        if (p.obj_row) p.obj_row[b * HMAXO + o] = t;
       }
       if (t == 0) { const int no = s_warp[0] + s_warp[1] + s_warp[2] + s_warp[3]; s_no = no; p.nobj[b] = no; }
     }
@@ -345,6 +352,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LPP == 1 &&
   }
 }
 
+// ---------------------------------------------------------------- closed form of the Monte-Carlo limit (estimator = 1)
+// psi(x) for x >= 1: lift to x >= 6 by psi(x) = psi(x + 1) - 1/x (at most 5 steps), then the asymptotic series
+// ln x - 1/(2x) - 1/(12 x^2) + 1/(120 x^4) - 1/(252 x^6) (truncation < 1/(240 x^8) < 3e-9 at x = 6).
+__device__ __forceinline__ float digamma_ge1(float x) {
+  float r = 0.f;
+#pragma unroll
+  for (int i = 0; i < 5; ++i)
+    if (x < 6.f) { r -= 1.f / x; x += 1.f; }
+  const float inv = 1.f / x, i2 = inv * inv;
+  return r + (logf(x) - 0.5f * inv - i2 * ((1.f / 12.f) - i2 * ((1.f / 120.f) - i2 * (1.f / 252.f))));
+}
+
+// H2': one wave per pair (four pairs per 256-thread workgroup, grid-stride over the pairs of image blockIdx.y); lane c owns Dirichlet columns
+// c and c + 64 (nd <= 96).  alpha = score * lam_hat with the float operations of hua_sample_kernel, S = sum alpha, m = alpha / S,
+//   total = -sum m ln m,  ale = psi(S + 1) - sum m psi(alpha + 1) (>= 0; clamped against rounding),  epi = total - ale.
+// A column with alpha == 0 (or m == 0) contributes 0 to every sum.  The three sums are xor butterflies (fixed order, every lane ends with the
+// same bits), no atomics and no LDS: a pair's result is a pure function of its inputs -- no seed, no sample count, no image id.
+__global__ __launch_bounds__(256) void hua_closed_kernel(const HuaArgs p) {
+  const int b = blockIdx.y;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nd = p.nd;
+  const int np = min(p.pair_count[b], p.max_pairs);
+  for (int pi = blockIdx.x * 4 + wave; pi < np; pi += gridDim.x * 4) {
+    const int cand = p.pair_cand[(long long)b * p.max_pairs + pi], obj = p.pair_obj[(long long)b * p.max_pairs + pi];
+    const int lvl = level_of(p, cand);
+    const float lamv = p.lam[(long long)b * p.n + cand];
+    const float lam_hat = p.lam_mean[b * HMAXL + lvl] / (lamv + 1e-7f) * 25.f;
+    const float* sc = p.scores + ((long long)b * p.n + cand) * (p.C + 1);
+    const bool on0 = lane < nd, on1 = lane + 64 < nd;
+    const float s0 = on0 ? sc[lane] : 0.f, s1 = on1 ? sc[lane + 64] : 0.f;
+    float best = -1.f;
+    int am = 0;
+    if (on0 && s0 > best) { best = s0; am = lane; }
+    if (on1 && s1 > best) { best = s1; am = lane + 64; }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {                  // first maximum (torch.argmax): larger value, ties -> lower class index
+      const float ob = __shfl_xor(best, o, 64);
+      const int oa = __shfl_xor(am, o, 64);
+      if (ob > best || (ob == best && oa < am)) { best = ob; am = oa; }
+    }
+    const float a0 = s0 * lam_hat, a1 = s1 * lam_hat;
+    const float S = wave_sum(a0 + a1);
+    const float m0 = a0 / S, m1 = a1 / S;
+    float ent = 0.f, mp = 0.f;
+    if (on0 && a0 > 0.f && m0 > 0.f) { ent -= m0 * logf(m0); mp += m0 * digamma_ge1(a0 + 1.f); }
+    if (on1 && a1 > 0.f && m1 > 0.f) { ent -= m1 * logf(m1); mp += m1 * digamma_ge1(a1 + 1.f); }
+    const float total = wave_sum(ent);
+    const float ale = fmaxf(digamma_ge1(S + 1.f) - wave_sum(mp), 0.f);
+    if (lane == 0) {
+      p.pair_cls[(long long)b * p.max_pairs + pi] = am;
+      p.pair_epi[(long long)b * p.max_pairs + pi] = total - ale;
+      p.pair_ale[(long long)b * p.max_pairs + pi] = ale;
+      if (p.pair_out) {
+        float* o = p.pair_out + ((long long)b * p.max_pairs + pi) * 4;
+        o[0] = (float)cand; o[1] = (float)obj; o[2] = ale; o[3] = total - ale;
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ float agg_fold(int mode, float acc, float v, int cnt) {
   if (cnt == 0) return v;
   return mode == 2 ? fmaxf(acc, v) : acc + v;
@@ -354,7 +421,13 @@ __device__ __forceinline__ float agg_final(int mode, float acc, int cnt) { retur
 // H3: one block per image.  Per level the pairs (object, argmax class, epistemic) are staged in LDS; a thread per (object, class) bin
 // takes the mean over its pairs IN PAIR ORDER (deterministic), a thread per object then folds the classes in class order, the levels in
 // level order, and thread 0 the objects in object order (Lambda_L2.py:526-536, 597-619).
+// OBJ (opt-in instance; the default one compiles to what it was): every level is reduced a second time with the pairs' aleatoric values
+// in place of the epistemic ones (same staging buffers, same registers: one extra reduce pass), which go through the same class and scale
+// folds on their own; after the folds the thread of detection row r writes obj_out[b, r] = (aleatoric, epistemic) -- the epistemic value
+// is the term the object fold consumes -- and obj_pairs[b, r] = pairs the object owns; rows that are no object (score <= thr,
+// r >= num_det) or own no pair get (NaN, NaN, 0).
 constexpr int HRED_STAGE = 2048;
+template <bool OBJ>
 __global__ __launch_bounds__(1024) void hua_reduce_kernel(const HuaArgs p) {
   extern __shared__ float s_bin[];                 // [no][nd] bin means of the current level, NaN = empty
   __shared__ int s_po[HRED_STAGE], s_pcl[HRED_STAGE];
@@ -362,10 +435,13 @@ __global__ __launch_bounds__(1024) void hua_reduce_kernel(const HuaArgs p) {
   __shared__ float s_lvl[HMAXO];                   // running fold over levels per object
   __shared__ int s_lvln[HMAXO];
   __shared__ unsigned long long s_cls[2];
+  __shared__ float s_lvla[OBJ ? HMAXO : 1];        // OBJ: running aleatoric fold, pair counts, detection row -> object
+  __shared__ int s_cnt[OBJ ? HMAXO : 1], s_rowobj[OBJ ? HMAXO : 1];
   const int b = blockIdx.x, t = threadIdx.x;
   const int no = p.nobj[b], nd = p.nd;
   if (t < 2) s_cls[t] = 0ull;
   for (int o = t; o < no; o += 1024) { s_lvl[o] = 0.f; s_lvln[o] = 0; }
+  if (OBJ && t < HMAXO) { s_lvla[t] = 0.f; s_cnt[t] = 0; s_rowobj[t] = -1; }
   const int* po = p.pair_obj + (long long)b * p.max_pairs;
   const int* pcl = p.pair_cls + (long long)b * p.max_pairs;
   const float* pe = p.pair_epi + (long long)b * p.max_pairs;
@@ -374,50 +450,81 @@ __global__ __launch_bounds__(1024) void hua_reduce_kernel(const HuaArgs p) {
     const int s = p.lvl_pair_start[b * (HMAXL + 1) + l], e = p.lvl_pair_start[b * (HMAXL + 1) + l + 1];
     if (e <= s) continue;                          // (block-uniform)
     const int nb = no * nd;
-    // running (sum, count) per bin in registers across the staged chunks of this level
-    float bs[(HMAXO * HMAXC + 1023) / 1024];
-    int bc[(HMAXO * HMAXC + 1023) / 1024];
+    for (int pass = 0; pass < (OBJ ? 2 : 1); ++pass) {      // pass 1 (OBJ): the aleatoric values
+      const float* pv = OBJ && pass ? p.pair_ale + (long long)b * p.max_pairs : pe;
+      // running (sum, count) per bin in registers across the staged chunks of this level
+      float bs[(HMAXO * HMAXC + 1023) / 1024];
+      int bc[(HMAXO * HMAXC + 1023) / 1024];
 #pragma unroll
-    for (int u = 0; u < (HMAXO * HMAXC + 1023) / 1024; ++u) { bs[u] = 0.f; bc[u] = 0; }
-    for (int k0 = s; k0 < e; k0 += HRED_STAGE) {
-      const int nk = min(HRED_STAGE, e - k0);
-      for (int k = t; k < nk; k += 1024) { s_po[k] = po[k0 + k]; s_pcl[k] = pcl[k0 + k]; s_pe[k] = pe[k0 + k]; }
-      __syncthreads();
+      for (int u = 0; u < (HMAXO * HMAXC + 1023) / 1024; ++u) { bs[u] = 0.f; bc[u] = 0; }
+      for (int k0 = s; k0 < e; k0 += HRED_STAGE) {
+        const int nk = min(HRED_STAGE, e - k0);
+        for (int k = t; k < nk; k += 1024) { s_po[k] = po[k0 + k]; s_pcl[k] = pcl[k0 + k]; s_pe[k] = pv[k0 + k]; }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < (HMAXO * HMAXC + 1023) / 1024; ++u) {
+          const int bin = u * 1024 + t;
+          if (bin < nb) {
+            const int o = bin / nd, c = bin - o * nd;
+            for (int k = 0; k < nk; ++k)
+              if (s_po[k] == o && s_pcl[k] == c) { bs[u] += s_pe[k]; ++bc[u]; }
+          }
+        }
+        __syncthreads();
+      }
 #pragma unroll
       for (int u = 0; u < (HMAXO * HMAXC + 1023) / 1024; ++u) {
         const int bin = u * 1024 + t;
         if (bin < nb) {
-          const int o = bin / nd, c = bin - o * nd;
-          for (int k = 0; k < nk; ++k)
-            if (s_po[k] == o && s_pcl[k] == c) { bs[u] += s_pe[k]; ++bc[u]; }
+          s_bin[bin] = bc[u] ? bs[u] / (float)bc[u] : __int_as_float(0x7fc00000);
+          if (OBJ && pass && bc[u]) atomicAdd(&s_cnt[bin / nd], bc[u]);
+        }
+      }
+      __syncthreads();
+      if (!OBJ || pass == 0) {
+        for (int o = t; o < no; o += 1024) {
+          float acc = 0.f;
+          int n = 0;
+          for (int c = 0; c < nd; ++c) {
+            const float v = s_bin[o * nd + c];
+            if (v == v) {
+              acc = agg_fold(p.agg_class, acc, v, n);
+              ++n;
+              atomicOr(&s_cls[c >> 6], 1ull << (c & 63));
+            }
+          }
+          if (n) {
+            const float lv = agg_final(p.agg_class, acc, n);
+            s_lvl[o] = agg_fold(p.agg_scale, s_lvl[o], lv, s_lvln[o]);
+            ++s_lvln[o];
+          }
+        }
+      } else {
+        for (int o = t; o < no; o += 1024) {       // (s_lvln[o] was incremented by pass 0 of this level: the same bins are non-empty)
+          float acc = 0.f;
+          int n = 0;
+          for (int c = 0; c < nd; ++c) {
+            const float v = s_bin[o * nd + c];
+            if (v == v) { acc = agg_fold(p.agg_class, acc, v, n); ++n; }
+          }
+          if (n) s_lvla[o] = agg_fold(p.agg_scale, s_lvla[o], agg_final(p.agg_class, acc, n), s_lvln[o] - 1);
         }
       }
       __syncthreads();
     }
-#pragma unroll
-    for (int u = 0; u < (HMAXO * HMAXC + 1023) / 1024; ++u) {
-      const int bin = u * 1024 + t;
-      if (bin < nb) s_bin[bin] = bc[u] ? bs[u] / (float)bc[u] : __int_as_float(0x7fc00000);
-    }
+  }
+  if (OBJ) {
+    for (int o = t; o < no; o += 1024) s_rowobj[p.obj_row[b * HMAXO + o]] = o;
     __syncthreads();
-    for (int o = t; o < no; o += 1024) {
-      float acc = 0.f;
-      int n = 0;
-      for (int c = 0; c < nd; ++c) {
-        const float v = s_bin[o * nd + c];
-        if (v == v) {
-          acc = agg_fold(p.agg_class, acc, v, n);
-          ++n;
-          atomicOr(&s_cls[c >> 6], 1ull << (c & 63));
-        }
-      }
-      if (n) {
-        const float lv = agg_final(p.agg_class, acc, n);
-        s_lvl[o] = agg_fold(p.agg_scale, s_lvl[o], lv, s_lvln[o]);
-        ++s_lvln[o];
-      }
+    if (t < p.max_num) {
+      const int o = s_rowobj[t];
+      const bool ok = o >= 0 && s_lvln[o] > 0;
+      const float nan = __int_as_float(0x7fc00000);
+      float* oo = p.obj_out + ((long long)b * p.max_num + t) * 2;
+      oo[0] = ok ? agg_final(p.agg_scale, s_lvla[o], s_lvln[o]) : nan;
+      oo[1] = ok ? agg_final(p.agg_scale, s_lvl[o], s_lvln[o]) : nan;
+      p.obj_pairs[(long long)b * p.max_num + t] = ok ? s_cnt[o] : 0;
     }
-    __syncthreads();
   }
   if (t == 0) {
     float acc = 0.f;
@@ -431,15 +538,19 @@ __global__ __launch_bounds__(1024) void hua_reduce_kernel(const HuaArgs p) {
 }
 
 extern "C" size_t aod_hua_ws_bytes(int B, int max_pairs) {
-  return (size_t)B * ((size_t)max_pairs * 20 + (HMAXL + 1) * 4 + HMAXL * 4 + 4) + 64;
+  return (size_t)B * ((size_t)max_pairs * 20 + (HMAXL + 1) * 4 + HMAXL * 4 + 4 + HMAXO * 4) + 64;      // (+ the object -> detection row map)
 }
 
-extern "C" int aod_hua_score(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
-                             const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg, const int64_t* image_ids,
-                             int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr, float fg_thr, int num_samples,
-                             uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode, int dirichlet_cols, float* unc, float* pair_out, int max_pairs,
-                             int32_t* pair_count, void* ws, aod_stream_t stream) {
+extern "C" int aod_hua_score_ex(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
+                                const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg, const int64_t* image_ids,
+                                int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr, float fg_thr, int num_samples,
+                                uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode, int dirichlet_cols, float* unc, float* pair_out,
+                                int max_pairs, int32_t* pair_count, int estimator, float* obj_out, int32_t* obj_pairs, void* ws,
+                                aod_stream_t stream) {
   if (B == 0) return 0;
+  AOD_CHECK_ARG(estimator == 0 || estimator == 1, "hua: estimator must be 0 (Monte-Carlo) or 1 (closed form)");
+  AOD_CHECK_ARG((obj_out == nullptr) == (obj_pairs == nullptr), "hua: obj_out and obj_pairs come together");
+  AOD_CHECK_ARG(!(obj_out && scale_mode), "hua: per-object outputs are not offered in scale_mode");
   AOD_CHECK_ARG(scores && lam && cand_anchor && level_start_host && level_any_fg && image_ids && unc && pair_count && ws, "hua: null pointer");
   AOD_CHECK_ARG(scale_mode || (boxes && dets && num_det), "hua: object mode needs boxes / dets / num_det");
   AOD_CHECK_ARG(L >= 1 && L <= HMAXL && C >= 1 && C <= HMAXC && max_num <= HMAXO && num_samples >= 1 && num_samples <= 8192 && max_pairs >= 1,
@@ -462,18 +573,31 @@ extern "C" int aod_hua_score(const float* boxes, const float* scores, const floa
   p.pair_ale = (float*)w; w += (size_t)B * max_pairs * 4;
   p.lvl_pair_start = (int*)w; w += (size_t)B * (HMAXL + 1) * 4;
   p.lam_mean = (float*)w; w += (size_t)B * HMAXL * 4;
-  p.nobj = (int*)w;
+  p.nobj = (int*)w; w += (size_t)B * 4;
+  p.obj_row = obj_out ? (int*)w : nullptr; p.obj_out = obj_out; p.obj_pairs = obj_pairs;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(hua_pairs_kernel, dim3(B), dim3(1024), 0, st, p);
   const int gx = max_pairs < 512 ? max_pairs : 512;
 #define AOD_HUA_SAMPLE(CPL_, LPP_, EX_) hipLaunchKernelGGL((hua_sample_kernel<CPL_, LPP_, EX_>), dim3(gx, B), dim3(256), 0, st, p)
-  if (p.nd == 20) AOD_HUA_SAMPLE(20, 1, true);
+  if (estimator == 1) hipLaunchKernelGGL(hua_closed_kernel, dim3((gx + 3) / 4, B), dim3(256), 0, st, p);      // four pairs per workgroup
+  else if (p.nd == 20) AOD_HUA_SAMPLE(20, 1, true);
   else if (p.nd == 21) AOD_HUA_SAMPLE(21, 1, true);
   else if (p.nd == 80) AOD_HUA_SAMPLE(20, 4, true);
   else if (p.nd <= 24) AOD_HUA_SAMPLE(24, 1, false);
   else AOD_HUA_SAMPLE(24, 4, false);
 #undef AOD_HUA_SAMPLE
-  hipLaunchKernelGGL(hua_reduce_kernel, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
+  if (obj_out) hipLaunchKernelGGL(hua_reduce_kernel<true>, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
+  else hipLaunchKernelGGL(hua_reduce_kernel<false>, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int aod_hua_score(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
+                             const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg, const int64_t* image_ids,
+                             int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr, float fg_thr, int num_samples,
+                             uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode, int dirichlet_cols, float* unc, float* pair_out, int max_pairs,
+                             int32_t* pair_count, void* ws, aod_stream_t stream) {
+  return aod_hua_score_ex(boxes, scores, lam, cand_anchor, dets, num_det, level_start_host, level_any_fg, image_ids, B, n, L, C, max_num,
+                          obj_score_thr, obj_iou_thr, fg_thr, num_samples, seed, agg3_host, clsW, scale_mode, dirichlet_cols, unc, pair_out,
+                          max_pairs, pair_count, 0, nullptr, nullptr, ws, stream);
 }

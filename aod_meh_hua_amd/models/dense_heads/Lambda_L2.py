@@ -200,6 +200,8 @@ class Lambda_L2Net(L_AnchorHead):
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=bool(kwargs.get('showNMS')), L_scores=L_scores, **kwargs)
         elif not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_NMS':
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=True, L_scores=L_scores, **kwargs)
+        elif kwargs['isEval'] and kwargs.get('detUnc'):      # per-detection uncertainties: HUA after NMS needs lambda
+            results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, L_scores=L_scores, **kwargs)
         else:
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, **kwargs)
         if not kwargs['isEval']:

@@ -116,6 +116,8 @@ class MyLSSDHead(L_AnchorHead):
         L_scores = self.forward_L(feats, head_out=None)
         if not kwargs['isEval'] and kwargs['uPool'] in ('Entropy_ALL', 'Entropy_NMS'):
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=kwargs['uPool'] == 'Entropy_NMS', L_scores=L_scores, **kwargs)
+        elif kwargs['isEval'] and kwargs.get('detUnc'):      # per-detection uncertainties: HUA after NMS needs lambda
+            results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, L_scores=L_scores, **kwargs)
         else:
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, **kwargs)
         if not kwargs['isEval']:

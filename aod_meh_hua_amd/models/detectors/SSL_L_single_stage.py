@@ -2,7 +2,7 @@
 (mmdet/models/detectors/SSL_L_single_stage.py:10-98, SSL_L_retinanet.py, SSD_L_single_stage.py)."""
 import warnings
 
-from ...core.bbox import bbox2result
+from ...core.bbox import bbox2result, unc2result
 from ..builder import DETECTORS, build_backbone, build_head, build_neck
 from .SSL_Lambda import SSLBase_L_Detector
 
@@ -47,6 +47,9 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
         feat = self.extract_feat(img)
         if kwargs['isEval']:
             _results_list = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, **kwargs)
+            if kwargs.get('detUnc'):      # (bbox_results, unc_results): unc_results[i][c] is (k, 2) (aleatoric, epistemic), row-aligned with bbox_results[i][c]
+                nc = self.bbox_head.num_classes
+                return ([bbox2result(d, l, nc) for d, l, _ in _results_list], [unc2result(u, l, nc) for _, l, u in _results_list])
             results_list = _results_list[0] if kwargs.get('isUnc') else _results_list
             return [bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes) for det_bboxes, det_labels in results_list]
         results_list, *uncertainties = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, **kwargs)

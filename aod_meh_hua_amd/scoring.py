@@ -175,8 +175,19 @@ def multiclass_nms_batch(boxes, scores, score_thr, iou_thr, max_num):
     return dets, labels, keep, num
 
 
+HUA_ESTIMATORS = {'mc': 0, 'closed': 1}
+
+
 def hua_score(cand, dets, num_det, image_ids, max_num, agg=(0, 2, 0), clsW=False, num_samples=500, seed=20, obj_score_thr=0.3,
-              obj_iou_thr=0.5, fg_thr=0.3, want_pairs=False, max_pairs=None, scale_mode=False, dirichlet_cols=0):
+              obj_iou_thr=0.5, fg_thr=0.3, want_pairs=False, max_pairs=None, scale_mode=False, dirichlet_cols=0, estimator='mc',
+              want_objects=False):
+    """estimator: 'mc' (num_samples Dirichlet draws, seeded) or 'closed' (the closed form of the Monte-Carlo limit: no seed, no sample count).
+    want_objects appends (obj_out [B, max_num, 2] = (aleatoric, epistemic) per detection row, obj_pairs [B, max_num] int32) to the return;
+    rows that are no object (score <= obj_score_thr, row >= num_det) or own no pair hold (NaN, NaN, 0)."""
+    if estimator not in HUA_ESTIMATORS:
+        raise ValueError(f"hua_score: unknown estimator {estimator!r} (expected 'mc' or 'closed')")
+    if want_objects and scale_mode:
+        raise ValueError('hua_score: per-object outputs are not offered in scale_mode')
     B, n, C1 = cand.scores.shape
     dev = cand.boxes.device
     L = len(cand.level_start) - 1
@@ -185,6 +196,17 @@ def hua_score(cand, dets, num_det, image_ids, max_num, agg=(0, 2, 0), clsW=False
     pair_count = torch.empty(B, dtype=torch.int32, device=dev)
     pair_out = torch.zeros(B, max_pairs, 4, device=dev) if want_pairs else None
     ws = torch.empty(int(_C.lib.aod_hua_ws_bytes(B, max_pairs)), dtype=torch.uint8, device=dev)
+    if estimator != 'mc' or want_objects:
+        obj_out = torch.empty(B, int(max_num), 2, device=dev) if want_objects else None
+        obj_pairs = torch.empty(B, int(max_num), dtype=torch.int32, device=dev) if want_objects else None
+        call('aod_hua_score_ex', ptr(cand.boxes), ptr(cand.scores), ptr(cand.lam), ptr(cand.cand_anchor), ptr(dets), ptr(num_det),
+             (C.c_int32 * (L + 1))(*cand.level_start), ptr(cand.any_fg), ptr(image_ids), B, n, L, C1 - 1, int(max_num), float(obj_score_thr),
+             float(obj_iou_thr), float(fg_thr), int(num_samples), int(seed), (C.c_int32 * 3)(*agg), int(bool(clsW)), int(bool(scale_mode)),
+             int(dirichlet_cols), ptr(unc), ptr(pair_out), int(max_pairs), ptr(pair_count), HUA_ESTIMATORS[estimator], ptr(obj_out),
+             ptr(obj_pairs), ptr(ws), stream())
+        out = (unc, pair_count, pair_out) if want_pairs else (unc,)
+        out = out + (obj_out, obj_pairs) if want_objects else out
+        return out if len(out) > 1 else unc
     call('aod_hua_score', ptr(cand.boxes), ptr(cand.scores), ptr(cand.lam), ptr(cand.cand_anchor), ptr(dets), ptr(num_det),
          (C.c_int32 * (L + 1))(*cand.level_start), ptr(cand.any_fg), ptr(image_ids), B, n, L, C1 - 1, int(max_num), float(obj_score_thr),
          float(obj_iou_thr), float(fg_thr), int(num_samples), int(seed), (C.c_int32 * 3)(*agg), int(bool(clsW)), int(bool(scale_mode)),
@@ -197,7 +219,10 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                 **kwargs):
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.
 
-    isEval=True (detection for mAP)  -> list of (det_bboxes [k,5], det_labels [k]) per image.
+    isEval=True (detection for mAP)  -> list of (det_bboxes [k,5], det_labels [k]) per image;
+                 with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
+                                        and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
+    hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / detUnc paths.
     isUnc with uPool == 'Entropy_NMS' -> (det_results, unc [B] device tensor)."""
     assert head.last_activation in ('relu', 'softmax')
     has_bg = head.last_activation == 'softmax'         # SSD: 21 logits incl. background (My_L_ssd_head.py:331-345)
@@ -218,7 +243,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
             image_ids = torch.arange(B, device=cand.boxes.device, dtype=torch.int64) + int(kwargs.get('batchIdx', 0)) * B
         cls_code, scale_code, _ = extract_agg_codes(kwargs['uPool2'] if 'object' in kwargs['uPool2'] else 'objectSum_' + kwargs['uPool2'])
         unc = hua_score(cand, None, None, image_ids.to(torch.int64).contiguous(), 1, (cls_code, scale_code, 0), False,
-                        seed=kwargs.get('hua_seed', 20), scale_mode=True)
+                        seed=kwargs.get('hua_seed', 20), scale_mode=True, estimator=kwargs.get('hua_estimator') or 'mc')
         det_results = [(cand.boxes[b], cand.scores[b]) for b in range(B)]
         if kwargs.get('_return_internals'):
             return det_results, unc, dict(cand=cand)
@@ -235,16 +260,25 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     max_num = cfg.max_per_img
     dets, labels, keep, num = multiclass_nms_batch(cand.boxes, cand.scores, cfg.score_thr, cfg.nms.get('iou_threshold', 0.5), max_num)
     B = dets.shape[0]
-    if not isUnc or kwargs.get('isEval'):
+    if (not isUnc or kwargs.get('isEval')) and not (kwargs.get('isEval') and kwargs.get('detUnc')):
         nh = num.cpu().tolist()           # evaluation path: variable-length results are part of the interface
         return [(dets[b, :nh[b]], labels[b, :nh[b]]) for b in range(B)]
     image_ids = kwargs.get('image_ids')
     if image_ids is None:
         bs = kwargs.get('batchIdx', 0)
         image_ids = torch.arange(B, device=dets.device, dtype=torch.int64) + int(bs) * B
+    estimator = kwargs.get('hua_estimator') or 'mc'
+    if kwargs.get('isEval'):              # detUnc: the detections of the evaluation path with their own (aleatoric, epistemic)
+        if kwargs.get('L_scores') is None:
+            raise ValueError('detUnc needs the lambda head outputs (L_scores)')
+        agg = extract_agg_codes(kwargs.get('uPool2') or 'objectSum_scaleMax_classSum')
+        _, obj_out, _ = hua_score(cand, dets, num, image_ids.to(torch.int64).contiguous(), max_num, agg, False, seed=kwargs.get('hua_seed', 20),
+                                  dirichlet_cols=C_ if has_bg else 0, estimator=estimator, want_objects=True)
+        nh = num.cpu().tolist()
+        return [(dets[b, :nh[b]], labels[b, :nh[b]], obj_out[b, :nh[b]]) for b in range(B)]
     agg = extract_agg_codes(kwargs['uPool2'])
     unc = hua_score(cand, dets, num, image_ids.to(torch.int64).contiguous(), max_num, agg, kwargs.get('clsW', False),
-                    seed=kwargs.get('hua_seed', 20), dirichlet_cols=C_ if has_bg else 0)
+                    seed=kwargs.get('hua_seed', 20), dirichlet_cols=C_ if has_bg else 0, estimator=estimator)
     det_results = [(dets[b], labels[b]) for b in range(B)]   # zero-padded to max_per_img rows (num_det rows are valid)
     if kwargs.get('_return_internals'):
         return det_results, unc, dict(cand=cand, dets=dets, labels=labels, keep=keep, num=num)

@@ -448,6 +448,22 @@ int aod_hua_score(const float* boxes, const float* scores, const float* lam, con
                   const int64_t* image_ids, int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr,
                   float fg_thr, int num_samples, uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode,
                   int dirichlet_cols, float* unc, float* pair_out, int max_pairs, int32_t* pair_count, void* ws, aod_stream_t stream);
+/* aod_hua_score with two opt-in extensions (same reference call site: Lambda_L2.py:343-349,489-537,597-619); aod_hua_score is
+ * aod_hua_score_ex(..., estimator = 0, obj_out = NULL, obj_pairs = NULL).
+ * estimator: 0 = Monte-Carlo (num_samples Dirichlet draws, Philox stream keyed by seed / image_ids / cand_anchor);
+ *            1 = closed form of the Monte-Carlo limit, per pair in fp32: S = sum a_c, m_c = a_c / S, total = -sum m_c ln m_c,
+ *                aleatoric = psi(S+1) - sum m_c psi(a_c+1), epistemic = total - aleatoric (a_c == 0 contributes 0);
+ *                num_samples, seed and image_ids are not read.
+ * obj_out (optional, [B, max_num, 2] f32) / obj_pairs ([B, max_num] int32; NULL iff obj_out is NULL): per DETECTION ROW of dets[b],
+ * (aleatoric, epistemic) after the class and scale folds -- the epistemic value is the term the object fold consumes -- and the number
+ * of pairs the row's object owns; (NaN, NaN, 0) for rows with score <= obj_score_thr, rows >= num_det and objects without a pair.
+ * Not offered with scale_mode = 1. */
+int aod_hua_score_ex(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor,
+                     const float* dets, const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg,
+                     const int64_t* image_ids, int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr,
+                     float fg_thr, int num_samples, uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode,
+                     int dirichlet_cols, float* unc, float* pair_out, int max_pairs, int32_t* pair_count, int estimator,
+                     float* obj_out, int32_t* obj_pairs, void* ws, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ SSD300-VGG16 variant (BASELINE config 0)
  * generic NHWC bf16 max-pool fwd/bwd (mmcv VGG pools, ceil_mode, + the 3x3 s1 p1 pool5 of backbones/ssd_vgg.py:66-68) */

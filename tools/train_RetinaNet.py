@@ -65,6 +65,8 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--synthetic-size', type=int, default=default_size)
     p.add_argument('--cycles', type=int, default=None, help='override the number of AL cycles')
     p.add_argument('--samples-per-gpu', type=int, default=None)
+    p.add_argument('--hua-estimator', choices=['mc', 'closed'], default=None,
+                   help='HUA estimator of the pool scoring pass: Monte-Carlo (default) or the closed form of its limit (config key model.test_cfg.hua_estimator)')
     p.add_argument('--device-transforms', action='store_true',
                    help='run Resize / RandomFlip / Normalize / Pad of the VOC pipelines as one HIP kernel per batch (config key data.device_transforms)')
     args = p.parse_args()
@@ -151,6 +153,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
         cfg.data.samples_per_gpu = args.samples_per_gpu
     if args.device_transforms:
         cfg.data.device_transforms = True
+    if args.hua_estimator:
+        cfg.model.test_cfg.hua_estimator = args.hua_estimator
     cfg.dump(osp.join(cfg.work_dir, osp.basename(args.config)))
     timestamp = time.strftime('%Y%m%d_%H%M%S', time.localtime())
     logger = get_root_logger(log_file=osp.join(cfg.work_dir, f'{timestamp}.log'), log_level=cfg.log_level)
