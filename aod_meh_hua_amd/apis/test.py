@@ -198,3 +198,88 @@ def single_gpu_test(model, data_loader, show=False, out_dir=None, show_score_thr
         else:
             results.extend(out)
     return (results, unc_results) if kwargs.get('detUnc') else results
+
+
+def eval_annotations(dataset):
+    """[dataset.get_ann_info(i)] read once per dataset object (VOC: one XML parse per image) and kept on it."""
+    anns = getattr(dataset, '_eval_annotations', None)
+    if anns is None or len(anns) != len(dataset):
+        anns = [dataset.get_ann_info(i) for i in range(len(dataset))]
+        try:
+            dataset._eval_annotations = anns
+        except AttributeError:
+            pass
+    return anns
+
+
+@torch.no_grad()
+def single_gpu_map(model, data_loader, iou_thr=0.5, dataset=None, show=False, out_dir=None, show_score_thr=0.3, logger='silent',
+                   scale_ranges=None, tpfp_fn=None, annotations=None, _timing=None, **kwargs):
+    """Evaluation on the device: detect (isEval=True, padded outputs) -> aod_eval_match -> core.evaluation_device.DeviceMapAccumulator, one
+    D2H copy per evaluation.  Returns (mean_ap, eval_results) for a float `iou_thr`, a list of such pairs for a list of thresholds -- each
+    bit-identical to eval_map(single_gpu_test(model, data_loader), annotations, iou_thr=thr, dataset=dataset).
+
+    The loop is single_gpu_uncertainty's: the test set is sharded over the ranks (shard_batches), batches come from the prefetch workers
+    through pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the detection pass replays one captured graph
+    (single stream: isEval has no two-phase form); the match kernel runs eagerly behind the replay on the same stream, so it has read the
+    graph's static outputs before the next replay overwrites them.  `annotations`: the dataset's, when the caller already holds them.
+    `_timing` (a dict; tools/eval_throughput.py): the loop is followed by a device sync and its wall time lands in _timing['pass_s']."""
+    import os
+    import time
+    t_start = time.perf_counter()
+    from ..core.evaluation import print_map_summary
+    from ..core.evaluation_device import DeviceMapAccumulator
+    if kwargs.get('detUnc'):
+        raise ValueError('single_gpu_map: detUnc is not offered on the device metric; use single_gpu_test(detUnc=True)')
+    for k in ('device_metric', 'metric', 'proposal_nums', 'interval'):          # EvalHook forwards the whole `evaluation` dict
+        kwargs.pop(k, None)
+    kwargs.setdefault('isUnc', False)
+    single = isinstance(iou_thr, (int, float))
+    iou_thrs = [float(iou_thr)] if single else [float(t) for t in iou_thr]
+    model.eval()
+    ds = data_loader.dataset
+    N = len(ds)
+    module = getattr(model, 'module', model)
+    dev = next(model.parameters()).device
+    acc = DeviceMapAccumulator(module.bbox_head.num_classes, iou_thrs, module.bbox_head.test_cfg.max_per_img, N, dev,
+                               scale_ranges=scale_ranges, tpfp_fn=tpfp_fn)
+    anns = annotations if annotations is not None else eval_annotations(ds)
+    assert len(anns) == N
+    rank, world = get_dist_info()
+    bs = data_loader.batch_size or 1
+    my_batches = shard_batches(N, bs, rank, world, False)
+    gscore = None
+    if os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda' and all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values()):
+        from ..graphs import GraphedScore
+        cache = _GSCORE.setdefault(model, {})
+        key = ('eval_padded',) + tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items()))
+        gscore = cache.get(key)
+        if gscore is None:
+            gscore = cache[key] = GraphedScore(model, rescale=True, isEval=True, _padded=True, **kwargs)
+    my_idx = [i for b in my_batches for i in b]
+    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
+    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
+    prog_bar = ProgressBar(len(my_idx))
+    pos = 0
+    for idxs, data in _shard_batches(ds, my_batches, data_loader.collate_fn, workers):
+        image_ids = all_ids[pos:pos + len(idxs)]
+        pos += len(idxs)
+        data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
+        if dev.type == 'cuda':
+            data['img'] = _pin(data['img'])
+        out = None
+        if gscore is not None and isinstance(data['img'], (list, tuple)) and len(data['img']) == 1:
+            out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids)
+        if out is None:
+            out = model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **kwargs)
+        dets, labels, num = out
+        acc.update(idxs, dets, labels, num, [anns[i] for i in idxs])
+        prog_bar.update(len(idxs))
+    if _timing is not None:
+        torch.cuda.synchronize()
+        _timing['pass_s'] = time.perf_counter() - t_start
+    acc.gather()
+    res = acc.finalize(dataset)
+    for mean_ap, eval_results in res:
+        print_map_summary(mean_ap, eval_results, dataset, None, logger=logger)
+    return res[0] if single else res

@@ -5,7 +5,8 @@
 The fork rounds UP to two decimals in three places -- cumulative recall and precision curves (mean_ap.py:364-365) and every sampled
 precision of the VOC07 11-point AP (:49-50) -- which shifts mAP by up to ~1 point against stock mmdet; those quirks are part of the
 number the paper reports and are kept.  Host-side numpy (the metric is a sequential greedy match over a few thousand boxes, not a GPU
-workload); one process instead of the reference's multiprocessing.Pool (same arithmetic, deterministic order)."""
+workload); one process instead of the reference's multiprocessing.Pool (same arithmetic, deterministic order).  An opt-in device form
+of the match (`aod_eval_match` + `evaluation_device.DeviceMapAccumulator`, driven by `apis.test.single_gpu_map`) gives the same bits."""
 import numpy as np
 
 
@@ -144,26 +145,38 @@ def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=N
                 for k, (min_area, max_area) in enumerate(area_ranges):
                     num_gts[k] += np.sum((gt_areas >= min_area) & (gt_areas < max_area))
         cls_dets = np.vstack(cls_dets)
-        num_dets = cls_dets.shape[0]
-        sort_inds = np.argsort(-cls_dets[:, -1])
-        tp = np.cumsum(np.hstack(tp)[:, sort_inds], axis=1)
-        fp = np.cumsum(np.hstack(fp)[:, sort_inds], axis=1)
-        eps = np.finfo(np.float32).eps
-        recalls = np.ceil(tp / np.maximum(num_gts[:, np.newaxis], eps) * 100) / 100          # the fork's ceil-to-2-decimals (:364-365)
-        precisions = np.ceil(tp / np.maximum((tp + fp), eps) * 100) / 100
-        if scale_ranges is None:
-            recalls, precisions, num_gts = recalls[0, :], precisions[0, :], num_gts.item()
-        ap = average_precision(recalls, precisions, 'area' if dataset != 'voc07' else '11points')
-        eval_results.append(dict(num_gts=num_gts, num_dets=num_dets, recall=recalls, precision=precisions, ap=ap))
+        eval_results.append(class_result(cls_dets[:, -1], np.hstack(tp), np.hstack(fp), num_gts, scale_ranges is None, dataset))
     if scale_ranges is not None:
         all_ap = np.vstack([r['ap'] for r in eval_results])
         all_num_gts = np.vstack([r['num_gts'] for r in eval_results])
         mean_ap = [all_ap[all_num_gts[:, i] > 0, i].mean() if np.any(all_num_gts[:, i] > 0) else 0.0 for i in range(num_scales)]
     else:
-        aps = [r['ap'] for r in eval_results if r['num_gts'] > 0]
-        mean_ap = np.array(aps).mean().item() if aps else 0.0
+        mean_ap = mean_of_aps(eval_results)
     print_map_summary(mean_ap, eval_results, dataset, area_ranges, logger=logger)
     return mean_ap, eval_results
+
+
+def class_result(scores, tp, fp, num_gts, single_scale, dataset):
+    """One class's entry of eval_map's result (mean_ap.py:352-373) from its detections' scores [n], tp / fp [scales, n] float32 (all in the
+    concatenation order: image-major, within an image by detection row) and num_gts [scales] int.  Shared with the device metric
+    (evaluation_device.DeviceMapAccumulator.finalize), which hands over the same arrays and so gets the same bits."""
+    num_dets = scores.shape[0]
+    sort_inds = np.argsort(-scores)
+    tp = np.cumsum(tp[:, sort_inds], axis=1)
+    fp = np.cumsum(fp[:, sort_inds], axis=1)
+    eps = np.finfo(np.float32).eps
+    recalls = np.ceil(tp / np.maximum(num_gts[:, np.newaxis], eps) * 100) / 100          # the fork's ceil-to-2-decimals (:364-365)
+    precisions = np.ceil(tp / np.maximum((tp + fp), eps) * 100) / 100
+    if single_scale:
+        recalls, precisions, num_gts = recalls[0, :], precisions[0, :], num_gts.item()
+    ap = average_precision(recalls, precisions, 'area' if dataset != 'voc07' else '11points')
+    return dict(num_gts=num_gts, num_dets=num_dets, recall=recalls, precision=precisions, ap=ap)
+
+
+def mean_of_aps(eval_results):
+    """mean_ap.py:396-401 without scale ranges: the mean over the classes that have a gt."""
+    aps = [r['ap'] for r in eval_results if r['num_gts'] > 0]
+    return np.array(aps).mean().item() if aps else 0.0
 
 
 def print_map_summary(mean_ap, results, dataset=None, scale_ranges=None, logger=None):

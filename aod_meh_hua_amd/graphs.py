@@ -516,6 +516,10 @@ class GraphedScore:
             self._fill_img(sl, img)
             self._fill_meta(sl, img_metas, image_ids)
             sl['g'].replay()
+            if self.kw.get('isEval') and self.kw.get('_padded'):
+                # evaluation form (apis/test.py single_gpu_map): the slot's STATIC (dets, labels, num) -- the caller consumes them on this
+                # stream before its next call replays over them
+                return sl['out']
             unc = sl['out'][1]
             return sl['out'][0], (unc.clone() if torch.is_tensor(unc) else unc)
         if self.s_conv is None:

@@ -662,10 +662,40 @@ class EvalHook(Hook):
     def after_train_epoch(self, runner):
         if not self.by_epoch or not self._should_evaluate(runner):
             return None
+        if self.eval_kwargs.get('device_metric'):
+            return self._device_metric(runner)
         from .apis.test import single_gpu_test
         results = single_gpu_test(runner.model, self.dataloader, **self.eval_kwargs)
         runner.log_buffer.output['eval_iter_num'] = len(self.dataloader)
         eval_res = self.dataloader.dataset.evaluate(results, logger=runner.logger, **self.eval_kwargs)
+        for name, val in eval_res.items():
+            runner.log_buffer.output[name] = val
+        runner.log_buffer.ready = True
+        return eval_res
+
+    def _device_metric(self, runner):
+        """evaluation = dict(..., device_metric=True): apis.test.single_gpu_map (detect -> match -> accumulate on the device, sharded over
+        the ranks) instead of single_gpu_test + dataset.evaluate; the dict is evaluate_voc's, value for value."""
+        from .apis.test import eval_annotations, single_gpu_map
+        kw = dict(self.eval_kwargs)
+        metric = kw.pop('metric', 'mAP')
+        metric = metric[0] if not isinstance(metric, str) and len(metric) == 1 else metric
+        if metric != 'mAP':
+            raise KeyError(f'metric {metric} is not supported')
+        dataset = self.dataloader.dataset
+        iou_thr = kw.pop('iou_thr', 0.5)
+        iou_thrs = [iou_thr] if isinstance(iou_thr, float) else list(iou_thr)
+        if getattr(self, '_annotations', None) is None:          # read once per hook, not once per evaluation
+            self._annotations = eval_annotations(dataset)
+        ds_name = 'voc07' if getattr(dataset, 'year', 2007) == 2007 else dataset.CLASSES
+        res = single_gpu_map(runner.model, self.dataloader, iou_thr=iou_thrs, dataset=ds_name, logger=runner.logger,
+                             annotations=self._annotations, **kw)
+        runner.log_buffer.output['eval_iter_num'] = len(self.dataloader)
+        eval_res, mean_aps = {}, []
+        for thr, (mean_ap, _) in zip(iou_thrs, res):
+            mean_aps.append(mean_ap)
+            eval_res[f'AP{int(thr * 100):02d}'] = round(mean_ap, 3)
+        eval_res['mAP'] = sum(mean_aps) / len(mean_aps)
         for name, val in eval_res.items():
             runner.log_buffer.output[name] = val
         runner.log_buffer.ready = True

@@ -47,6 +47,8 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
         feat = self.extract_feat(img)
         if kwargs['isEval']:
             _results_list = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, **kwargs)
+            if kwargs.get('_padded'):     # device metric: (dets [B,max,5], labels [B,max], num [B]) stay on the device, no bbox2result
+                return _results_list
             if kwargs.get('detUnc'):      # (bbox_results, unc_results): unc_results[i][c] is (k, 2) (aleatoric, epistemic), row-aligned with bbox_results[i][c]
                 nc = self.bbox_head.num_classes
                 return ([bbox2result(d, l, nc) for d, l, _ in _results_list], [unc2result(u, l, nc) for _, l, u in _results_list])

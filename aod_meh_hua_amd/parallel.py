@@ -8,6 +8,7 @@ defines what is built here:
                      (sized for xGMI's per-link-bound rings); called once after each of the two backward passes.
   * shard_range   -- contiguous block of the unlabeled pool for this rank, [r*ceil(N/W), (r+1)*ceil(N/W)).
   * gather_scores -- all-gather of the per-rank fp32 score blocks (+ trim of the padding).
+  * gather_rows   -- all-gather of fixed-size buffers whose rows the ranks own disjointly (the device mAP accumulator).
   * broadcast_model -- rank-0 weights to everybody after each cycle's re-init (tools/train_RetinaNet.py:156-157).
 """
 import math
@@ -254,6 +255,26 @@ def gather_scores(local_scores, n_total):
     out = [torch.empty_like(buf) for _ in range(world)]
     dist.all_gather(out, buf)
     return torch.cat(out)[:n_total]
+
+
+def gather_rows(buf, owned):
+    """Rows of a fixed-size buffer that the ranks own disjointly -> the full buffer on every rank.  buf: [N, ...] of any dtype (the same
+    shape on every rank), owned: [N] bool, this rank's rows.  One all-gather of the buffer and one of the mask; a row is taken from the
+    rank that owns it, a row nobody owns keeps this rank's value.  Returns (buf, owned); no process group: the inputs themselves.  No
+    host sync."""
+    rank, world = get_dist_info()
+    if world == 1:
+        return buf, owned
+    bufs = [torch.empty_like(buf) for _ in range(world)]
+    masks = [torch.empty_like(owned, dtype=torch.uint8) for _ in range(world)]
+    dist.all_gather(bufs, buf.contiguous())
+    dist.all_gather(masks, owned.to(torch.uint8))
+    out, any_owned = buf.clone(), owned.clone()
+    for b, m in zip(bufs, masks):
+        m = m.bool()
+        out = torch.where(m.view((-1,) + (1,) * (buf.dim() - 1)), b, out)
+        any_owned |= m
+    return out, any_owned
 
 
 def broadcast_model(model, src=0):

@@ -220,6 +220,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.
 
     isEval=True (detection for mAP)  -> list of (det_bboxes [k,5], det_labels [k]) per image;
+                 with _padded=True   -> (dets [B,max,5], labels [B,max] int64, num [B] int32) on the device, no host sync;
                  with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
     hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / detUnc paths.
@@ -260,6 +261,11 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     max_num = cfg.max_per_img
     dets, labels, keep, num = multiclass_nms_batch(cand.boxes, cand.scores, cfg.score_thr, cfg.nms.get('iou_threshold', 0.5), max_num)
     B = dets.shape[0]
+    if kwargs.get('isEval') and kwargs.get('_padded'):
+        # device metric (apis/test.py single_gpu_map): the padded triple stays on the device -- no num.cpu(), graph-capturable
+        if kwargs.get('detUnc'):
+            raise ValueError('detUnc is not offered with the padded evaluation outputs')
+        return dets, labels, num
     if (not isUnc or kwargs.get('isEval')) and not (kwargs.get('isEval') and kwargs.get('detUnc')):
         nh = num.cpu().tolist()           # evaluation path: variable-length results are part of the interface
         return [(dets[b, :nh[b]], labels[b, :nh[b]]) for b in range(B)]

@@ -429,6 +429,16 @@ size_t aod_nms_ws_bytes(int B, int n, int C);
 int aod_multiclass_nms(const float* boxes, const float* scores, int B, int n, int C, float score_thr, float iou_thr,
                        int max_num, float* dets, int64_t* det_labels, int64_t* keep, int32_t* num_det,
                        void* ws, aod_stream_t stream);
+/* tpfp_default (mmdet/core/evaluation/mean_ap.py:154-239, area_ranges=None) for a whole batch, all classes and T (1..8) IoU thresholds in
+ * one launch.  dets [B,M,5] / labels [B,M] int64 / num [B] int32: the outputs of aod_multiclass_nms (rows >= num[b] are never read;
+ * M <= 2048).  gt_boxes [B,G,4], gt_labels [B,G] int32, gt_ignore [B,G] uint8, gt_num [B] int32: per image the real gts in annotation
+ * order, THEN the ignored gts in annotation order (the host stacks gt_bboxes above gt_bboxes_ignore per class and argmax takes the first
+ * maximum; the packed list filtered by class has that order).  iou_thr_host: HOST array of T thresholds, compared as fp32.
+ * flags [T,B,M] uint8: 0 neither (best gt ignored, or row >= num[b]), 1 tp, 2 fp.  Claimants of one gt rank by descending score, ties by
+ * lower row (stable); IoU is bbox_overlaps (bbox_overlaps.py:4-48) bit for bit in fp32.  No workspace, no host sync. */
+int aod_eval_match(const float* dets, const int64_t* labels, const int32_t* num, const float* gt_boxes, const int32_t* gt_labels,
+                   const uint8_t* gt_ignore, const int32_t* gt_num, int B, int M, int G, const float* iou_thr_host, int T,
+                   uint8_t* flags, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ HUA (K13-K15)
  * replaces GetObjectIdx + ComputeObjUnc + AggregateObjScaleUnc (Lambda_L2.py:343-349,489-537,597-619;

@@ -69,6 +69,9 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                    help='HUA estimator of the pool scoring pass: Monte-Carlo (default) or the closed form of its limit (config key model.test_cfg.hua_estimator)')
     p.add_argument('--device-transforms', action='store_true',
                    help='run Resize / RandomFlip / Normalize / Pad of the VOC pipelines as one HIP kernel per batch (config key data.device_transforms)')
+    p.add_argument('--device-metric', action='store_true',
+                   help='EvalHook computes mAP on the device: padded detections -> aod_eval_match -> one D2H copy, the test set sharded over '
+                        'the ranks (config key evaluation.device_metric); same numbers as the host metric')
     args = p.parse_args()
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
@@ -155,6 +158,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
         cfg.data.device_transforms = True
     if args.hua_estimator:
         cfg.model.test_cfg.hua_estimator = args.hua_estimator
+    if args.device_metric:
+        cfg.evaluation.device_metric = True
     cfg.dump(osp.join(cfg.work_dir, osp.basename(args.config)))
     timestamp = time.strftime('%Y%m%d_%H%M%S', time.localtime())
     logger = get_root_logger(log_file=osp.join(cfg.work_dir, f'{timestamp}.log'), log_level=cfg.log_level)
