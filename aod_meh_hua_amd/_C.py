@@ -143,6 +143,8 @@ _SIGS = {
     'aod_sgd_multi': (C.c_int, [P, P, P, P, I32, F32, P, F32, F32, I32, F32, P]),
     'aod_sgd_multi_clipped': (C.c_int, [P, P, P, P, I32, F32, P, F32, F32, I32, F32, P, P]),
     'aod_grad_norm_multi': (C.c_int, [P, P, I32, F32, F32, I32, P, I64, P, P]),
+    'aod_ensemble_mi_partials_len': (SZ, [I32, P, I32]),
+    'aod_ensemble_mi': (C.c_int, [P, I32, I32, P, I32, I32, P, P, I64, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

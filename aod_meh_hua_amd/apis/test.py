@@ -182,6 +182,94 @@ def single_gpu_uncertainty(model, data_loader, **kwargs):
 
 
 @torch.no_grad()
+def single_gpu_ensemble(models, data_loader, n_cls=None, **kwargs):
+    """Ensemble_MI (mmdet/apis/CalEnsembleUnc.py:137-162) for 2 <= K <= 32 built models, on single_gpu_uncertainty's loop: the pool is sharded
+    over the ranks, batches come from the prefetch workers through pinned memory, the scores stay on the device and are gathered once.
+    Returns a [N] fp32 tensor identical on every rank.
+
+    Per batch: K forwards (isEval=True, justOut=True: classification maps only), then ONE aod_ensemble_mi launch pair on the same stream
+    (scoring.ensemble_mi).  While the batch shape repeats (and AOD_HIP_GRAPH != 0) each member replays its own captured forward and hands
+    back its graph's static maps; the MI kernel runs eagerly behind the K replays on the caller's stream, so it has read them before the
+    next batch's replays overwrite them.  n_cls: classes per anchor row, default the head's cls_out_channels."""
+    import os
+    from ..scoring import ensemble_mi
+    models = list(models)
+    if not 2 <= len(models) <= 32:
+        raise ValueError(f'single_gpu_ensemble: 2..32 ensemble members are supported, got {len(models)}')
+    for m in models:
+        m.eval()
+    dataset = data_loader.dataset
+    N = len(dataset)
+    rank, world = get_dist_info()
+    bs = data_loader.batch_size or 1
+    my_batches = shard_batches(N, bs, rank, world, False)
+    dev = next(models[0].parameters()).device
+    if n_cls is None:
+        n_cls = getattr(models[0], 'module', models[0]).bbox_head.cls_out_channels
+    gscores = None
+    if (os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda'
+            and all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values())):
+        from ..graphs import GraphedScore
+        gscores = []
+        for k, m in enumerate(models):
+            # one graph per MEMBER: a model listed twice gets two (each owns the static maps it hands back)
+            key = ('just_out', sum(1 for o in models[:k] if o is m)) + tuple(sorted((n, type(v).__name__, v) for n, v in kwargs.items()))
+            cache = _GSCORE.setdefault(m, {})
+            g = cache.get(key)
+            if g is None:
+                g = cache[key] = GraphedScore(m, rescale=True, isEval=True, justOut=True, **kwargs)
+            gscores.append(g)
+    device_side = hasattr(dataset, 'device_batch')
+    my_idx = [i for b in my_batches for i in b]
+    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
+    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
+    batches = ((idxs, None) for idxs in my_batches) if device_side else _shard_batches(dataset, my_batches, data_loader.collate_fn, workers)
+    prog_bar = ProgressBar(len(my_idx))
+    chunks = []
+    pos = 0
+    for idxs, data in batches:
+        image_ids = all_ids[pos:pos + len(idxs)]
+        pos += len(idxs)
+        if device_side:
+            data = dataset.device_batch(idxs, dev, image_ids=image_ids)
+        else:
+            data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
+            if dev.type == 'cuda':
+                data['img'] = _pin(data['img'])
+        single = isinstance(data['img'], (list, tuple)) and len(data['img']) == 1
+        if single and dev.type == 'cuda':
+            # the batch goes to the device ONCE (one H2D copy / one transform launch); every member reads that tensor
+            img = data['img'][0]
+            img = img.to_device(dev) if isinstance(img, DeviceImageBatch) else img.to(dev, non_blocking=True)
+            data['img'] = [img]
+        members = []
+        for k, m in enumerate(models):
+            out = None
+            if gscores is not None and single:
+                out = gscores[k].maybe(data['img'][0], data['img_metas'][0], image_ids)
+            if out is None:
+                out = m(return_loss=False, rescale=True, isEval=True, justOut=True, **data, **kwargs)
+            members.append(out)
+        chunks.append(ensemble_mi(members, n_cls))
+        prog_bar.update(len(idxs))
+    local = torch.cat(chunks) if chunks else torch.zeros(0, device=dev)
+    return gather_scores(local, N)
+
+
+def Ensemble_uncertainty(cfg, *models, data_loader=None, **kwargs):
+    """mmdet/apis/CalEnsembleUnc.py:86-88 with the reference's name and argument order (cfg, m1, m2, m3, data_loader), for 2..32 members:
+    the loader is the last positional argument or the `data_loader` keyword.  Returns the CPU score tensor update_X_L takes."""
+    models = list(models)
+    if data_loader is None:
+        if not models:
+            raise TypeError('Ensemble_uncertainty(cfg, m1, m2, ..., data_loader): no data loader given')
+        data_loader = models.pop()
+    if not hasattr(data_loader, 'dataset'):
+        raise TypeError('Ensemble_uncertainty(cfg, m1, m2, ..., data_loader): the last argument must be the pool loader')
+    return single_gpu_ensemble(models, data_loader, **kwargs).cpu()
+
+
+@torch.no_grad()
 def single_gpu_test(model, data_loader, show=False, out_dir=None, show_score_thr=0.3, **kwargs):
     """test.py:138-195 (detection results for evaluation; isEval=True).  detUnc=True: returns (results, unc_results) where
     unc_results[i][c] is a (k, 2) float32 array (aleatoric, epistemic), row-aligned with results[i][c]; the box arrays keep five columns

@@ -45,6 +45,11 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
     def simple_test(self, img, img_metas, rescale=False, **kwargs):
         """SSL_L_single_stage.py:68-98."""
         feat = self.extract_feat(img)
+        if kwargs['isEval'] and kwargs.get('justOut'):
+            # MyRetinaSingleStage.py:46-49 (honoured with isEval only): the per-level classification maps [B, A*C, h, w] fp32 of an ensemble
+            # member (apis/test.py single_gpu_ensemble) -- no decode, no NMS, no HUA
+            head = self.bbox_head
+            return list(head.test_heads(feat)[0][0] if hasattr(head, 'test_heads') else head.forward(feat)[0])
         if kwargs['isEval']:
             _results_list = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, **kwargs)
             if kwargs.get('_padded'):     # device metric: (dets [B,max,5], labels [B,max], num [B]) stay on the device, no bbox2result

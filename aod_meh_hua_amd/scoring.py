@@ -215,6 +215,66 @@ def hua_score(cand, dets, num_det, image_ids, max_num, agg=(0, 2, 0), clsW=False
     return (unc, pair_count, pair_out) if want_pairs else unc
 
 
+def _dense(t):
+    return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def ensemble_mi(members, n_cls, out=None):
+    """Mutual information between K ensemble members' sigmoid classification maps, one score per image: the public form of the reference's
+    ComputeMI (mmdet/apis/CalEnsembleUnc.py:164-180, K = 3 models) and ComputeMCDropoutMI (mmdet/apis/CalMCDropoutUnc.py:183-199, K = n
+    stochastic outputs of one model) on the aod_ensemble_mi kernel.
+
+    members: K lists (2 <= K <= 32) of L per-level logit maps (1 <= L <= 8), fp32 device tensors [B, ...] of the same shapes in every
+    member, dense in memory with the batch outermost (contiguous or channels_last; nothing is copied).  n_cls: classes per anchor row.
+    Returns out [B] fp32 on the device (no host sync); a term with p = 0 contributes 0 where the reference turns the image into NaN."""
+    members = [list(m) for m in members]
+    K = len(members)
+    if not 2 <= K <= 32:
+        raise ValueError(f'ensemble_mi: 2..32 members are supported, got {K}')
+    L = len(members[0])
+    if not 1 <= L <= 8:
+        raise ValueError(f'ensemble_mi: 1..8 levels are supported, got {L}')
+    n_cls = int(n_cls)
+    if n_cls < 1:
+        raise ValueError(f'ensemble_mi: n_cls must be positive, got {n_cls}')
+    first = members[0]
+    for k, m in enumerate(members):
+        if len(m) != L:
+            raise ValueError(f'ensemble_mi: member {k} has {len(m)} levels, member 0 has {L}')
+        for l, t in enumerate(m):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError(f'ensemble_mi: member {k} level {l} is not an fp32 tensor')
+            if t.dim() < 1 or tuple(t.shape) != tuple(first[l].shape):
+                raise ValueError(f'ensemble_mi: member {k} level {l} has shape {tuple(t.shape)}, member 0 has {tuple(first[l].shape)}')
+    B = int(first[0].shape[0])
+    n = []
+    for l, t in enumerate(first):
+        if int(t.shape[0]) != B or B < 1 or t.numel() == 0:
+            raise ValueError(f'ensemble_mi: level {l} has shape {tuple(t.shape)}; every level needs the same positive batch size')
+        if (t.numel() // B) % n_cls:
+            raise ValueError(f'ensemble_mi: level {l} holds {t.numel() // B} elements per image, not a multiple of n_cls = {n_cls}')
+        n.append(t.numel() // B)
+    dev = first[0].device
+    for k, m in enumerate(members):
+        for l, t in enumerate(m):
+            if not t.is_cuda:
+                raise _C.AodHipError('ensemble_mi needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+            if t.device != dev:
+                raise ValueError(f'ensemble_mi: member {k} level {l} lives on {t.device}, member 0 on {dev}')
+            if not _dense(t):
+                raise ValueError(f'ensemble_mi: member {k} level {l} is not dense (contiguous or channels_last); no copy is made here')
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B,) and out.is_contiguous()):
+        raise ValueError(f'ensemble_mi: out must be a contiguous fp32 device tensor of shape ({B},)')
+    sizes = (C.c_int64 * L)(*n)
+    cap = int(_C.lib.aod_ensemble_mi_partials_len(L, sizes, B))
+    ws = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    call('aod_ensemble_mi', (C.c_void_p * (K * L))(*[t.data_ptr() for m in members for t in m]), K, L, sizes, B, n_cls, ptr(out), ptr(ws), cap,
+         stream())
+    return out
+
+
 def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes, scale_factors, cfg, rescale=False, with_nms=True,
                 **kwargs):
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.

@@ -542,6 +542,19 @@ int aod_sgd_multi_clipped(void* const* params, void* const* grads, void* const* 
 int aod_grad_norm_multi(void* const* grads, const int64_t* sizes, int ntensors, float grad_scale, float max_norm, int flags,
                         float* partials_ws, int64_t ws_capacity, float* state, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ ensemble / MC-dropout mutual information (csrc/ensemble_mi.hip)
+ * Replaces mmdet/apis/CalEnsembleUnc.py:164-180 (ComputeMI) and mmdet/apis/CalMCDropoutUnc.py:183-199 (ComputeMCDropoutMI): the Python loop
+ * over levels x images of a dozen torch ops each, ending in .tolist().  maps[k * L + l] = device pointer of member k's classification map of
+ * level l: dense fp32, B x n_per_level[l] elements, batch outermost (NCHW-contiguous and channels_last both qualify: the score is a sum over
+ * all elements; the class structure enters through rows_l = n_per_level[l] / n_cls only).  2 <= K <= 32 members, 1 <= L <= 8 levels.
+ *   out[b] = mean_l ( sum_e [ -avg ln avg + (1/K) sum_k p_k ln p_k ] / rows_l ),   p_k = sigmoid(x_k), avg = mean_k p_k,   0 ln 0 = 0
+ * (the reference yields NaN for an image once one sigmoid underflows).  partials_ws: aod_ensemble_mi_partials_len(L, n_per_level, B) floats
+ * (ws_capacity = what the caller holds; -2 when too small).  Two launches, no atomics; the sums have a fixed order that does not depend on B
+ * or on an image's position in the batch: same bits on every launch, and for an image scored alone or inside a batch. */
+size_t aod_ensemble_mi_partials_len(int L, const int64_t* n_per_level, int B);
+int aod_ensemble_mi(const void* const* maps, int K, int L, const int64_t* n_per_level, int B, int n_cls, float* out, float* partials_ws,
+                    int64_t ws_capacity, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */
