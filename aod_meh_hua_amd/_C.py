@@ -145,6 +145,9 @@ _SIGS = {
     'aod_grad_norm_multi': (C.c_int, [P, P, I32, F32, F32, I32, P, I64, P, P]),
     'aod_ensemble_mi_partials_len': (SZ, [I32, P, I32]),
     'aod_ensemble_mi': (C.c_int, [P, I32, I32, P, I32, I32, P, P, I64, P]),
+    'aod_dropout2d_masks': (C.c_int, [P, P, I32, P, I32, I32, F32, U64, C.c_uint32, P]),
+    'aod_dropout2d_apply': (C.c_int, [P, P, I64, I32, I32, I32, I32, P]),
+    'aod_dropout2d_apply_multi': (C.c_int, [P, P, I64, I32, I32, P, P, P, I32, I32, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -269,6 +269,143 @@ def Ensemble_uncertainty(cfg, *models, data_loader=None, **kwargs):
     return single_gpu_ensemble(models, data_loader, **kwargs).cpu()
 
 
+_MCD_STACKS = _weakref.WeakKeyDictionary()      # model -> {map shapes: the preallocated [n][L] stack of a batch shape}
+_MCD_STATE = _weakref.WeakKeyDictionary()       # model -> {(batch size, options): the static factor table and the captured forward that reads it}
+
+
+def _mcd_adjacent(out):
+    """the maps are fp32 and lie back to back in one storage (the row ranges of a level-batched prediction conv's output buffer)"""
+    base = out[0].untyped_storage().data_ptr()
+    return all(t.dtype == torch.float32 and t.untyped_storage().data_ptr() == base for t in out) and all(
+        out[l + 1].data_ptr() == out[l].data_ptr() + 4 * out[l].numel() for l in range(len(out) - 1))
+
+
+def _mcd_stack(model, out, n):
+    """n slots for the L classification maps of one batch shape.  The maps of a level-batched prediction conv are adjacent row ranges of one
+    buffer: a slot is then ONE flat allocation with the same per-level views, filled by one device copy per sample; else L copies."""
+    key = (n,) + tuple((tuple(t.shape), tuple(t.stride())) for t in out)
+    cache = _MCD_STACKS.setdefault(model, {})
+    st = cache.get(key)
+    if st is None:
+        sizes = [t.numel() for t in out]
+        flat = _mcd_adjacent(out)
+        slots = []
+        for _ in range(n):
+            if flat:
+                buf, o, views = torch.empty(sum(sizes), dtype=torch.float32, device=out[0].device), 0, []
+                for t, sz in zip(out, sizes):
+                    views.append(buf.as_strided(tuple(t.shape), tuple(t.stride()), o))
+                    o += sz
+                slots.append((buf, views))
+            else:
+                slots.append((None, [torch.empty_like(t) for t in out]))
+        st = cache[key] = (flat, sum(sizes), slots)
+    return st
+
+
+@torch.no_grad()
+def single_gpu_mcdropout(model, data_loader, n=25, rate=0.1, seed=0, n_cls=None, **kwargs):
+    """MCDropout_MI (mmdet/apis/CalMCDropoutUnc.py:137-163) on single_gpu_ensemble's loop: the pool is sharded over the ranks, batches come from
+    the prefetch workers through pinned memory (one H2D copy per batch), the scores stay on the device and are gathered once.  Returns a [N]
+    fp32 tensor identical on every rank.
+
+    Per batch and per sample k = 0..n-1: one aod_dropout2d_masks launch writes the Dropout2d factors of every site into the static table
+    (keyed by seed, k and the GLOBAL image ids), one forward with a Dropout2d(rate) behind every ReLU that feeds the classification maps
+    (functional.mc_dropout: eval mode, isEval=True, justOut=True), one device copy of the maps into slot k of a preallocated stack; then ONE
+    scoring.ensemble_mi call over the n slots.  While the batch shape repeats (and AOD_HIP_GRAPH != 0) the n forwards are n replays of ONE
+    captured forward, which reads the table the mask kernel has just rewritten.  An image's score is a function of (weights, image, seed,
+    image id, n, rate) only: the same bits alone, in any batch, on any rank count, eager or replayed."""
+    import os
+    from .. import functional as AF
+    from .. import hipops as ho
+    from ..scoring import ensemble_mi
+    rate, n = float(rate), int(n)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f'single_gpu_mcdropout: rate must be in [0, 1), got {rate}')
+    if not 2 <= n <= 32:
+        raise ValueError(f'single_gpu_mcdropout: 2..32 stochastic forwards are supported (scoring.ensemble_mi takes up to 32 members), got n = {n}')
+    sites = AF.dropout_sites(model)               # NotImplementedError for the SSD detectors (VGG sites are not built)
+    L = len({k.rsplit('@', 1)[1] for k in sites if '@' in k})
+    if n * L > 256:
+        raise ValueError(f'single_gpu_mcdropout: n * levels = {n} * {L} exceeds the 256 map pointers of one ensemble_mi launch')
+    model.eval()
+    dataset = data_loader.dataset
+    N = len(dataset)
+    rank, world = get_dist_info()
+    bs = data_loader.batch_size or 1
+    my_batches = shard_batches(N, bs, rank, world, False)
+    dev = next(model.parameters()).device
+    if n_cls is None:
+        n_cls = getattr(model, 'module', model).bbox_head.cls_out_channels
+    # the static factor table [bs, T] and the captured forward that reads it: one pair per (model, batch size, options)
+    primitives = all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values())
+    key = (bs,) + (tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items())) if primitives else ())
+    cache = _MCD_STATE.setdefault(model, {})
+    ent = cache.get(key) if primitives else None
+    if ent is None:
+        ent = dict(table=torch.ones(bs, sites.T, dtype=torch.float32, device=dev), g=None)
+        if primitives:
+            cache[key] = ent
+    table = ent['table']
+    offsets = sites.offsets(dev)
+    gscore = None
+    if os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda' and primitives:
+        if ent['g'] is None:
+            from ..graphs import GraphedScore
+            ent['g'] = GraphedScore(model, rescale=True, isEval=True, justOut=True, mc_dropout=AF.MCDropoutState(table, sites), **kwargs)
+        gscore = ent['g']
+    device_side = hasattr(dataset, 'device_batch')
+    my_idx = [i for b in my_batches for i in b]
+    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
+    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
+    batches = ((idxs, None) for idxs in my_batches) if device_side else _shard_batches(dataset, my_batches, data_loader.collate_fn, workers)
+    prog_bar = ProgressBar(len(my_idx))
+    chunks = []
+    pos = 0
+    for idxs, data in batches:
+        image_ids = all_ids[pos:pos + len(idxs)]
+        pos += len(idxs)
+        if device_side:
+            data = dataset.device_batch(idxs, dev, image_ids=image_ids)
+        else:
+            data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
+            if dev.type == 'cuda':
+                data['img'] = _pin(data['img'])
+        single = isinstance(data['img'], (list, tuple)) and len(data['img']) == 1
+        if single and dev.type == 'cuda':
+            # the batch goes to the device ONCE; the n forwards read that tensor
+            img = data['img'][0]
+            img = img.to_device(dev) if isinstance(img, DeviceImageBatch) else img.to(dev, non_blocking=True)
+            data['img'] = [img]
+        stack = None
+        for k in range(n):
+            ho.dropout2d_masks(table, image_ids, offsets, rate, seed, k)
+            out = None
+            if gscore is not None and single:
+                out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids)
+            if out is None:
+                out = model(return_loss=False, rescale=True, isEval=True, justOut=True, mc_dropout=AF.MCDropoutState(table, sites), **data, **kwargs)
+            if stack is None:
+                stack = _mcd_stack(model, out, n)
+            flat, total, slots = stack
+            buf, views = slots[k]
+            if flat and _mcd_adjacent(out):       # (a replay overwrites the graph's static maps: every sample is copied out)
+                buf.copy_(out[0].as_strided((total,), (1,)))
+            else:
+                for d, t in zip(views, out):
+                    d.copy_(t)
+        chunks.append(ensemble_mi([views for _, views in stack[2]], n_cls))
+        prog_bar.update(len(idxs))
+    local = torch.cat(chunks) if chunks else torch.zeros(0, device=dev)
+    return gather_scores(local, N)
+
+
+def MCDropout_uncertainty(cfg, model, data_loader, **kwargs):
+    """mmdet/apis/CalMCDropoutUnc.py:86-88 with the reference's name and argument order.  kwargs: n (default 25 forwards), rate (0.1), seed,
+    n_cls.  Returns the CPU score tensor update_X_L takes."""
+    return single_gpu_mcdropout(model, data_loader, **kwargs).cpu()
+
+
 @torch.no_grad()
 def single_gpu_test(model, data_loader, show=False, out_dir=None, show_score_thr=0.3, **kwargs):
     """test.py:138-195 (detection results for evaluation; isEval=True).  detUnc=True: returns (results, unc_results) where

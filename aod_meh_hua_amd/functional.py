@@ -909,6 +909,116 @@ def conv_towers_nograd(xss, convs, relu=True):
     return [[as_nchw(o[s.row0:s.row0 + s.rows], s.B, s.H, s.W) for s in dsegs] for o in outs]
 
 
+# --------------------------------------------------------------------------- MC-dropout forwards (csrc/dropout.hip)
+class DropoutSites(dict):
+    """site name -> (site index, table offset, channels), in the order of the oracle's keyed ReLU sites (oracle/model.py `_relu`):
+    'backbone.bn1'; '<block>.bn1' / '.bn2' / '.out'; 'bbox_head.cls_convs.<i>@<level>' (level-major).  T = table width (sum of the channel
+    counts); prefix[id(module)] = the name a Bottleneck / the backbone / the head builds its site names from."""
+    T = 0
+    prefix = None
+
+    def offsets(self, device):
+        """the sites' first table columns as the device int32 array aod_dropout2d_masks reads (one per device, cached)"""
+        cache = self.__dict__.setdefault('_dev', {})
+        t = cache.get(device)
+        if t is None:
+            t = cache[device] = torch.tensor([v[1] for v in self.values()], dtype=torch.int32).to(device)
+        return t
+
+
+def dropout_sites(model):
+    """The Dropout2d sites of an MC-dropout forward of a ResNet + FPN + Lambda_L2Net detector: one per ReLU application that feeds the
+    classification maps -- the backbone's and the cls tower's (a tower conv is applied once per pyramid level: one site per (conv, level));
+    FPN has no ReLU, and the reg / MEH towers are not run by that forward."""
+    m = getattr(model, 'module', model)
+    bb, head = m.backbone, m.bbox_head
+    if not (hasattr(bb, 'res_layers') and hasattr(head, 'cls_convs')):
+        raise NotImplementedError(f'dropout_sites: MC-dropout sites are defined for the ResNet + Lambda_L2Net detectors, not for '
+                                  f'{type(bb).__name__} / {type(head).__name__} (SSD / VGG sites are not built)')
+    sites = DropoutSites()
+    sites.prefix = {id(bb): 'backbone', id(head): 'bbox_head'}
+
+    def add(name, ch):
+        sites[name] = (len(sites), sites.T, int(ch))
+        sites.T += int(ch)
+    add('backbone.bn1', bb.conv1.out_channels)
+    for li, lname in enumerate(bb.res_layers):
+        for bi, blk in enumerate(getattr(bb, lname)):
+            p = f'backbone.layer{li + 1}.{bi}'
+            sites.prefix[id(blk)] = p
+            add(p + '.bn1', blk.conv1.out_channels)
+            add(p + '.bn2', blk.conv2.out_channels)
+            add(p + '.out', blk.conv3.out_channels)
+    levels = int(m.neck.num_outs) if getattr(m, 'with_neck', False) else len(bb.out_indices)
+    for l in range(levels):
+        for i, cm in enumerate(head.cls_convs):
+            add(f'bbox_head.cls_convs.{i}@{l}', cm.conv.out_channels)
+    return sites
+
+
+_MCD = None        # (table [Bmax, T] fp32, DropoutSites) while a dropout forward runs; None: nothing below launches or branches
+
+
+class mc_dropout:
+    """Context of ONE stochastic forward (isEval=True, justOut=True, no autograd): the whole-block inference fusions stand down
+    (bottleneck64_applies / bottleneck128_applies), so every ReLU output on the path exists in memory, and each is multiplied in place by its
+    site's slice of `table` (dropout_apply).  The table is read at run time: a captured forward replays with whatever it holds then."""
+
+    def __init__(self, table, sites):
+        self.state = (table, sites)
+
+    def __enter__(self):
+        global _MCD
+        assert not torch.is_grad_enabled(), 'MC-dropout forwards run under torch.no_grad() (dropout in training is not built)'
+        self.prev, _MCD = _MCD, self.state
+        return self
+
+    def __exit__(self, *exc):
+        global _MCD
+        _MCD = self.prev
+
+
+class MCDropoutState:
+    """(factor table, DropoutSites) as ONE opaque object: what travels to simple_test as the `mc_dropout` keyword.  MMDataParallel's scatter
+    rebuilds tuples and dicts on the way (a DropoutSites would arrive as a plain dict); an object of another type passes as it is."""
+    __slots__ = ('table', 'sites')
+
+    def __init__(self, table, sites):
+        self.table, self.sites = table, sites
+
+
+def mc_dropout_active():
+    return _MCD is not None
+
+
+def dropout_apply(ys, names, owner=None):
+    """Dropout2d behind a ReLU: y *= factors of site `name`, in place, for a tensor or a level list `ys` ([B, width(C), H, W] conv
+    outputs) and their site names (`owner`: the module whose DropoutSites.prefix the names are relative to).  A level list whose members
+    are row ranges of one buffer (a level-batched conv's outputs) takes ONE launch (aod_dropout2d_apply_multi), else one per level."""
+    table, sites = _MCD
+    single = torch.is_tensor(ys)
+    yl, nl = ([ys], [names]) if single else (list(ys), list(names))
+    if owner is not None:
+        nl = [sites.prefix[id(owner)] + n for n in nl]
+    ents = [sites[n] for n in nl]
+    rows = []
+    for y, (_, off, ch) in zip(yl, ents):
+        r = as_rows(y)
+        assert r.data_ptr() == y.data_ptr() and r.shape[1] == ho.width(ch), (tuple(y.shape), ch)      # a view of y: the product is y's
+        rows.append(r)
+    B = yl[0].shape[0]
+    ch = ents[0][2]
+    rb = rows[0].shape[1] * rows[0].element_size()
+    base = min(rows, key=lambda r: r.data_ptr())
+    offs = [r.data_ptr() - base.data_ptr() for r in rows]
+    if 1 < len(rows) <= 8 and all(o % rb == 0 for o in offs) and all(e[2] == ch for e in ents) and all(y.shape[0] == B for y in yl):
+        ho.dropout2d_apply_multi(base, table, B, [(o // rb, y.shape[2] * y.shape[3], e[1]) for o, y, e in zip(offs, yl, ents)], ch)
+    else:
+        for y, r, e in zip(yl, rows, ents):
+            ho.dropout2d_apply(r, table, e[1], y.shape[0], y.shape[2] * y.shape[3], e[2])
+    return ys
+
+
 # --------------------------------------------------------------------------- stem helpers
 def image_to_nhwc(img, cpad=8):
     """fp32 NCHW image batch -> bf16 NHWC rows viewed as [B, cpad, H, W] (no grad: images are leaves)."""
@@ -924,6 +1034,8 @@ def image_to_nhwc(img, cpad=8):
 def bottleneck64_applies(blk, x):
     """a 64-channel, stride-1 bottleneck (resnet.py:262-301) whose forward keeps nothing for a backward pass: inference, or a frozen
     block (layer1 under frozen_stages = 1) on an input that needs no gradient"""
+    if _MCD is not None:          # MC-dropout forward: the three-launch form, a Dropout2d behind each ReLU
+        return False
     if _os.environ.get('AOD_FUSE_BOTTLENECK', '1') == '0' or blk.planes != 64 or x.dtype != torch.bfloat16:
         return False
     if ho.X3 and _os.environ.get('AOD_FUSE_BOTTLENECK_X3', '1') == '0':
@@ -1024,6 +1136,8 @@ def _frag_form(blk):
 def bottleneck128_applies(blk, x):
     """an identity bottleneck of the 128-plane stage (resnet.py:262-301: 512 -> 128 -> 128 -> 512, stride 1, no downsample branch) whose
     forward keeps nothing for a backward pass (inference / frozen): one launch (aod_bottleneck128_fwd)"""
+    if _MCD is not None:
+        return False
     if _os.environ.get('AOD_FUSE_BOTTLENECK128', '1') == '0' or not _wide_stage(blk) or blk.downsample is not None:
         return False
     c1, c2, c3 = blk.conv1, blk.conv2, blk.conv3

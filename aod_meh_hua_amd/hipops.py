@@ -833,6 +833,43 @@ def x3_add(a, b):
     return out
 
 
+def dropout2d_masks(table, image_ids, site_offsets, rate, seed, sample):
+    """The Dropout2d factors of one stochastic forward (aod_dropout2d_masks): rows 0 .. len(image_ids) - 1 of the fp32 table [Bmax, T],
+    one row per image id (device int64), columns by `site_offsets` (device int32, one entry per site).  Plain arguments: rate, seed, sample."""
+    B, T = int(image_ids.numel()), int(table.shape[1])
+    if not (table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous() and table.shape[0] >= B):
+        raise ValueError(f'dropout2d_masks: the table must be a contiguous fp32 [>= {B}, T] tensor, got {tuple(table.shape)} {table.dtype}')
+    if not (image_ids.dtype == torch.int64 and image_ids.is_contiguous() and site_offsets.dtype == torch.int32 and site_offsets.is_contiguous()):
+        raise ValueError('dropout2d_masks: image_ids must be contiguous int64 and site_offsets contiguous int32')
+    call('aod_dropout2d_masks', ptr(table), ptr(image_ids), B, ptr(site_offsets), int(site_offsets.numel()), T, float(rate),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample), stream())
+    return table
+
+
+def dropout2d_apply(x_rows, table, col0, B, HW, Cc):
+    """x_rows [B * HW, width(Cc)] (bf16, contiguous) *= table[b, col0 + c], in place (aod_dropout2d_apply)"""
+    if not (x_rows.dtype == torch.bfloat16 and x_rows.is_contiguous() and tuple(x_rows.shape) == (B * HW, width(Cc))):
+        raise ValueError(f'dropout2d_apply: rows {tuple(x_rows.shape)} {x_rows.dtype} are not the contiguous bf16 [{B * HW}, {width(Cc)}] rows of {Cc} channels')
+    if not (table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1 and table.shape[0] >= B and 0 <= col0 and col0 + Cc <= table.shape[1]):
+        raise ValueError(f'dropout2d_apply: table {tuple(table.shape)} does not hold columns {col0}..{col0 + Cc} of {B} images')
+    call('aod_dropout2d_apply', ptr(x_rows), C.c_void_p(table.data_ptr() + 4 * col0), table.stride(0), B, HW, Cc, 1 if X3 else 0, stream())
+    return x_rows
+
+
+def dropout2d_apply_multi(base_rows, table, B, segs, Cc):
+    """the same for up to 8 row segments (first row, rows per image, first table column) of one row buffer in ONE launch
+    (aod_dropout2d_apply_multi): the tower outputs of one depth, one segment per pyramid level"""
+    n = len(segs)
+    if not (base_rows.dtype == torch.bfloat16 and base_rows.is_contiguous() and base_rows.shape[1] == width(Cc)):
+        raise ValueError(f'dropout2d_apply_multi: rows {tuple(base_rows.shape)} {base_rows.dtype} are not contiguous bf16 rows of {Cc} channels')
+    if not (table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1 and table.shape[0] >= B
+            and all(0 <= off and off + Cc <= table.shape[1] for _, _, off in segs)):
+        raise ValueError(f'dropout2d_apply_multi: table {tuple(table.shape)} does not hold the segments\' columns for {B} images')
+    call('aod_dropout2d_apply_multi', ptr(base_rows), ptr(table), table.stride(0), B, n, (C.c_int64 * n)(*[s[0] for s in segs]),
+         (C.c_int32 * n)(*[s[1] for s in segs]), (C.c_int32 * n)(*[s[2] for s in segs]), Cc, 1 if X3 else 0, stream())
+    return base_rows
+
+
 IMAGE_XFORM_ITEM_BYTES = 80          # sizeof(aod_image_xform_item_t), include/aod_hip.h
 
 

@@ -52,6 +52,11 @@ class Bottleneck(BaseModule):
         # (a block WITH a downsample branch reads a stage input: conv1 and the downsample conv share it -- and with the neck's lateral conv --
         # through the gradient junction ResNet.forward put on it)
         ds = self.downsample is not None
+        if AF.mc_dropout_active():                 # MC-dropout forward (no autograd): one Dropout2d behind each of the three ReLU uses
+            out = AF.dropout_apply(self.conv1(x, bn=self.norm1, relu=True), '.bn1', self)
+            out = AF.dropout_apply(self.conv2(out, bn=self.norm2, relu=True), '.bn2', self)
+            identity = x if not ds else self.downsample[0](x, bn=self.downsample[1])
+            return AF.dropout_apply(self.conv3(out, bn=self.norm3, res=identity, relu=True), '.out', self)
         pre, ch = (None, None, None), None
         if AF.bottleneck128_train_applies(self, x):      # training forward of an identity block of the 128- / 256-plane stage: ONE launch
             pre = AF.bottleneck128_train_fwd(x, self)    # computes t1, t2 and y; the three calls below only record the autograd nodes around
@@ -158,6 +163,11 @@ class ResNet(BaseModule):
                 x = AF.image_to_nhwc(x, 8)
             x = self.conv1(x, bn=self.norm1, relu=True)
             x = AF.max_pool_3x3_s2(x)
+        if AF.mc_dropout_active():
+            # the stem's Dropout2d sits between its ReLU and the max-pool; a factor is one non-negative constant per plane, and max commutes
+            # with that multiplication (rounding included: it is monotone), so the fused conv + BN + ReLU + pool launch stays and the
+            # factor is applied to the pooled tensor
+            x = AF.dropout_apply(x, '.bn1', self)
         outs = []
         AF.check_junctions()
         for i, name in enumerate(self.res_layers):

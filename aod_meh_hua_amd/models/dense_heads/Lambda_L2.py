@@ -87,6 +87,18 @@ class Lambda_L2Net(L_AnchorHead):
         return (self.retina_cls(cls_feat, out_f32=True, sole_consumer=len(self.cls_convs) > 0),
                 self.retina_reg(reg_feat, out_f32=True, sole_consumer=len(self.reg_convs) > 0))
 
+    def forward_cls_dropout(self, feats):
+        """The classification maps of one MC-dropout forward (functional.mc_dropout active, no autograd): the cls tower alone, level-batched
+        (one launch per conv), one Dropout2d per (conv, level) behind its ReLU -- the five levels of one depth in ONE apply launch -- then
+        retina_cls.  The reg and MEH towers do not feed the maps and are not run."""
+        assert AF.mc_dropout_active() and not torch.is_grad_enabled()
+        cls_feat = list(feats)
+        for i, conv in enumerate(self.cls_convs):
+            cls_feat = conv(cls_feat)
+            if conv.with_activation:
+                AF.dropout_apply(cls_feat, [f'.cls_convs.{i}@{l}' for l in range(len(cls_feat))], self)
+        return self.retina_cls(cls_feat, out_f32=True)
+
     def forward_L(self, feats, head_out=None, **kwargs):
         """Lambda_L2.py:82-83,96-103: MEH tower + retina_L + ReLU (fused)."""
         L_feat = list(feats)

@@ -44,6 +44,14 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
 
     def simple_test(self, img, img_metas, rescale=False, **kwargs):
         """SSL_L_single_stage.py:68-98."""
+        mcd = kwargs.get('mc_dropout')
+        if mcd is not None:
+            # one stochastic forward of the MC-dropout baseline (apis/test.py single_gpu_mcdropout; CalMCDropoutUnc.py:137-163): mcd = a
+            # functional.MCDropoutState (factor table, sites); the classification maps of a forward with a Dropout2d behind every ReLU that feeds them
+            from ... import functional as AF
+            assert kwargs['isEval'] and kwargs.get('justOut'), 'MC-dropout forwards return classification maps only (isEval=True, justOut=True)'
+            with AF.mc_dropout(mcd.table, mcd.sites):
+                return list(self.bbox_head.forward_cls_dropout(self.extract_feat(img)))
         feat = self.extract_feat(img)
         if kwargs['isEval'] and kwargs.get('justOut'):
             # MyRetinaSingleStage.py:46-49 (honoured with isEval only): the per-level classification maps [B, A*C, h, w] fp32 of an ensemble

@@ -555,6 +555,27 @@ size_t aod_ensemble_mi_partials_len(int L, const int64_t* n_per_level, int B);
 int aod_ensemble_mi(const void* const* maps, int K, int L, const int64_t* n_per_level, int B, int n_cls, float* out, float* partials_ws,
                     int64_t ws_capacity, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ MC-dropout baseline: Dropout2d factors and their application (csrc/dropout.hip)
+ * The stochastic forward of mmdet/apis/CalMCDropoutUnc.py:137-163: one Dropout2d(rate) behind every ReLU (utils/functions.py:492-505), i.e.
+ * one factor per (image, site, channel), 0 or 1 / (1 - rate), for the whole plane.  The conv kernels are untouched: the factors of one
+ * forward are written into a dense fp32 table [B][T] (T = sum of the sites' channel counts) by ONE launch, and every ReLU output on the
+ * path is multiplied in place by its site's slice of its image's row.
+ *   aod_dropout2d_masks: table[b][site_offsets[s] + c] = u > rate ? 1 / (1 - rate) : 0 with u = u01(word c & 3 of Philox4x32-10 at counter
+ *     (c >> 2, s, sample, (uint32) image_ids[b]), key ((uint32) seed ^ 0x44524F50, seed >> 32)), u01(w) = ((w >> 8) + 1) * 2^-24 in (0, 1]:
+ *     rate = 0 writes ones.  image_ids [B] int64 and site_offsets [n_sites] int32 (ascending, site s spans up to the next offset, the last
+ *     one up to T) are DEVICE arrays; sample is a plain argument.  A factor depends on (seed, sample, image id, site, channel) only.
+ *   aod_dropout2d_apply: NHWC rows [B * HW, width(C)] *= table_row0[(row / HW) * row_stride_T + c], in place.  x3 = 0: bf16 rows of C columns
+ *     (C % 8 == 0), value = bf16_rne((float) x * f).  x3 = 1: X-layout rows of 2 * ceil32(C) columns; head + tail are re-formed in fp32,
+ *     multiplied and split again; pad columns stay zero.
+ *   aod_dropout2d_apply_multi: the same for 1..8 row segments of one buffer `x` in one launch (the tower outputs of one depth: one segment
+ *     per pyramid level): segment s = rows seg_row0[s] .. + B * seg_hw[s], factors table[b * row_stride_T + seg_off[s] + c].  The three
+ *     seg_* arrays are HOST arrays. */
+int aod_dropout2d_masks(float* table, const int64_t* image_ids, int B, const int32_t* site_offsets, int n_sites, int T, float rate,
+                        uint64_t seed, uint32_t sample, aod_stream_t stream);
+int aod_dropout2d_apply(void* x, const float* table_row0, int64_t row_stride_T, int B, int HW, int C, int x3, aod_stream_t stream);
+int aod_dropout2d_apply_multi(void* x, const float* table, int64_t row_stride_T, int B, int nseg, const int64_t* seg_row0,
+                              const int32_t* seg_hw, const int32_t* seg_off, int C, int x3, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */
