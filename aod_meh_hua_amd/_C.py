@@ -107,6 +107,10 @@ _SIGS = {
     'aod_edl_focal_l1_levels_bwd': (C.c_int, [P, P, P, P, P, P, I32, P, I32, F32, F32, P, P, P, P, P, I32, I32, I32, I32, P]),
     'aod_meh_loss_levels_fwd': (C.c_int, [P, P, P, I32, P, P, P, P]),
     'aod_meh_loss_levels_bwd': (C.c_int, [P, P, P, I32, P, P, P, I32, I32, I32, P]),
+    'aod_meh_loss_fwd_ex': (C.c_int, [P, P, P, I64, I32, P, P, P]),
+    'aod_meh_loss_bwd_ex': (C.c_int, [P, P, P, I64, I32, P, P, I32, I32, I32, P]),
+    'aod_meh_loss_levels_fwd_ex': (C.c_int, [P, P, P, I32, P, I32, P, P, P]),
+    'aod_meh_loss_levels_bwd_ex': (C.c_int, [P, P, P, I32, P, I32, P, P, I32, I32, I32, P]),
     'aod_softmax_rowmax': (C.c_int, [P, I32, I64, I32, F32, P, P, I32, P]),
     'aod_topk_stable': (C.c_int, [P, I32, I64, I32, P, I64, P]),
     'aod_pre_nms_levels': (C.c_int, [I32, P, P, P, P, P, P, I32, I32, F32, I32, I32, P, P, P, P, F32, P, P, P, P, P, P, P, I64, P]),
@@ -118,6 +122,8 @@ _SIGS = {
     'aod_hua_score': (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, F32, I32, U64, P, I32, I32, I32, P, P, I32, P, P, P]),
     'aod_hua_score_ex': (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, F32, I32, U64, P, I32, I32, I32, P, P, I32, P,
                                    I32, P, P, P, P]),
+    'aod_hua_score_ex2': (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, F32, I32, U64, P, I32, I32, I32, P, P, I32, P,
+                                    I32, I32, P, P, P, P]),
     'aod_maxpool_fwd': (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
     'aod_maxpool_bwd': (C.c_int, [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
     'aod_l2norm_fwd': (C.c_int, [P, P, P, I64, I32, F32, P]),

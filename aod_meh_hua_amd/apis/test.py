@@ -35,6 +35,7 @@ class Uncertainty_fns:
         return unc.cpu() if torch.is_tensor(unc) else [u.cpu() if torch.is_tensor(u) else u for u in unc]
 
     Entropy_ALL = Entropy_NMS          # test.py:52-63: same loop; the head switches on cfg.uncertainty_pool (ComputeScaleUnc path)
+    Entropy_Avg = Entropy_NMS          # CalMCDropoutUnc.py:65-76: same loop again (Lambda_L2Net_NoL: ComputeAvgUnc + AggregateAvgUnc)
 
     @staticmethod
     def Entropy_NoNMS(cfg, *args, **kwargs):

@@ -33,6 +33,10 @@ struct HuaArgs {
   int nd;           // Dirichlet columns: C (evidence head, zero-padded bg column) or C+1 (SSD softmax incl. background)
   int scale_mode;   // 1: Entropy_ALL / ComputeScaleUnc (Lambda_L2.py:539-569): every foreground anchor is a pair of ONE pseudo object,
                     //    lambda mean over ALL anchors of the (image, level); dets / num_det / boxes are not read
+                    // 2: Entropy_Avg / ComputeAvgUnc + AggregateAvgUnc (Lambda_L2_noL.py:552-572,631-640): the pairs of mode 1, no class bins --
+                    //    mean of the pairs' epistemic values per (image, level), then the mean over the levels that own a pair (hua_avg_kernel)
+  int lam_mode;     // 0: alpha = score * mean(lambda) / (lambda + 1e-7) * 25 (Lambda_L2.py:513-516); 1: alpha = score, lambda is not read
+                    //    (Lambda_L2_noL.py:528-532,588-590: the scaling is commented out there)
   float* unc; float* pair_out; int max_pairs; int* pair_count;
   // workspace
   int* pair_cand; int* pair_obj; int* pair_cls; float* pair_epi; float* pair_ale; int* lvl_pair_start; float* lam_mean; int* nobj;
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(1024) void hua_pairs_kernel(const HuaArgs p) {
   {
     // mean(lambda) over the pairs of (image, level) (Lambda_L2.py:513-515): one wave per level, lanes stride over the pairs
     const int wv = t >> 6, ln = t & 63;
-    if (wv < p.L) {
+    if (wv < p.L && p.lam_mode == 0) {       // (lam_mode 1: nobody reads lam_mean)
       int s = 0, e = 0, acc = 0;
       for (int l = 0; l <= wv; ++l) { s = acc; acc += s_lvl[l + 1]; e = acc; }
       s = min(s, p.max_pairs); e = min(e, p.max_pairs);
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LPP == 1 &&
     const int cand = p.pair_cand[(long long)b * p.max_pairs + pi], obj = p.pair_obj[(long long)b * p.max_pairs + pi];
     const int lvl = level_of(p, cand);
     const float lamv = p.lam[(long long)b * p.n + cand];
-    const float lam_hat = p.lam_mean[b * HMAXL + lvl] / (lamv + 1e-7f) * 25.f;
+    const float lam_hat = p.lam_mode ? 1.f : p.lam_mean[b * HMAXL + lvl] / (lamv + 1e-7f) * 25.f;      // (score * 1.f == score: alpha is the score)
     const float* sc = p.scores + ((long long)b * p.n + cand) * (p.C + 1);
     const unsigned c2 = (unsigned)p.cand_anchor[(long long)b * p.n + cand];
     const unsigned c3 = (unsigned)p.image_ids[b];
@@ -378,7 +382,7 @@ __global__ __launch_bounds__(256) void hua_closed_kernel(const HuaArgs p) {
     const int cand = p.pair_cand[(long long)b * p.max_pairs + pi], obj = p.pair_obj[(long long)b * p.max_pairs + pi];
     const int lvl = level_of(p, cand);
     const float lamv = p.lam[(long long)b * p.n + cand];
-    const float lam_hat = p.lam_mean[b * HMAXL + lvl] / (lamv + 1e-7f) * 25.f;
+    const float lam_hat = p.lam_mode ? 1.f : p.lam_mean[b * HMAXL + lvl] / (lamv + 1e-7f) * 25.f;      // (score * 1.f == score: alpha is the score)
     const float* sc = p.scores + ((long long)b * p.n + cand) * (p.C + 1);
     const bool on0 = lane < nd, on1 = lane + 64 < nd;
     const float s0 = on0 ? sc[lane] : 0.f, s1 = on1 ? sc[lane + 64] : 0.f;
@@ -537,17 +541,47 @@ __global__ __launch_bounds__(1024) void hua_reduce_kernel(const HuaArgs p) {
   }
 }
 
+// H3'' (scale_mode = 2, Entropy_Avg): one block per image.  Per level, thread t sums the epistemic values of pairs s + t, s + t + 1024, ...
+// in that order, the 1024 partial sums fold in a fixed LDS tree, thread 0 divides by the pair count and adds the level means in level
+// order: no atomics, and nothing depends on the other images of the batch -- an image scores the same bits alone, in any batch, on any
+// rank count.  A level counts iff it owns a pair (the reference's `if sUncs:` also drops a level whose mean is exactly 0.0: not reproduced);
+// an image without a pair scores 0 (the reference: mean of an empty list = NaN, which update_X_L's argsort would rank most uncertain).
+__global__ __launch_bounds__(1024) void hua_avg_kernel(const HuaArgs p) {
+  __shared__ float s_sum[1024];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const float* pe = p.pair_epi + (long long)b * p.max_pairs;
+  float acc = 0.f;
+  int nl = 0;
+  for (int l = 0; l < p.L; ++l) {
+    const int s = p.lvl_pair_start[b * (HMAXL + 1) + l], e = p.lvl_pair_start[b * (HMAXL + 1) + l + 1];
+    if (e <= s) continue;                          // (block-uniform)
+    float v = 0.f;
+    for (int k = s + t; k < e; k += 1024) v += pe[k];
+    s_sum[t] = v;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+      if (t < o) s_sum[t] += s_sum[t + o];
+      __syncthreads();
+    }
+    if (t == 0) { acc += s_sum[0] / (float)(e - s); ++nl; }
+    __syncthreads();
+  }
+  if (t == 0) p.unc[b] = nl ? acc / (float)nl : 0.f;
+}
+
 extern "C" size_t aod_hua_ws_bytes(int B, int max_pairs) {
   return (size_t)B * ((size_t)max_pairs * 20 + (HMAXL + 1) * 4 + HMAXL * 4 + 4 + HMAXO * 4) + 64;      // (+ the object -> detection row map)
 }
 
-extern "C" int aod_hua_score_ex(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
+extern "C" int aod_hua_score_ex2(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
                                 const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg, const int64_t* image_ids,
                                 int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr, float fg_thr, int num_samples,
                                 uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode, int dirichlet_cols, float* unc, float* pair_out,
-                                int max_pairs, int32_t* pair_count, int estimator, float* obj_out, int32_t* obj_pairs, void* ws,
+                                int max_pairs, int32_t* pair_count, int estimator, int lam_mode, float* obj_out, int32_t* obj_pairs, void* ws,
                                 aod_stream_t stream) {
   if (B == 0) return 0;
+  AOD_CHECK_ARG(lam_mode == 0 || lam_mode == 1, "hua: lam_mode must be 0 (lambda-scaled alpha) or 1 (alpha = score)");
+  AOD_CHECK_ARG(scale_mode >= 0 && scale_mode <= 2, "hua: scale_mode must be 0 (objects), 1 (Entropy_ALL) or 2 (Entropy_Avg)");
   AOD_CHECK_ARG(estimator == 0 || estimator == 1, "hua: estimator must be 0 (Monte-Carlo) or 1 (closed form)");
   AOD_CHECK_ARG((obj_out == nullptr) == (obj_pairs == nullptr), "hua: obj_out and obj_pairs come together");
   AOD_CHECK_ARG(!(obj_out && scale_mode), "hua: per-object outputs are not offered in scale_mode");
@@ -562,7 +596,7 @@ extern "C" int aod_hua_score_ex(const float* boxes, const float* scores, const f
   AOD_CHECK_ARG(p.level_start[0] == 0 && p.level_start[L] == n, "hua: level_start must cover [0, n)");
   p.obj_score_thr = obj_score_thr; p.obj_iou_thr = obj_iou_thr; p.fg_thr = fg_thr; p.num_samples = num_samples;
   p.seed_lo = (unsigned)(seed & 0xffffffffull); p.seed_hi = (unsigned)(seed >> 32);
-  p.agg_class = agg3_host ? agg3_host[0] : 0; p.agg_scale = agg3_host ? agg3_host[1] : 2; p.agg_obj = agg3_host ? agg3_host[2] : 0; p.clsW = clsW; p.scale_mode = scale_mode; p.nd = dirichlet_cols > 0 ? dirichlet_cols : C;
+  p.agg_class = agg3_host ? agg3_host[0] : 0; p.agg_scale = agg3_host ? agg3_host[1] : 2; p.agg_obj = agg3_host ? agg3_host[2] : 0; p.clsW = clsW; p.scale_mode = scale_mode; p.lam_mode = lam_mode; p.nd = dirichlet_cols > 0 ? dirichlet_cols : C;
   AOD_CHECK_ARG(p.nd == C || p.nd == C + 1, "hua: dirichlet_cols must be C or C+1");
   p.unc = unc; p.pair_out = pair_out; p.max_pairs = max_pairs; p.pair_count = pair_count;
   char* w = (char*)ws;
@@ -586,10 +620,22 @@ extern "C" int aod_hua_score_ex(const float* boxes, const float* scores, const f
   else if (p.nd <= 24) AOD_HUA_SAMPLE(24, 1, false);
   else AOD_HUA_SAMPLE(24, 4, false);
 #undef AOD_HUA_SAMPLE
-  if (obj_out) hipLaunchKernelGGL(hua_reduce_kernel<true>, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
+  if (scale_mode == 2) hipLaunchKernelGGL(hua_avg_kernel, dim3(B), dim3(1024), 0, st, p);
+  else if (obj_out) hipLaunchKernelGGL(hua_reduce_kernel<true>, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
   else hipLaunchKernelGGL(hua_reduce_kernel<false>, dim3(B), dim3(1024), (size_t)max_num * p.nd * 4, st, p);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int aod_hua_score_ex(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,
+                                const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg, const int64_t* image_ids,
+                                int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr, float fg_thr, int num_samples,
+                                uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode, int dirichlet_cols, float* unc, float* pair_out,
+                                int max_pairs, int32_t* pair_count, int estimator, float* obj_out, int32_t* obj_pairs, void* ws,
+                                aod_stream_t stream) {
+  return aod_hua_score_ex2(boxes, scores, lam, cand_anchor, dets, num_det, level_start_host, level_any_fg, image_ids, B, n, L, C, max_num,
+                           obj_score_thr, obj_iou_thr, fg_thr, num_samples, seed, agg3_host, clsW, scale_mode ? 1 : 0, dirichlet_cols, unc,
+                           pair_out, max_pairs, pair_count, estimator, 0, obj_out, obj_pairs, ws, stream);
 }
 
 extern "C" int aod_hua_score(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor, const float* dets,

@@ -409,6 +409,15 @@ extern "C" int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labe
 }
 
 // ---------------------------------------------------------------- MEH loss
+// FORM (launch-uniform, one kernel instance each): how the Model Evidence Head is regressed onto the detached per-anchor loss
+//   0  L2    sum(((|lam + 1e-9 - loss|) * w)^2)                       Lambda_L2.py:235-241
+//   1  L1    sum(|(|lam + 1e-9 - loss|) * w|)                         Lambda_L1.py:239-241
+//   2  MSLE  sum(((|log(lam + 1e-9 + 1) - log(loss + 1)|) * w)^2)     Lambda_MSLE.py:239-242
+// The gradients are autograd's, factor by factor: abs' = sign (0 at 0), so the L1 gradient is g * sign(|d| * w) * w * sign(d) = g * |w| * sign(d)
+// (a negative weight flips twice) and 0 where lam + 1e-9 == loss; MSLE's is ((g * 2 * (|d| * w)) * w) * sign(d) / (lam + 1e-9 + 1).  The two
+// logs cancel where lam ~ loss: the accurate logf, not the hardware log2 -- the kernels are bound by their three input streams.
+__device__ __forceinline__ float sign0(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+template <int FORM>
 __global__ __launch_bounds__(256) void meh_fwd_kernel(const float* __restrict__ lam, const float* __restrict__ loss, const float* __restrict__ bw4,
                                                       const LossLevels lv, float* __restrict__ partials) {
   float s = 0.f;
@@ -416,8 +425,15 @@ __global__ __launch_bounds__(256) void meh_fwd_kernel(const float* __restrict__ 
   level_of_block(lv, (int)blockIdx.x, level, blk0, row0, n);
   const long long i = row0 + (long long)((int)blockIdx.x - blk0) * 256 + threadIdx.x;
   if (i < n) {
-    const float d = fabsf(lam[i] + 1e-9f - loss[i]) * bw4[i * 4];
-    s = d * d;
+    if (FORM == 1) {
+      s = fabsf(fabsf(lam[i] + 1e-9f - loss[i]) * bw4[i * 4]);
+    } else if (FORM == 2) {
+      const float d = fabsf(logf(lam[i] + 1e-9f + 1.f) - logf(loss[i] + 1.f)) * bw4[i * 4];
+      s = d * d;
+    } else {
+      const float d = fabsf(lam[i] + 1e-9f - loss[i]) * bw4[i * 4];
+      s = d * d;
+    }
   }
   __shared__ float red[4];
   s = wave_sum(s);
@@ -425,7 +441,7 @@ __global__ __launch_bounds__(256) void meh_fwd_kernel(const float* __restrict__ 
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
-template <bool OUT_BF16>
+template <bool OUT_BF16, int FORM>
 __global__ void meh_bwd_kernel(const float* __restrict__ lam, const float* __restrict__ loss, const float* __restrict__ bw4, const LossLevels lv,
                                const float* __restrict__ g, void* __restrict__ grad, int A, int pitch, int g_lstride) {
   int level, blk0; long long row0, n;
@@ -433,58 +449,102 @@ __global__ void meh_bwd_kernel(const float* __restrict__ lam, const float* __res
   const long long i = row0 + (long long)((int)blockIdx.x - blk0) * 256 + threadIdx.x;
   if (i < n) {
     const float w = bw4[i * 4];
-    const float v = g[level * g_lstride] * 2.f * w * w * (lam[i] + 1e-9f - loss[i]);
+    float v;
+    if (FORM == 1) {
+      const float d = lam[i] + 1e-9f - loss[i];
+      v = g[level * g_lstride] * sign0(fabsf(d) * w) * w * sign0(d);
+    } else if (FORM == 2) {
+      const float x = lam[i] + 1e-9f + 1.f;
+      const float d = logf(x) - logf(loss[i] + 1.f);
+      v = g[level * g_lstride] * 2.f * (fabsf(d) * w) * w * sign0(d) / x;
+    } else {
+      v = g[level * g_lstride] * 2.f * w * w * (lam[i] + 1e-9f - loss[i]);
+    }
     const long long o = (i / A) * pitch + (i % A);
     if (OUT_BF16) ((bf16_t*)grad)[o] = (bf16_t)v; else ((float*)grad)[o] = v;
   }
 }
-extern "C" int aod_meh_loss_fwd(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, float* out_sum, float* partials,
-                                aod_stream_t stream) {
+#define AOD_MEH_FWD(nb_)                                                                                                                   \
+  do {                                                                                                                                     \
+    if (form == 1) hipLaunchKernelGGL(meh_fwd_kernel<1>, dim3((unsigned)(nb_)), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, partials); \
+    else if (form == 2) hipLaunchKernelGGL(meh_fwd_kernel<2>, dim3((unsigned)(nb_)), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, partials); \
+    else hipLaunchKernelGGL(meh_fwd_kernel<0>, dim3((unsigned)(nb_)), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, partials); \
+  } while (0)
+#define AOD_MEH_BWD_(BF, F_, nb_, ls_)                                                                                                     \
+  hipLaunchKernelGGL((meh_bwd_kernel<BF, F_>), dim3((unsigned)(nb_)), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, g, grad_lam, A, pitch, ls_)
+#define AOD_MEH_BWD(nb_, ls_)                                                                                                              \
+  do {                                                                                                                                     \
+    if (out_bf16) { if (form == 1) AOD_MEH_BWD_(true, 1, nb_, ls_); else if (form == 2) AOD_MEH_BWD_(true, 2, nb_, ls_); else AOD_MEH_BWD_(true, 0, nb_, ls_); } \
+    else { if (form == 1) AOD_MEH_BWD_(false, 1, nb_, ls_); else if (form == 2) AOD_MEH_BWD_(false, 2, nb_, ls_); else AOD_MEH_BWD_(false, 0, nb_, ls_); } \
+  } while (0)
+extern "C" int aod_meh_loss_fwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, int form, float* out_sum,
+                                   float* partials, aod_stream_t stream) {
   AOD_CHECK_ARG(lam && loss_noR && bbox_w4 && out_sum && partials, "meh_fwd: null pointer");
+  AOD_CHECK_ARG(form >= 0 && form <= 2, "meh_fwd: form must be 0 (L2), 1 (L1) or 2 (MSLE)");
   if (n == 0) return 0;
   LossLevels lv; long long tot;
   const long long nb = fill_levels(lv, 1, &n, 256, tot);
-  hipLaunchKernelGGL(meh_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, partials);
+  AOD_MEH_FWD(nb);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nb, 1, out_sum);
   AOD_LAUNCH_CHECK();
   return 0;
 }
-// all levels in one launch (Lambda_L2.py:235-241 once per level): out_sums[nlevels]
-extern "C" int aod_meh_loss_levels_fwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
-                                       float* out_sums, float* partials, aod_stream_t stream) {
+extern "C" int aod_meh_loss_fwd(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, float* out_sum, float* partials,
+                                aod_stream_t stream) {
+  return aod_meh_loss_fwd_ex(lam, loss_noR, bbox_w4, n, 0, out_sum, partials, stream);
+}
+// all levels in one launch (Lambda_L2.py:235-241 / Lambda_L1.py:236-241 / Lambda_MSLE.py:236-242 once per level): out_sums[nlevels]
+extern "C" int aod_meh_loss_levels_fwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
+                                          int form, float* out_sums, float* partials, aod_stream_t stream) {
   AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "meh_levels_fwd: 1..8 levels");
   AOD_CHECK_ARG(lam && loss_noR && bbox_w4 && out_sums && partials, "meh_levels_fwd: null pointer");
+  AOD_CHECK_ARG(form >= 0 && form <= 2, "meh_levels_fwd: form must be 0 (L2), 1 (L1) or 2 (MSLE)");
   LossLevels lv; long long tot;
   const int nb = fill_levels(lv, nlevels, level_rows, 256, tot);
-  if (nb) hipLaunchKernelGGL(meh_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, partials);
+  if (nb) AOD_MEH_FWD(nb);
   hipLaunchKernelGGL(reduce_partials_levels_kernel, dim3(nlevels), dim3(256), 0, (hipStream_t)stream, partials, lv, 1, out_sums, 1, nlevels, (const int*)nullptr,
                      0, (float*)nullptr, (float*)nullptr);
   AOD_LAUNCH_CHECK();
   return 0;
 }
-extern "C" int aod_meh_loss_bwd(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, const float* g, void* grad_lam,
-                                int out_bf16, int A, int pitch, aod_stream_t stream) {
+extern "C" int aod_meh_loss_levels_fwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
+                                       float* out_sums, float* partials, aod_stream_t stream) {
+  return aod_meh_loss_levels_fwd_ex(lam, loss_noR, bbox_w4, nlevels, level_rows, 0, out_sums, partials, stream);
+}
+extern "C" int aod_meh_loss_bwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, int form, const float* g,
+                                   void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream) {
   AOD_CHECK_ARG(lam && loss_noR && bbox_w4 && g && grad_lam && A >= 1 && pitch >= A, "meh_bwd: bad args");
+  AOD_CHECK_ARG(form >= 0 && form <= 2, "meh_bwd: form must be 0 (L2), 1 (L1) or 2 (MSLE)");
   if (n == 0) return 0;
   LossLevels lv; long long tot;
   const long long nb = fill_levels(lv, 1, &n, 256, tot);
-  if (out_bf16) hipLaunchKernelGGL((meh_bwd_kernel<true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, g, grad_lam, A, pitch, 0);
-  else hipLaunchKernelGGL((meh_bwd_kernel<false>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, g, grad_lam, A, pitch, 0);
+  AOD_MEH_BWD(nb, 0);
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int aod_meh_loss_bwd(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, const float* g, void* grad_lam,
+                                int out_bf16, int A, int pitch, aod_stream_t stream) {
+  return aod_meh_loss_bwd_ex(lam, loss_noR, bbox_w4, n, 0, g, grad_lam, out_bf16, A, pitch, stream);
+}
+extern "C" int aod_meh_loss_levels_bwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
+                                          int form, const float* g, void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream) {
+  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "meh_levels_bwd: 1..8 levels");
+  AOD_CHECK_ARG(lam && loss_noR && bbox_w4 && g && grad_lam && A >= 1 && pitch >= A, "meh_levels_bwd: bad args");
+  AOD_CHECK_ARG(form >= 0 && form <= 2, "meh_levels_bwd: form must be 0 (L2), 1 (L1) or 2 (MSLE)");
+  LossLevels lv; long long tot;
+  const int nb = fill_levels(lv, nlevels, level_rows, 256, tot);
+  if (nb == 0) return 0;
+  AOD_MEH_BWD(nb, 1);
   AOD_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int aod_meh_loss_levels_bwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
                                        const float* g, void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream) {
-  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "meh_levels_bwd: 1..8 levels");
-  AOD_CHECK_ARG(lam && loss_noR && bbox_w4 && g && grad_lam && A >= 1 && pitch >= A, "meh_levels_bwd: bad args");
-  LossLevels lv; long long tot;
-  const int nb = fill_levels(lv, nlevels, level_rows, 256, tot);
-  if (nb == 0) return 0;
-  if (out_bf16) hipLaunchKernelGGL((meh_bwd_kernel<true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, g, grad_lam, A, pitch, 1);
-  else hipLaunchKernelGGL((meh_bwd_kernel<false>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lam, loss_noR, bbox_w4, lv, g, grad_lam, A, pitch, 1);
-  AOD_LAUNCH_CHECK();
-  return 0;
+  return aod_meh_loss_levels_bwd_ex(lam, loss_noR, bbox_w4, nlevels, level_rows, 0, g, grad_lam, out_bf16, A, pitch, stream);
 }
+#undef AOD_MEH_FWD
+#undef AOD_MEH_BWD
+#undef AOD_MEH_BWD_
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Elementwise form [rows, C] of the EDL softmax-focal loss: what EDL_Softmax_FocalLoss.forward(reduction='none') returns in the

@@ -1480,19 +1480,19 @@ class MEHLossLevelsFn(Function):
     all-level views; returns the per-level sums [L]."""
 
     @staticmethod
-    def forward(ctx, lam, loss_noR, bbox_w, level_rows, A):
-        out = ho.meh_loss_levels_fwd(lam, loss_noR, bbox_w, level_rows)
+    def forward(ctx, lam, loss_noR, bbox_w, level_rows, A, form='l2'):
+        out = ho.meh_loss_levels_fwd(lam, loss_noR, bbox_w, level_rows, form=form)
         ctx.save_for_backward(lam, loss_noR, bbox_w)
-        ctx.cfg = (tuple(level_rows), A)
+        ctx.cfg = (tuple(level_rows), A, form)
         return out
 
     @staticmethod
     def backward(ctx, g):
         lam, loss_noR, bw = ctx.saved_tensors
-        level_rows, A = ctx.cfg
+        level_rows, A, form = ctx.cfg
         gl = torch.empty(lam.numel() // A, A, dtype=torch.float32, device=lam.device)
-        ho.meh_loss_levels_bwd(lam, loss_noR, bw, level_rows, g.float().contiguous(), gl, A)
-        return gl.view(lam.shape), None, None, None, None
+        ho.meh_loss_levels_bwd(lam, loss_noR, bw, level_rows, g.float().contiguous(), gl, A, form=form)
+        return gl.view(lam.shape), None, None, None, None, None
 
 
 class _LevelViewsFn(Function):
@@ -1525,15 +1525,16 @@ def dense_levels(levels):
 
 
 class MEHLossFn(Function):
-    """sum(((|lambda + 1e-9 - loss_noR|) * w)^2) for one level (Lambda_L2.py:235-241)."""
+    """sum(((|lambda + 1e-9 - loss_noR|) * w)^2) for one level (Lambda_L2.py:235-241); form = 'l1' / 'msle': the sums of Lambda_L1.py:239-241 /
+    Lambda_MSLE.py:239-242 (hipops.MEH_FORMS)."""
 
     @staticmethod
-    def forward(ctx, L_score, loss_noR, bbox_w, arena=None, level=0):
-        ctx.arena, ctx.level = arena, level
+    def forward(ctx, L_score, loss_noR, bbox_w, arena=None, level=0, form='l2'):
+        ctx.arena, ctx.level, ctx.form = arena, level, form
         lam = as_rows(L_score).view(-1)
         bw = bbox_w.reshape(-1, 4).contiguous()
         loss_noR = loss_noR.contiguous()
-        out = ho.meh_loss_fwd(lam, loss_noR, bw)
+        out = ho.meh_loss_fwd(lam, loss_noR, bw, form=form)
         ctx.save_for_backward(lam, loss_noR, bw)
         ctx.shape = L_score.shape
         return out[0]
@@ -1543,5 +1544,5 @@ class MEHLossFn(Function):
         lam, loss_noR, bw = ctx.saved_tensors
         B, A, H, W = ctx.shape
         dst = ctx.arena.slice('lam', ctx.level, B * H * W, A, lam.device).view(-1, 1) if ctx.arena is not None else None
-        gl = ho.meh_loss_bwd(lam, loss_noR, bw, g.reshape(1).float().contiguous(), grad=dst)
-        return as_nchw(gl.view(B * H * W, A), B, H, W), None, None, None, None
+        gl = ho.meh_loss_bwd(lam, loss_noR, bw, g.reshape(1).float().contiguous(), grad=dst, form=ctx.form)
+        return as_nchw(gl.view(B * H * W, A), B, H, W), None, None, None, None, None

@@ -382,7 +382,7 @@ class GraphedScore:
         self.dev = next(_unwrap(model).parameters()).device
         m = _unwrap(model)
         two_phase = (hasattr(m, 'extract_feat') and hasattr(getattr(m, 'bbox_head', None), 'test_heads') and not score_kwargs.get('isEval')
-                     and getattr(m.test_cfg, 'uncertainty_pool', None) in ('Entropy_NMS', 'Entropy_ALL'))
+                     and getattr(m.test_cfg, 'uncertainty_pool', None) in ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg'))
         self.pipe = two_phase and (os.environ.get('AOD_SCORE_PIPELINE', '1') != '0' if pipeline is None else bool(pipeline))
         self.s_conv = self.s_tail = None
 

@@ -693,20 +693,29 @@ def edl_focal_l1_bwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, g_cls, g
     return grad_cls, grad_bbox
 
 
-def meh_loss_fwd(lam, loss_noR, bbox_w4, out_sum=None):
+MEH_FORMS = {'l2': 0, 'l1': 1, 'msle': 2}      # Lambda_L2.py:240-241 | Lambda_L1.py:240-241 | Lambda_MSLE.py:240-242
+
+
+def meh_loss_fwd(lam, loss_noR, bbox_w4, out_sum=None, form='l2'):
     n = lam.numel()
     if out_sum is None:
         out_sum = zeros_f32(1, lam.device)
     part = torch.empty(max(int(_C.lib.aod_loss_partials_len(n)), 1), dtype=torch.float32, device=lam.device)
+    if form != 'l2':
+        call('aod_meh_loss_fwd_ex', ptr(lam), ptr(loss_noR), ptr(bbox_w4), n, MEH_FORMS[form], ptr(out_sum), ptr(part), stream())
+        return out_sum
     call('aod_meh_loss_fwd', ptr(lam), ptr(loss_noR), ptr(bbox_w4), n, ptr(out_sum), ptr(part), stream())
     return out_sum
 
 
-def meh_loss_bwd(lam, loss_noR, bbox_w4, g, out_bf16=False, A=1, pitch=None, grad=None):
+def meh_loss_bwd(lam, loss_noR, bbox_w4, g, out_bf16=False, A=1, pitch=None, grad=None, form='l2'):
     n = lam.numel()
     pitch = pitch or A
     if grad is None:
         grad = (torch.empty if pitch == A else torch.zeros)(n // A, pitch, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=lam.device)
+    if form != 'l2':
+        call('aod_meh_loss_bwd_ex', ptr(lam), ptr(loss_noR), ptr(bbox_w4), n, MEH_FORMS[form], ptr(g), ptr(grad), int(out_bf16), A, pitch, stream())
+        return grad
     call('aod_meh_loss_bwd', ptr(lam), ptr(loss_noR), ptr(bbox_w4), n, ptr(g), ptr(grad), int(out_bf16), A, pitch, stream())
     return grad
 
@@ -752,20 +761,26 @@ def edl_focal_l1_levels_bwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, l
     return grad_cls, grad_bbox
 
 
-def meh_loss_levels_fwd(lam, loss_noR, bbox_w4, level_rows):
+def meh_loss_levels_fwd(lam, loss_noR, bbox_w4, level_rows, form='l2'):
     L = len(level_rows)
     assert sum(level_rows) == lam.numel()
     lr = _level_rows(level_rows)
     out = torch.empty(L, dtype=torch.float32, device=lam.device)
     part = torch.empty(max(int(_C.lib.aod_loss_levels_partials_len(L, lr)), 1), dtype=torch.float32, device=lam.device)
+    if form != 'l2':
+        call('aod_meh_loss_levels_fwd_ex', ptr(lam), ptr(loss_noR), ptr(bbox_w4), L, lr, MEH_FORMS[form], ptr(out), ptr(part), stream())
+        return out
     call('aod_meh_loss_levels_fwd', ptr(lam), ptr(loss_noR), ptr(bbox_w4), L, lr, ptr(out), ptr(part), stream())
     return out
 
 
-def meh_loss_levels_bwd(lam, loss_noR, bbox_w4, level_rows, g, grad, A):
+def meh_loss_levels_bwd(lam, loss_noR, bbox_w4, level_rows, g, grad, A, form='l2'):
     L = len(level_rows)
     lr = _level_rows(level_rows)
     assert g.shape == (L,) and g.is_contiguous() and g.dtype == torch.float32
+    if form != 'l2':
+        call('aod_meh_loss_levels_bwd_ex', ptr(lam), ptr(loss_noR), ptr(bbox_w4), L, lr, MEH_FORMS[form], ptr(g), ptr(grad), 0, A, A, stream())
+        return grad
     call('aod_meh_loss_levels_bwd', ptr(lam), ptr(loss_noR), ptr(bbox_w4), L, lr, ptr(g), ptr(grad), 0, A, A, stream())
     return grad
 

@@ -119,6 +119,11 @@ class Lambda_L2Net(L_AnchorHead):
 
     # ------------------------------------------------------------------ losses
     _can_defer_avg = True
+    # what the reference's ablation heads change (models/dense_heads/Lambda_ablations.py sets them, and nothing else):
+    _meh_form = 'l2'             # MEH regression form: 'l2' | 'l1' | 'msle' (hipops.MEH_FORMS)
+    _hua_lam = 'scaled'          # 'scaled': alpha = score * mean(lambda) / (lambda + 1e-7) * 25; 'none': alpha = score
+    _hua_thr_kwargs = False      # True: the score_thr / iou_thr kwargs replace HUA's 0.3 / 0.5 (this head ignores them, as its reference does)
+    _hua_entropy_avg = False     # True: uncertainty_pool = 'Entropy_Avg' is offered
 
     @force_fp32(apply_to=('cls_score', 'bbox_pred'))
     def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights, sIdx, num_total_samples, **kwargs):
@@ -171,12 +176,12 @@ class Lambda_L2Net(L_AnchorHead):
         level_rows = [l.shape[0] * l.shape[2] * l.shape[3] * A for l in L_scores]
         if [int(t.numel()) for t in losses] != level_rows:
             return None
-        return AF.MEHLossLevelsFn.apply(lam_d.view(-1), noR, bw, level_rows, A)
+        return AF.MEHLossLevelsFn.apply(lam_d.view(-1), noR, bw, level_rows, A, self._meh_form)
 
     @force_fp32(apply_to=('L_score'))
     def loss_single_L(self, L_score, loss, label_weights, bbox_weights, sIdx=0, **kwargs):
-        """Lambda_L2.py:235-241: mean(((|lambda + 1e-9 - loss|) * bbox_weights[...,0])^2) * 5."""
-        s = AF.MEHLossFn.apply(L_score, loss, bbox_weights, kwargs.get('grad_arena'), int(sIdx))
+        """Lambda_L2.py:235-241: mean(((|lambda + 1e-9 - loss|) * bbox_weights[...,0])^2) * 5 (`_meh_form`: the L1 / MSLE sums instead)."""
+        s = AF.MEHLossFn.apply(L_score, loss, bbox_weights, kwargs.get('grad_arena'), int(sIdx), self._meh_form)
         if kwargs.get('defer_scale'):                             # loss_L() scales all levels in one launch
             return s, 5.0 / loss.numel()
         return s * (5.0 / loss.numel()), 0
@@ -208,6 +213,8 @@ class Lambda_L2Net(L_AnchorHead):
         outs, L_scores = _preds if _preds is not None else self.test_heads(feats)
         if not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_NoNMS':
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=False, **kwargs)
+        elif not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_Avg':      # (Lambda_L2Net_NoL; any other head: score_batch raises)
+            results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=False, L_scores=L_scores, **kwargs)
         elif not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_ALL':
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=bool(kwargs.get('showNMS')), L_scores=L_scores, **kwargs)
         elif not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_NMS':

@@ -176,16 +176,27 @@ def multiclass_nms_batch(boxes, scores, score_thr, iou_thr, max_num):
 
 
 HUA_ESTIMATORS = {'mc': 0, 'closed': 1}
+HUA_LAM_MODES = {'scaled': 0, 'none': 1}
 
 
 def hua_score(cand, dets, num_det, image_ids, max_num, agg=(0, 2, 0), clsW=False, num_samples=500, seed=20, obj_score_thr=0.3,
               obj_iou_thr=0.5, fg_thr=0.3, want_pairs=False, max_pairs=None, scale_mode=False, dirichlet_cols=0, estimator='mc',
-              want_objects=False):
+              want_objects=False, lam_mode='scaled'):
     """estimator: 'mc' (num_samples Dirichlet draws, seeded) or 'closed' (the closed form of the Monte-Carlo limit: no seed, no sample count).
+    The closed form is the n -> infinity limit; it is NOT the expectation of a finite-sample run (the `total` term of the Monte-Carlo
+    estimator, the entropy of the mean of n samples, is biased downwards at finite n), so 'closed' and 'mc' with 50 samples (Entropy_Avg) differ by more than sampling noise.
+    lam_mode: 'scaled' (alpha = score * mean(lambda) / (lambda + 1e-7) * 25, Lambda_L2.py:513-516) or 'none' (alpha = score: Lambda_L2Net_NoL,
+    Lambda_L2_noL.py:526-532, 586-592).
+    scale_mode: False (objects), True (Entropy_ALL: class bins per level) or 'avg' (Entropy_Avg, Lambda_L2_noL.py:552-572, 631-640: mean over
+    the levels that own a foreground row of the level's mean per-row epistemic value; `agg` / `clsW` are not read).
     want_objects appends (obj_out [B, max_num, 2] = (aleatoric, epistemic) per detection row, obj_pairs [B, max_num] int32) to the return;
     rows that are no object (score <= obj_score_thr, row >= num_det) or own no pair hold (NaN, NaN, 0)."""
     if estimator not in HUA_ESTIMATORS:
         raise ValueError(f"hua_score: unknown estimator {estimator!r} (expected 'mc' or 'closed')")
+    if lam_mode not in HUA_LAM_MODES:
+        raise ValueError(f"hua_score: unknown lam_mode {lam_mode!r} (expected 'scaled' or 'none')")
+    if scale_mode not in (False, True, 'avg', 0, 1):
+        raise ValueError(f"hua_score: unknown scale_mode {scale_mode!r} (expected False, True or 'avg')")
     if want_objects and scale_mode:
         raise ValueError('hua_score: per-object outputs are not offered in scale_mode')
     B, n, C1 = cand.scores.shape
@@ -196,6 +207,17 @@ def hua_score(cand, dets, num_det, image_ids, max_num, agg=(0, 2, 0), clsW=False
     pair_count = torch.empty(B, dtype=torch.int32, device=dev)
     pair_out = torch.zeros(B, max_pairs, 4, device=dev) if want_pairs else None
     ws = torch.empty(int(_C.lib.aod_hua_ws_bytes(B, max_pairs)), dtype=torch.uint8, device=dev)
+    if lam_mode != 'scaled' or scale_mode == 'avg':
+        obj_out = torch.empty(B, int(max_num), 2, device=dev) if want_objects else None
+        obj_pairs = torch.empty(B, int(max_num), dtype=torch.int32, device=dev) if want_objects else None
+        call('aod_hua_score_ex2', ptr(cand.boxes), ptr(cand.scores), ptr(cand.lam), ptr(cand.cand_anchor), ptr(dets), ptr(num_det),
+             (C.c_int32 * (L + 1))(*cand.level_start), ptr(cand.any_fg), ptr(image_ids), B, n, L, C1 - 1, int(max_num), float(obj_score_thr),
+             float(obj_iou_thr), float(fg_thr), int(num_samples), int(seed), (C.c_int32 * 3)(*agg), int(bool(clsW)),
+             2 if scale_mode == 'avg' else int(bool(scale_mode)), int(dirichlet_cols), ptr(unc), ptr(pair_out), int(max_pairs), ptr(pair_count),
+             HUA_ESTIMATORS[estimator], HUA_LAM_MODES[lam_mode], ptr(obj_out), ptr(obj_pairs), ptr(ws), stream())
+        out = (unc, pair_count, pair_out) if want_pairs else (unc,)
+        out = out + (obj_out, obj_pairs) if want_objects else out
+        return out if len(out) > 1 else unc
     if estimator != 'mc' or want_objects:
         obj_out = torch.empty(B, int(max_num), 2, device=dev) if want_objects else None
         obj_pairs = torch.empty(B, int(max_num), dtype=torch.int32, device=dev) if want_objects else None
@@ -283,8 +305,17 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                  with _padded=True   -> (dets [B,max,5], labels [B,max] int64, num [B] int32) on the device, no host sync;
                  with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
-    hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / detUnc paths.
-    isUnc with uPool == 'Entropy_NMS' -> (det_results, unc [B] device tensor)."""
+    hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / Entropy_Avg / detUnc paths.
+    isUnc with uPool == 'Entropy_NMS' -> (det_results, unc [B] device tensor).
+    Two class attributes of the head select the reference's ablations: `_hua_lam` ('scaled' | 'none': whether lambda scales alpha) and
+    `_hua_thr_kwargs` (whether the `score_thr` / `iou_thr` kwargs replace the 0.3 / 0.5 of GetObjectIdx, the level gate and the candidate
+    filter, Lambda_L2_ablation.py:261-265,355,496-518; a falsy or missing value falls back to 0.3 / 0.5).
+    uPool == 'Entropy_Avg' (Lambda_L2Net_NoL only, Lambda_L2_noL.py:367-369,552-572,631-640): per (image, level) the rows are all anchors
+    whose softmax maximum exceeds 0.3 (hard-coded there, not score_thr; no top-k), 50 Dirichlet(softmax) samples per row, level value = mean
+    of the rows' epistemic values, image score = mean over the levels that have such a row.  Two corner cases of the reference are NOT
+    reproduced: an image without a foreground row on any level scores 0 here (there: mean of an empty list = NaN, which update_X_L's
+    argsort ranks most uncertain), and a level counts iff it has a foreground row (there `if sUncs:` also drops a level whose mean is
+    exactly 0.0)."""
     assert head.last_activation in ('relu', 'softmax')
     has_bg = head.last_activation == 'softmax'         # SSD: 21 logits incl. background (My_L_ssd_head.py:331-345)
     C_ = head.cls_out_channels
@@ -293,18 +324,30 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     uPool = kwargs.get('uPool')
     if isUnc and uPool == 'Entropy_NoNMS':
         raise NotImplementedError('uncertainty_pool=Entropy_NoNMS crashes in the reference too (ComputeScaleUnc with L_scores=None)')
-    if isUnc and uPool == 'Entropy_ALL':
+    lam_mode = getattr(head, '_hua_lam', 'scaled')
+    obj_thr, iou_thr = 0.3, 0.5
+    if getattr(head, '_hua_thr_kwargs', False):
+        obj_thr, iou_thr = float(kwargs.get('score_thr') or 0.3), float(kwargs.get('iou_thr') or 0.5)
+    if isUnc and uPool == 'Entropy_Avg' and not getattr(head, '_hua_entropy_avg', False):
+        raise NotImplementedError(f'uncertainty_pool=Entropy_Avg is offered by Lambda_L2Net_NoL only: the reference of {type(head).__name__} '
+                                  'has no such branch')
+    if isUnc and uPool in ('Entropy_ALL', 'Entropy_Avg'):
         # Lambda_L2.py:281-283 (no top-k), :354 (no NMS), :364-365 ComputeScaleUnc + AggregateScaleUnc
-        assert not has_bg, 'Entropy_ALL is built for the RetinaNet evidence head'
+        # Entropy_Avg (Lambda_L2_noL.py:367-369): the same front end (every anchor a candidate, raw softmax), ComputeAvgUnc + AggregateAvgUnc
+        assert not has_bg, f'{uPool} is built for the RetinaNet evidence head'
         cand = pre_nms(mlvl_cls_scores, mlvl_bbox_preds, kwargs['L_scores'], mlvl_anchors, img_shapes, scale_factors, -1, C_,
                        head.bbox_coder.means, head.bbox_coder.stds, rescale=rescale, normalize=False)
         B = cand.boxes.shape[0]
         image_ids = kwargs.get('image_ids')
         if image_ids is None:
             image_ids = torch.arange(B, device=cand.boxes.device, dtype=torch.int64) + int(kwargs.get('batchIdx', 0)) * B
-        cls_code, scale_code, _ = extract_agg_codes(kwargs['uPool2'] if 'object' in kwargs['uPool2'] else 'objectSum_' + kwargs['uPool2'])
-        unc = hua_score(cand, None, None, image_ids.to(torch.int64).contiguous(), 1, (cls_code, scale_code, 0), False,
-                        seed=kwargs.get('hua_seed', 20), scale_mode=True, estimator=kwargs.get('hua_estimator') or 'mc')
+        if uPool == 'Entropy_Avg':
+            unc = hua_score(cand, None, None, image_ids.to(torch.int64).contiguous(), 1, (0, 0, 0), False, num_samples=50,
+                            seed=kwargs.get('hua_seed', 20), scale_mode='avg', estimator=kwargs.get('hua_estimator') or 'mc', lam_mode=lam_mode)
+        else:
+            cls_code, scale_code, _ = extract_agg_codes(kwargs['uPool2'] if 'object' in kwargs['uPool2'] else 'objectSum_' + kwargs['uPool2'])
+            unc = hua_score(cand, None, None, image_ids.to(torch.int64).contiguous(), 1, (cls_code, scale_code, 0), False,
+                            seed=kwargs.get('hua_seed', 20), scale_mode=True, estimator=kwargs.get('hua_estimator') or 'mc', lam_mode=lam_mode)
         det_results = [(cand.boxes[b], cand.scores[b]) for b in range(B)]
         if kwargs.get('_return_internals'):
             return det_results, unc, dict(cand=cand)
@@ -315,7 +358,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                     for c, a in zip(mlvl_cls_scores, na)]
     nms_pre = cfg.get('nms_pre', -1)
     cand = pre_nms(mlvl_cls_scores, mlvl_bbox_preds, L_scores, mlvl_anchors, img_shapes, scale_factors, nms_pre, C_,
-                   head.bbox_coder.means, head.bbox_coder.stds, rescale=rescale, has_bg=has_bg)
+                   head.bbox_coder.means, head.bbox_coder.stds, rescale=rescale, has_bg=has_bg, fg_thr=obj_thr)
     if not with_nms:
         return [(cand.boxes[b], cand.scores[b]) for b in range(cand.boxes.shape[0])]
     max_num = cfg.max_per_img
@@ -339,12 +382,14 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
             raise ValueError('detUnc needs the lambda head outputs (L_scores)')
         agg = extract_agg_codes(kwargs.get('uPool2') or 'objectSum_scaleMax_classSum')
         _, obj_out, _ = hua_score(cand, dets, num, image_ids.to(torch.int64).contiguous(), max_num, agg, False, seed=kwargs.get('hua_seed', 20),
-                                  dirichlet_cols=C_ if has_bg else 0, estimator=estimator, want_objects=True)
+                                  dirichlet_cols=C_ if has_bg else 0, estimator=estimator, want_objects=True, obj_score_thr=obj_thr,
+                                  obj_iou_thr=iou_thr, fg_thr=obj_thr, lam_mode=lam_mode)
         nh = num.cpu().tolist()
         return [(dets[b, :nh[b]], labels[b, :nh[b]], obj_out[b, :nh[b]]) for b in range(B)]
     agg = extract_agg_codes(kwargs['uPool2'])
     unc = hua_score(cand, dets, num, image_ids.to(torch.int64).contiguous(), max_num, agg, kwargs.get('clsW', False),
-                    seed=kwargs.get('hua_seed', 20), dirichlet_cols=C_ if has_bg else 0, estimator=estimator)
+                    seed=kwargs.get('hua_seed', 20), dirichlet_cols=C_ if has_bg else 0, estimator=estimator, obj_score_thr=obj_thr,
+                    obj_iou_thr=iou_thr, fg_thr=obj_thr, lam_mode=lam_mode)
     det_results = [(dets[b], labels[b]) for b in range(B)]   # zero-padded to max_per_img rows (num_det rows are valid)
     if kwargs.get('_return_internals'):
         return det_results, unc, dict(cand=cand, dets=dets, labels=labels, keep=keep, num=num)

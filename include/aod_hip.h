@@ -373,6 +373,19 @@ int aod_meh_loss_levels_fwd(const float* lam, const float* loss_noR, const float
                             float* out_sums, float* partials, aod_stream_t stream);
 int aod_meh_loss_levels_bwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
                             const float* g, void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream);
+/* The four MEH passes with the loss FORM of the reference's ablation heads; the entries above are form = 0.  Per row, d = the form's
+ * difference, w = bbox_w4[i*4], in fp32; same partial sums, same reduction order and the same gradient layout as above.
+ *   form 0  L2    (Lambda_L2.py:235-241)    d = lam+1e-9 - loss                   term (|d|*w)^2   grad g*2*w^2*d
+ *   form 1  L1    (Lambda_L1.py:236-241)    d = lam+1e-9 - loss                   term ||d|*w|     grad g*|w|*sign(d), 0 where d == 0
+ *   form 2  MSLE  (Lambda_MSLE.py:236-242)  d = log(lam+1e-9+1) - log(loss+1)     term (|d|*w)^2   grad g*2*(|d|*w)*w*sign(d)/(lam+1e-9+1) */
+int aod_meh_loss_fwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, int form,
+                        float* out_sum, float* partials, aod_stream_t stream);
+int aod_meh_loss_bwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int64_t n, int form,
+                        const float* g, void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream);
+int aod_meh_loss_levels_fwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
+                               int form, float* out_sums, float* partials, aod_stream_t stream);
+int aod_meh_loss_levels_bwd_ex(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
+                               int form, const float* g, void* grad_lam, int out_bf16, int A, int pitch, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ geometry (K9, K10)
  * replaces: AnchorGenerator.grid_anchors/valid_flags (core/anchor/anchor_generator.py:308-438),
@@ -474,6 +487,21 @@ int aod_hua_score_ex(const float* boxes, const float* scores, const float* lam, 
                      float fg_thr, int num_samples, uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode,
                      int dirichlet_cols, float* unc, float* pair_out, int max_pairs, int32_t* pair_count, int estimator,
                      float* obj_out, int32_t* obj_pairs, void* ws, aod_stream_t stream);
+/* aod_hua_score_ex for the reference's ablation heads; aod_hua_score_ex is aod_hua_score_ex2(..., lam_mode = 0) with scale_mode 0 / 1.
+ * lam_mode: 0 = alpha = score * mean(lambda) / (lambda + 1e-7) * 25 (Lambda_L2.py:513-516, 551-554);
+ *           1 = alpha = score: Lambda_L2Net_NoL's ComputeObjUnc / ComputeScaleUnc (Lambda_L2_noL.py:526-532, 586-592), lam is not read.
+ * scale_mode = 2: Entropy_Avg, ComputeAvgUnc + AggregateAvgUnc (Lambda_L2_noL.py:552-572, 631-640): the pairs of scale_mode = 1 (every
+ *   candidate whose max score exceeds fg_thr, pseudo object 0, same Philox keying), no class bins: unc[b] = mean over the levels that own a
+ *   pair of (mean of the level's per-pair epistemic values), 0 when no level owns one (the reference yields NaN there, and drops a level
+ *   whose mean is exactly 0.0: neither is reproduced).  Fixed summation order, no atomics: an image's score does not depend on its batch.
+ *   With num_samples = 50, lam_mode = 1, estimator = 0 this is the reference's pool; estimator = 1 is its n -> infinity limit, NOT its
+ *   50-sample expectation (the `total` term, the entropy of the mean of n samples, is biased downwards at finite n).  agg3_host and clsW are not read. */
+int aod_hua_score_ex2(const float* boxes, const float* scores, const float* lam, const int32_t* cand_anchor,
+                      const float* dets, const int32_t* num_det, const int32_t* level_start_host, const int32_t* level_any_fg,
+                      const int64_t* image_ids, int B, int n, int L, int C, int max_num, float obj_score_thr, float obj_iou_thr,
+                      float fg_thr, int num_samples, uint64_t seed, const int32_t* agg3_host, int clsW, int scale_mode,
+                      int dirichlet_cols, float* unc, float* pair_out, int max_pairs, int32_t* pair_count, int estimator, int lam_mode,
+                      float* obj_out, int32_t* obj_pairs, void* ws, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ SSD300-VGG16 variant (BASELINE config 0)
  * generic NHWC bf16 max-pool fwd/bwd (mmcv VGG pools, ceil_mode, + the 3x3 s1 p1 pool5 of backbones/ssd_vgg.py:66-68) */

@@ -46,7 +46,15 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--work-dir', default='WORK_DIR')
     p.add_argument('--resume-from')
     p.add_argument('--load-from')
-    p.add_argument('--bbox-head')
+    p.add_argument('--bbox-head', help='head type written into cfg.model.bbox_head.type: Lambda_L2Net (default) or one of the ablation heads '
+                                       'Lambda_L1Net | Lambda_MSLENet | Lambda_L2Net_ablation | Lambda_L2Net_NoL')
+    p.add_argument('--uncertainty-pool', default=None,
+                   help="pool scoring rule (default: the config's uncertainty_pool): Random | Entropy_NMS | Entropy_ALL | Entropy_Avg "
+                        '(Entropy_Avg: Lambda_L2Net_NoL only)')
+    p.add_argument('--hua-score-thr', type=float, default=score_thr,
+                   help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
+    p.add_argument('--hua-iou-thr', type=float, default=iou_thr,
+                   help='iou_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
     p.add_argument('--uncertainty', help='uncertainty type (accepted like the reference accepts it, tools/train_RetinaNet.py:56: never read there either)')
     p.add_argument('--no-validate', default=False, help='whether not to evaluate during training')
     group_gpus = p.add_mutually_exclusive_group()
@@ -65,6 +73,7 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--synthetic-size', type=int, default=default_size)
     p.add_argument('--cycles', type=int, default=None, help='override the number of AL cycles')
     p.add_argument('--samples-per-gpu', type=int, default=None)
+    p.add_argument('--log-interval', type=int, default=None, help='iterations between two lines of the text log (config key log_config.interval)')
     p.add_argument('--hua-estimator', choices=['mc', 'closed'], default=None,
                    help='HUA estimator of the pool scoring pass: Monte-Carlo (default) or the closed form of its limit (config key model.test_cfg.hua_estimator)')
     p.add_argument('--device-transforms', action='store_true',
@@ -116,6 +125,9 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
     str2unc = {'SACA': 'scaleAvg_classAvg', 'SSCS': 'scaleSum_classSum', 'SACS': 'scaleAvg_classSum', 'SSCA': 'scaleSum_classAvg'}
     if args.Unc_type:
         cfg.uncertainty_pool2 = str2unc[args.Unc_type]
+    if args.uncertainty_pool:
+        cfg.uncertainty_pool = args.uncertainty_pool
+        cfg.model.test_cfg.uncertainty_pool = args.uncertainty_pool
     base_dir = osp.dirname(osp.dirname(osp.abspath(__file__)))
     cfg.work_dir = osp.join(base_dir, 'work_dirs', args.work_dir)
     mkdir_or_exist(cfg.work_dir)
@@ -154,6 +166,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
         cfg.cycles = list(range(args.cycles))
     if args.samples_per_gpu:
         cfg.data.samples_per_gpu = args.samples_per_gpu
+    if args.log_interval:
+        cfg.log_config.interval = args.log_interval
     if args.device_transforms:
         cfg.data.device_transforms = True
     if args.hua_estimator:
@@ -232,7 +246,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             poolModel = MMDataParallel(model, device_ids=cfg.gpu_ids)
             with torch.no_grad():
                 uncertainty = calculate_uncertainty(cfg, poolModel, data_loader, return_box=False, showNMS=False, saveUnc=False,
-                                                    saveMaxConf=saveMaxConf, clsW=clsW, scaleUnc=False, score_thr=score_thr, iou_thr=iou_thr)
+                                                    saveMaxConf=saveMaxConf, clsW=clsW, scaleUnc=False, score_thr=args.hua_score_thr,
+                                                    iou_thr=args.hua_iou_thr)
             maxconf = None
             if saveMaxConf:                                                   # :236-240
                 uncertainty, maxconf = uncertainty
