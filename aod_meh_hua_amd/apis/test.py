@@ -6,6 +6,10 @@ Re-design for 8 x MI355X: the pool is SHARDED -- each rank scores th
 (the reference's loader is dist=False, so every rank would score the whole pool).  Scores stay on the device
 inside the loop; the host syncs once per pool.  The Philox stream is keyed by the global image index, so the
 result is bit-identical for any world size."""
+import os
+import time
+import weakref as _weakref
+
 import numpy as np
 import torch
 
@@ -46,7 +50,6 @@ class Uncertainty_fns:
 
 # captured scoring graphs, per model (weak keys; a GraphedScore holds its model weakly too, so a dead model frees its graph memory pool by
 # reference counting -- and nothing unpicklable hangs in the module's __dict__: copy.deepcopy(model) keeps working after a pool was scored)
-import weakref as _weakref
 _GSCORE = _weakref.WeakKeyDictionary()
 
 
@@ -60,6 +63,11 @@ def calculate_uncertainty(cfg, *args, **kwargs):
 
 def _unwrap(x):
     return x.data if isinstance(x, DataContainer) else x
+
+
+def _inputs(batch):
+    """the forward's inputs of a collated batch"""
+    return {k: _unwrap(v) for k, v in batch.items() if k in ('img', 'img_metas')}
 
 
 def _shard_batches(dataset, batches, collate, workers):
@@ -90,76 +98,133 @@ def _pin(x):
     return x
 
 
+def _single(data):
+    """one image tensor (or DeviceImageBatch) for the whole batch: the only form a GraphedScore takes"""
+    return isinstance(data['img'], (list, tuple)) and len(data['img']) == 1
+
+
+class _PoolPass:
+    """One pool-sized pass over data_loader.dataset: the plumbing under single_gpu_uncertainty, single_gpu_ensemble, single_gpu_mcdropout
+    and single_gpu_map.  It owns this rank's batches (the ONE parallel.shard_batches call), their GLOBAL image ids as one device tensor
+    sliced per batch without a host sync (they key the Philox streams of the HUA sampler and of the dropout masks), the loader (prefetch
+    workers into pinned memory, or the dataset's own device_batch), the progress bar, and the gather of the per-image scores.  A driver
+    adds its graph (_graphed), its forward (_replay_or_eager) and what it does with the outputs.
+    device_batch=False: a dataset's device_batch is not used (single_gpu_map takes the host loader always)."""
+
+    def __init__(self, data_loader, dev, interleaved=False, device_batch=True):
+        self.dataset, self.dev, self.interleaved = data_loader.dataset, dev, interleaved
+        self.N = len(self.dataset)
+        self.rank, self.world = get_dist_info()
+        self.bs = data_loader.batch_size or 1
+        self.my_batches = shard_batches(self.N, self.bs, self.rank, self.world, interleaved)
+        self.my_idx = [i for b in self.my_batches for i in b]
+        self.all_ids = torch.tensor(self.my_idx, dtype=torch.int64).to(dev)
+        # images produced on the device (datasets.DevicePhiloxPool): no host collate / H2D
+        self.device_side = device_batch and hasattr(self.dataset, 'device_batch')
+        workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
+        self._stream = (((idxs, None) for idxs in self.my_batches) if self.device_side
+                        else _shard_batches(self.dataset, self.my_batches, data_loader.collate_fn, workers))
+        self.prog_bar = ProgressBar(len(self.my_idx))
+
+    def batches(self, to_device=False, static_image=None):
+        """yields (idxs, image_ids, data): data holds `img` / `img_metas` only, unwrapped, the images pinned when the device is a GPU.
+        to_device: a single-image-list batch goes to the device ONCE here (one H2D copy / one transform launch) for drivers that run
+        several forwards on it; single_gpu_uncertainty leaves that copy to GraphedScore._fill_img (from pinned memory, on its conv stream).
+        static_image (GraphedScore.static_image): the device-generated pool writes its batch straight into the buffer the next replay reads."""
+        dataset, dev, pos = self.dataset, self.dev, 0
+        for idxs, data in self._stream:
+            image_ids = self.all_ids[pos:pos + len(idxs)]
+            pos += len(idxs)
+            if self.device_side:
+                out = static_image((len(idxs), 3) + tuple(dataset.size)) if static_image is not None and hasattr(dataset, 'size') else None
+                data = dataset.device_batch(idxs, dev, image_ids=image_ids, out=out)
+            else:
+                data = _inputs(data)
+                if dev.type == 'cuda':
+                    data['img'] = _pin(data['img'])
+            if to_device and dev.type == 'cuda' and _single(data):
+                img = data['img'][0]
+                img = img.to_device(dev) if isinstance(img, DeviceImageBatch) else img.to(dev, non_blocking=True)
+                data['img'] = [img]
+            yield idxs, image_ids, data
+            self.prog_bar.update(len(idxs))
+
+    def cat(self, chunks):
+        return torch.cat(chunks) if chunks else torch.zeros(0, device=self.dev)
+
+    def gather(self, local):
+        """this rank's scores (in my_idx order) -> the full [N] vector on every rank"""
+        if not self.interleaved:
+            return gather_scores(local, self.N)
+        per = -(-(-(-self.N // self.bs)) // self.world) * self.bs       # slots per rank of the interleaved partition: ceil(ceil(N / bs) / world) batches of bs
+        return gather_scores_indexed(local, self.my_idx, self.N, per=per)
+
+
+def _option_key(kwargs):
+    """the part of a graph's cache key that names the forward's options, whatever order they were passed in; None when a value is not a
+    hashable primitive (no caching, no graph: str() of a tensor / object could collide)"""
+    if not all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values()):
+        return None
+    return tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items()))
+
+
+def _graphed(model, dev, prefix, kwargs, cache=None, **ctor):
+    """The GraphedScore(model, rescale=True, **ctor, **kwargs) cached under prefix + _option_key(kwargs), built on first use; None (the
+    caller runs eagerly) when AOD_HIP_GRAPH=0, off the GPU, or for options that cannot be keyed.  cache: default _GSCORE[model] -- one
+    captured graph per (model, options): a pool is scored once per AL cycle with a freshly built model, but callers that score several
+    pools with one model (bench, tests) must not pay the capture again."""
+    opts = _option_key(kwargs)
+    if opts is None or dev.type != 'cuda' or os.environ.get('AOD_HIP_GRAPH', '1') == '0':
+        return None
+    if cache is None:
+        cache = _GSCORE.setdefault(model, {})
+    g = cache.get(prefix + opts)
+    if g is None:
+        from ..graphs import GraphedScore
+        g = cache[prefix + opts] = GraphedScore(model, rescale=True, **ctor, **kwargs)
+    return g
+
+
+def _replay_or_eager(gscore, data, image_ids, eager, **maybe_kw):
+    """the captured forward's outputs while single-image-list batches keep one shape (GraphedScore.maybe), else eager()'s"""
+    if gscore is not None and _single(data):
+        out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids, **maybe_kw)
+        if out is not None:
+            return out
+    return eager()
+
+
 def single_gpu_uncertainty(model, data_loader, **kwargs):
     """test.py:90-135, sharded.  Returns a [N] fp32 tensor (N = len(dataset)) identical on every rank."""
     model.eval()
-    dataset = data_loader.dataset
-    N = len(dataset)
-    rank, world = get_dist_info()
-    bs = data_loader.batch_size or 1
+    dev = next(model.parameters()).device
     # partition of the pool over the ranks (parallel.shard_batches): AOD_POOL_SHARD = contiguous | interleaved | auto (default: contiguous
     # until a pass measured more than 5 % imbalance between the ranks' loop times -- then every later pass of this process strides the batches)
-    import os
     shard_mode = os.environ.get('AOD_POOL_SHARD', 'auto')
     interleaved = shard_mode == 'interleaved' or (shard_mode == 'auto' and _SHARD_STATE['interleaved'])
-    my_batches = shard_batches(N, bs, rank, world, interleaved)
-    collate = data_loader.collate_fn
-    prog_bar = ProgressBar(sum(len(b) for b in my_batches))
+    pool = _PoolPass(data_loader, dev, interleaved)
+    bs, world = pool.bs, pool.world
     chunks, conf_chunks = [], []
     kwargs.setdefault('scaleUnc', False)
     # HIP-graph replay of the scoring batch (graphs.GraphedScore) while batches keep one shape; side-effect options stay eager
     plain = not any(kwargs.get(k) for k in ('showNMS', 'saveUnc', 'saveMaxConf', 'scaleUnc', 'draw'))
-    others = []
-    gscore = None
-    if plain and os.environ.get('AOD_HIP_GRAPH', '1') != '0' and next(model.parameters()).is_cuda:
-        from ..graphs import GraphedScore
-        # one captured graph per (model, options): a pool is scored once per AL cycle with a freshly built model, but callers that score
-        # several pools with one model (bench, tests) must not pay the capture again
-        # (the key holds hashable primitives only; any other option value -> no caching, no graph: str() of a tensor / object could collide)
-        if all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values()):
-            cache = _GSCORE.setdefault(model, {})
-            key = tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items()))
-            gscore = cache.get(key)
-            if gscore is None:
-                gscore = cache[key] = GraphedScore(model, rescale=True, isEval=False, batchIdx=0, **kwargs)
-    dev = next(model.parameters()).device
-    device_side = hasattr(dataset, 'device_batch')       # images produced on the device (datasets.DevicePhiloxPool): no host collate / H2D
-    my_idx = [i for b in my_batches for i in b]
-    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)             # GLOBAL image ids: they key the Philox streams of the HUA sampler
-    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
-    batches = ((idxs, None) for idxs in my_batches) if device_side else _shard_batches(dataset, my_batches, collate, workers)
+    gscore = _graphed(model, dev, (), kwargs, isEval=False, batchIdx=0) if plain else None
     timed = world > 1 and dev.type == 'cuda' and torch.distributed.is_available() and torch.distributed.is_initialized()
     if timed:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    pos = 0
-    for idxs, data in batches:
-        s = idxs[0]
-        image_ids = all_ids[pos:pos + len(idxs)]
-        pos += len(idxs)
-        if device_side:
-            out = gscore.static_image((len(idxs), 3) + tuple(dataset.size)) if gscore is not None and hasattr(dataset, 'size') else None
-            data = dataset.device_batch(idxs, dev, image_ids=image_ids, out=out)
-        else:
-            data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
-            if dev.type == 'cuda':
-                data['img'] = _pin(data['img'])
-        out = None
-        if gscore is not None and isinstance(data['img'], (list, tuple)) and len(data['img']) == 1:
-            out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids, defer=True)       # (scores are read after gscore.sync() below)
-        if out is not None:
-            result, unc = out
-        else:
+    for idxs, image_ids, data in pool.batches(static_image=gscore.static_image if gscore is not None else None):
+        def eager():
             with torch.no_grad():
-                result, unc, *others = model(return_loss=False, rescale=True, isEval=False, batchIdx=s // bs, image_ids=image_ids, **data, **kwargs)
+                return model(return_loss=False, rescale=True, isEval=False, batchIdx=idxs[0] // bs, image_ids=image_ids, **data, **kwargs)
+        # (replayed scores are read after gscore.sync() below)
+        result, unc, *others = _replay_or_eager(gscore, data, image_ids, eager, defer=True)
         chunks.append(torch.as_tensor(unc, dtype=torch.float32, device=dev).reshape(-1))
         if kwargs.get('saveMaxConf'):          # test.py:130,134
             conf_chunks.append(torch.as_tensor(others[0], dtype=torch.float32, device=dev).reshape(-1))
-        prog_bar.update(len(idxs))
-    dev = next(model.parameters()).device
     if gscore is not None:
         gscore.sync()                       # deferred selection halves (second stream) -> this stream
-    local = torch.cat(chunks) if chunks else torch.zeros(0, device=dev)
+    local = pool.cat(chunks)
     if timed:           # load balance of this pass: every rank learns every rank's loop time and takes the same decision for the next pass
         import torch.distributed as dist
         ev1.record()
@@ -174,17 +239,14 @@ def single_gpu_uncertainty(model, data_loader, **kwargs):
         _SHARD_STATE['over'] = _SHARD_STATE['over'] + 1 if _SHARD_STATE['imbalance'] > 0.05 else 0
         if _SHARD_STATE['over'] >= 2:
             _SHARD_STATE['interleaved'] = True
-    per = -(-(-(-N // bs)) // world) * bs       # slots per rank of the interleaved partition: ceil(ceil(N / bs) / world) batches of bs
-    gather = (lambda v: gather_scores_indexed(v, my_idx, N, per=per)) if interleaved else (lambda v: gather_scores(v, N))
     if kwargs.get('saveMaxConf'):
-        conf = torch.cat(conf_chunks) if conf_chunks else torch.zeros(0, device=dev)
-        return gather(local), gather(conf)
-    return gather(local)
+        return pool.gather(local), pool.gather(pool.cat(conf_chunks))
+    return pool.gather(local)
 
 
 @torch.no_grad()
 def single_gpu_ensemble(models, data_loader, n_cls=None, **kwargs):
-    """Ensemble_MI (mmdet/apis/CalEnsembleUnc.py:137-162) for 2 <= K <= 32 built models, on single_gpu_uncertainty's loop: the pool is sharded
+    """Ensemble_MI (mmdet/apis/CalEnsembleUnc.py:137-162) for 2 <= K <= 32 built models, on _PoolPass's loop: the pool is sharded
     over the ranks, batches come from the prefetch workers through pinned memory, the scores stay on the device and are gathered once.
     Returns a [N] fp32 tensor identical on every rank.
 
@@ -192,69 +254,26 @@ def single_gpu_ensemble(models, data_loader, n_cls=None, **kwargs):
     (scoring.ensemble_mi).  While the batch shape repeats (and AOD_HIP_GRAPH != 0) each member replays its own captured forward and hands
     back its graph's static maps; the MI kernel runs eagerly behind the K replays on the caller's stream, so it has read them before the
     next batch's replays overwrite them.  n_cls: classes per anchor row, default the head's cls_out_channels."""
-    import os
     from ..scoring import ensemble_mi
     models = list(models)
     if not 2 <= len(models) <= 32:
         raise ValueError(f'single_gpu_ensemble: 2..32 ensemble members are supported, got {len(models)}')
     for m in models:
         m.eval()
-    dataset = data_loader.dataset
-    N = len(dataset)
-    rank, world = get_dist_info()
-    bs = data_loader.batch_size or 1
-    my_batches = shard_batches(N, bs, rank, world, False)
     dev = next(models[0].parameters()).device
+    pool = _PoolPass(data_loader, dev)
     if n_cls is None:
         n_cls = getattr(models[0], 'module', models[0]).bbox_head.cls_out_channels
-    gscores = None
-    if (os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda'
-            and all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values())):
-        from ..graphs import GraphedScore
-        gscores = []
-        for k, m in enumerate(models):
-            # one graph per MEMBER: a model listed twice gets two (each owns the static maps it hands back)
-            key = ('just_out', sum(1 for o in models[:k] if o is m)) + tuple(sorted((n, type(v).__name__, v) for n, v in kwargs.items()))
-            cache = _GSCORE.setdefault(m, {})
-            g = cache.get(key)
-            if g is None:
-                g = cache[key] = GraphedScore(m, rescale=True, isEval=True, justOut=True, **kwargs)
-            gscores.append(g)
-    device_side = hasattr(dataset, 'device_batch')
-    my_idx = [i for b in my_batches for i in b]
-    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
-    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
-    batches = ((idxs, None) for idxs in my_batches) if device_side else _shard_batches(dataset, my_batches, data_loader.collate_fn, workers)
-    prog_bar = ProgressBar(len(my_idx))
+    # one graph per MEMBER: a model listed twice gets two (each owns the static maps it hands back)
+    gscores = [_graphed(m, dev, ('just_out', sum(1 for o in models[:k] if o is m)), kwargs, isEval=True, justOut=True)
+               for k, m in enumerate(models)]
     chunks = []
-    pos = 0
-    for idxs, data in batches:
-        image_ids = all_ids[pos:pos + len(idxs)]
-        pos += len(idxs)
-        if device_side:
-            data = dataset.device_batch(idxs, dev, image_ids=image_ids)
-        else:
-            data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
-            if dev.type == 'cuda':
-                data['img'] = _pin(data['img'])
-        single = isinstance(data['img'], (list, tuple)) and len(data['img']) == 1
-        if single and dev.type == 'cuda':
-            # the batch goes to the device ONCE (one H2D copy / one transform launch); every member reads that tensor
-            img = data['img'][0]
-            img = img.to_device(dev) if isinstance(img, DeviceImageBatch) else img.to(dev, non_blocking=True)
-            data['img'] = [img]
-        members = []
-        for k, m in enumerate(models):
-            out = None
-            if gscores is not None and single:
-                out = gscores[k].maybe(data['img'][0], data['img_metas'][0], image_ids)
-            if out is None:
-                out = m(return_loss=False, rescale=True, isEval=True, justOut=True, **data, **kwargs)
-            members.append(out)
+    for idxs, image_ids, data in pool.batches(to_device=True):          # every member reads the one device tensor
+        members = [_replay_or_eager(g, data, image_ids,
+                                    lambda: m(return_loss=False, rescale=True, isEval=True, justOut=True, **data, **kwargs))
+                   for g, m in zip(gscores, models)]
         chunks.append(ensemble_mi(members, n_cls))
-        prog_bar.update(len(idxs))
-    local = torch.cat(chunks) if chunks else torch.zeros(0, device=dev)
-    return gather_scores(local, N)
+    return pool.gather(pool.cat(chunks))
 
 
 def Ensemble_uncertainty(cfg, *models, data_loader=None, **kwargs):
@@ -306,7 +325,7 @@ def _mcd_stack(model, out, n):
 
 @torch.no_grad()
 def single_gpu_mcdropout(model, data_loader, n=25, rate=0.1, seed=0, n_cls=None, **kwargs):
-    """MCDropout_MI (mmdet/apis/CalMCDropoutUnc.py:137-163) on single_gpu_ensemble's loop: the pool is sharded over the ranks, batches come from
+    """MCDropout_MI (mmdet/apis/CalMCDropoutUnc.py:137-163) on _PoolPass's loop: the pool is sharded over the ranks, batches come from
     the prefetch workers through pinned memory (one H2D copy per batch), the scores stay on the device and are gathered once.  Returns a [N]
     fp32 tensor identical on every rank.
 
@@ -316,7 +335,6 @@ def single_gpu_mcdropout(model, data_loader, n=25, rate=0.1, seed=0, n_cls=None,
     scoring.ensemble_mi call over the n slots.  While the batch shape repeats (and AOD_HIP_GRAPH != 0) the n forwards are n replays of ONE
     captured forward, which reads the table the mask kernel has just rewritten.  An image's score is a function of (weights, image, seed,
     image id, n, rate) only: the same bits alone, in any batch, on any rank count, eager or replayed."""
-    import os
     from .. import functional as AF
     from .. import hipops as ho
     from ..scoring import ensemble_mi
@@ -330,62 +348,26 @@ def single_gpu_mcdropout(model, data_loader, n=25, rate=0.1, seed=0, n_cls=None,
     if n * L > 256:
         raise ValueError(f'single_gpu_mcdropout: n * levels = {n} * {L} exceeds the 256 map pointers of one ensemble_mi launch')
     model.eval()
-    dataset = data_loader.dataset
-    N = len(dataset)
-    rank, world = get_dist_info()
-    bs = data_loader.batch_size or 1
-    my_batches = shard_batches(N, bs, rank, world, False)
     dev = next(model.parameters()).device
+    pool = _PoolPass(data_loader, dev)
     if n_cls is None:
         n_cls = getattr(model, 'module', model).bbox_head.cls_out_channels
-    # the static factor table [bs, T] and the captured forward that reads it: one pair per (model, batch size, options)
-    primitives = all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values())
-    key = (bs,) + (tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items())) if primitives else ())
-    cache = _MCD_STATE.setdefault(model, {})
-    ent = cache.get(key) if primitives else None
-    if ent is None:
-        ent = dict(table=torch.ones(bs, sites.T, dtype=torch.float32, device=dev), g=None)
-        if primitives:
-            cache[key] = ent
+    # the static factor table [bs, T] and the captured forward that reads it: one entry per (model, batch size, options)
+    opts = _option_key(kwargs)
+    ent = {} if opts is None else _MCD_STATE.setdefault(model, {}).setdefault((pool.bs,) + opts, {})      # (options that cannot be keyed: not kept)
+    if 'table' not in ent:
+        ent['table'] = torch.ones(pool.bs, sites.T, dtype=torch.float32, device=dev)
     table = ent['table']
     offsets = sites.offsets(dev)
-    gscore = None
-    if os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda' and primitives:
-        if ent['g'] is None:
-            from ..graphs import GraphedScore
-            ent['g'] = GraphedScore(model, rescale=True, isEval=True, justOut=True, mc_dropout=AF.MCDropoutState(table, sites), **kwargs)
-        gscore = ent['g']
-    device_side = hasattr(dataset, 'device_batch')
-    my_idx = [i for b in my_batches for i in b]
-    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
-    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
-    batches = ((idxs, None) for idxs in my_batches) if device_side else _shard_batches(dataset, my_batches, data_loader.collate_fn, workers)
-    prog_bar = ProgressBar(len(my_idx))
+    state = AF.MCDropoutState(table, sites)
+    gscore = _graphed(model, dev, ('graph',), kwargs, cache=ent, isEval=True, justOut=True, mc_dropout=state)
     chunks = []
-    pos = 0
-    for idxs, data in batches:
-        image_ids = all_ids[pos:pos + len(idxs)]
-        pos += len(idxs)
-        if device_side:
-            data = dataset.device_batch(idxs, dev, image_ids=image_ids)
-        else:
-            data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
-            if dev.type == 'cuda':
-                data['img'] = _pin(data['img'])
-        single = isinstance(data['img'], (list, tuple)) and len(data['img']) == 1
-        if single and dev.type == 'cuda':
-            # the batch goes to the device ONCE; the n forwards read that tensor
-            img = data['img'][0]
-            img = img.to_device(dev) if isinstance(img, DeviceImageBatch) else img.to(dev, non_blocking=True)
-            data['img'] = [img]
+    for idxs, image_ids, data in pool.batches(to_device=True):          # the n forwards read the one device tensor
         stack = None
         for k in range(n):
             ho.dropout2d_masks(table, image_ids, offsets, rate, seed, k)
-            out = None
-            if gscore is not None and single:
-                out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids)
-            if out is None:
-                out = model(return_loss=False, rescale=True, isEval=True, justOut=True, mc_dropout=AF.MCDropoutState(table, sites), **data, **kwargs)
+            out = _replay_or_eager(gscore, data, image_ids, lambda: model(return_loss=False, rescale=True, isEval=True, justOut=True,
+                                                                           mc_dropout=state, **data, **kwargs))
             if stack is None:
                 stack = _mcd_stack(model, out, n)
             flat, total, slots = stack
@@ -396,9 +378,7 @@ def single_gpu_mcdropout(model, data_loader, n=25, rate=0.1, seed=0, n_cls=None,
                 for d, t in zip(views, out):
                     d.copy_(t)
         chunks.append(ensemble_mi([views for _, views in stack[2]], n_cls))
-        prog_bar.update(len(idxs))
-    local = torch.cat(chunks) if chunks else torch.zeros(0, device=dev)
-    return gather_scores(local, N)
+    return pool.gather(pool.cat(chunks))
 
 
 def MCDropout_uncertainty(cfg, model, data_loader, **kwargs):
@@ -415,7 +395,7 @@ def single_gpu_test(model, data_loader, show=False, out_dir=None, show_score_thr
     model.eval()
     results, unc_results = [], []
     for data in data_loader:
-        data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
+        data = _inputs(data)
         kw = dict(kwargs)
         kw.setdefault('isUnc', False)              # EvalHook forwards the whole `evaluation` dict (interval popped): isUnc, metric, ...
         out = model(return_loss=False, rescale=True, isEval=True, **data, **kw)
@@ -445,13 +425,11 @@ def single_gpu_map(model, data_loader, iou_thr=0.5, dataset=None, show=False, ou
     D2H copy per evaluation.  Returns (mean_ap, eval_results) for a float `iou_thr`, a list of such pairs for a list of thresholds -- each
     bit-identical to eval_map(single_gpu_test(model, data_loader), annotations, iou_thr=thr, dataset=dataset).
 
-    The loop is single_gpu_uncertainty's: the test set is sharded over the ranks (shard_batches), batches come from the prefetch workers
+    The loop is _PoolPass's: the test set is sharded over the ranks (shard_batches), batches come from the prefetch workers
     through pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the detection pass replays one captured graph
     (single stream: isEval has no two-phase form); the match kernel runs eagerly behind the replay on the same stream, so it has read the
     graph's static outputs before the next replay overwrites them.  `annotations`: the dataset's, when the caller already holds them.
     `_timing` (a dict; tools/eval_throughput.py): the loop is followed by a device sync and its wall time lands in _timing['pass_s']."""
-    import os
-    import time
     t_start = time.perf_counter()
     from ..core.evaluation import print_map_summary
     from ..core.evaluation_device import DeviceMapAccumulator
@@ -471,36 +449,12 @@ def single_gpu_map(model, data_loader, iou_thr=0.5, dataset=None, show=False, ou
                                scale_ranges=scale_ranges, tpfp_fn=tpfp_fn)
     anns = annotations if annotations is not None else eval_annotations(ds)
     assert len(anns) == N
-    rank, world = get_dist_info()
-    bs = data_loader.batch_size or 1
-    my_batches = shard_batches(N, bs, rank, world, False)
-    gscore = None
-    if os.environ.get('AOD_HIP_GRAPH', '1') != '0' and dev.type == 'cuda' and all(isinstance(v, (bool, int, float, str, type(None))) for v in kwargs.values()):
-        from ..graphs import GraphedScore
-        cache = _GSCORE.setdefault(model, {})
-        key = ('eval_padded',) + tuple(sorted((k, type(v).__name__, v) for k, v in kwargs.items()))
-        gscore = cache.get(key)
-        if gscore is None:
-            gscore = cache[key] = GraphedScore(model, rescale=True, isEval=True, _padded=True, **kwargs)
-    my_idx = [i for b in my_batches for i in b]
-    all_ids = torch.tensor(my_idx, dtype=torch.int64).to(dev)
-    workers = int(os.environ.get('AOD_POOL_WORKERS', getattr(data_loader, 'num_workers', 0) or 0))
-    prog_bar = ProgressBar(len(my_idx))
-    pos = 0
-    for idxs, data in _shard_batches(ds, my_batches, data_loader.collate_fn, workers):
-        image_ids = all_ids[pos:pos + len(idxs)]
-        pos += len(idxs)
-        data = {k: _unwrap(v) for k, v in data.items() if k in ('img', 'img_metas')}
-        if dev.type == 'cuda':
-            data['img'] = _pin(data['img'])
-        out = None
-        if gscore is not None and isinstance(data['img'], (list, tuple)) and len(data['img']) == 1:
-            out = gscore.maybe(data['img'][0], data['img_metas'][0], image_ids)
-        if out is None:
-            out = model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **kwargs)
-        dets, labels, num = out
+    pool = _PoolPass(data_loader, dev, device_batch=False)
+    gscore = _graphed(model, dev, ('eval_padded',), kwargs, isEval=True, _padded=True)
+    for idxs, image_ids, data in pool.batches():
+        dets, labels, num = _replay_or_eager(gscore, data, image_ids,
+                                             lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **kwargs))
         acc.update(idxs, dets, labels, num, [anns[i] for i in idxs])
-        prog_bar.update(len(idxs))
     if _timing is not None:
         torch.cuda.synchronize()
         _timing['pass_s'] = time.perf_counter() - t_start
