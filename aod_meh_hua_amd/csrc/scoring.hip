@@ -16,6 +16,18 @@
 // the two maxima are taken over the C-1 foreground columns.
 // CT: compile-time bound of C.  The loops are fully unrolled and predicated (same order of operations) so that x[] / s[] stay in registers;
 // with run-time trip counts the arrays were demoted to scratch memory (784 B per lane).
+// Sums over the classes.  Up to 24 classes (CT = 24) a sum is one running sum in column order, fused with the loop that produces its
+// terms: the bits and the code these rows have always had.  With more (CT = MAXC), eighty additions in one chain lost up to 6 x the
+// float32 oracle's own error on an 80-class row maximum (tests/test_gpu_pre_nms_edges.py): that instantiation keeps eight
+// partial sums (column c into c & 7) and folds them as a tree, which stays within the oracle's error -- and its chain of dependent adds
+// is a tenth as long.
+template <int CT>
+__device__ __forceinline__ float wide_sum(const float* v, int C) {
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < CT; ++c) if (c < C) a[c & 7] += v[c];
+  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
 template <int CT>
 __device__ __forceinline__ void row_scores_bg(const float* __restrict__ x, int C, float* s, float& max_alpha, float& max_score) {
   float m = x[0];
@@ -23,7 +35,8 @@ __device__ __forceinline__ void row_scores_bg(const float* __restrict__ x, int C
   for (int c = 1; c < CT; ++c) if (c < C) m = fmaxf(m, x[c]);
   float sum = 0.f;
 #pragma unroll
-  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = expf(x[c] - m); sum += s[c]; }
+  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = expf(x[c] - m); if constexpr (CT <= 24) sum += s[c]; }
+  if constexpr (CT > 24) sum = wide_sum<CT>(s, C);
   max_alpha = 0.f;
 #pragma unroll
   for (int c = 0; c < CT; ++c) if (c < C) { s[c] = s[c] / sum; if (c < C - 1) max_alpha = fmaxf(max_alpha, s[c]); }
@@ -36,11 +49,13 @@ __device__ __forceinline__ void row_scores(const float* __restrict__ x, int C, f
   for (int c = 1; c < CT; ++c) if (c < C) m = fmaxf(m, x[c]);
   float sum = 0.f;
 #pragma unroll
-  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = expf(x[c] - m); sum += s[c]; }
+  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = expf(x[c] - m); if constexpr (CT <= 24) sum += s[c]; }
+  if constexpr (CT > 24) sum = wide_sum<CT>(s, C);
   float S = 0.f;
   max_alpha = 0.f;
 #pragma unroll
-  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = s[c] / sum; S += s[c]; max_alpha = fmaxf(max_alpha, s[c]); }
+  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = s[c] / sum; if constexpr (CT <= 24) S += s[c]; max_alpha = fmaxf(max_alpha, s[c]); }
+  if constexpr (CT > 24) S = wide_sum<CT>(s, C);
   const float den = (S + 1e-20f) + 1e-9f;
   max_score = 0.f;
 #pragma unroll
@@ -305,7 +320,8 @@ __device__ __forceinline__ void gather_one(const GatherArgs& p, int b, int j, lo
     for (int c = 1; c < CT; ++c) if (c < p.C) m = fmaxf(m, x[c]);
     float sum = 0.f;
 #pragma unroll
-    for (int c = 0; c < CT; ++c) if (c < p.C) { s[c] = expf(x[c] - m); sum += s[c]; }
+    for (int c = 0; c < CT; ++c) if (c < p.C) { s[c] = expf(x[c] - m); if constexpr (CT <= 24) sum += s[c]; }
+    if constexpr (CT > 24) sum = wide_sum<CT>(s, p.C);
 #pragma unroll
     for (int c = 0; c < CT; ++c) if (c < p.C) s[c] = s[c] / sum;
   }
