@@ -154,6 +154,10 @@ _SIGS = {
     'aod_dropout2d_masks': (C.c_int, [P, P, I32, P, I32, I32, F32, U64, C.c_uint32, P]),
     'aod_dropout2d_apply': (C.c_int, [P, P, I64, I32, I32, I32, I32, P]),
     'aod_dropout2d_apply_multi': (C.c_int, [P, P, I64, I32, I32, P, P, P, I32, I32, P]),
+    'aod_pool_descriptor': (C.c_int, [P, I32, P, P, I32, I32, I32, P, I64, P]),
+    'aod_kcenter_chunk': (C.c_int, []),
+    'aod_kcenter_ws_len': (SZ, [I64]),
+    'aod_kcenter_greedy': (C.c_int, [P, I64, I32, P, I64, I64, P, P, P, P, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -15,7 +15,7 @@ import torch
 
 from ..datasets import DeviceImageBatch
 from ..mmcv_lite import DataContainer, ProgressBar
-from ..parallel import gather_scores, gather_scores_indexed, get_dist_info, shard_batches, shard_range
+from ..parallel import gather_rows, gather_scores, gather_scores_indexed, get_dist_info, shard_batches, shard_range
 
 
 class Uncertainty_fns:
@@ -40,6 +40,15 @@ class Uncertainty_fns:
 
     Entropy_ALL = Entropy_NMS          # test.py:52-63: same loop; the head switches on cfg.uncertainty_pool (ComputeScaleUnc path)
     Entropy_Avg = Entropy_NMS          # CalMCDropoutUnc.py:65-76: same loop again (Lambda_L2Net_NoL: ComputeAvgUnc + AggregateAvgUnc)
+
+    @staticmethod
+    def Coreset(cfg, *args, **kwargs):
+        # diversity-based selection (Sener & Savarese, ICLR 2018): needs the labelled set as the initial centers.  The HUA options that
+        # calculate_uncertainty's callers pass for the Entropy_* pools (score_thr, clsW, ...) have no meaning for a descriptor pass
+        if kwargs.get('X_L') is None:
+            raise TypeError("Uncertainty_fns.Coreset needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
+        model, dataloader = args
+        return Coreset_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'))
 
     @staticmethod
     def Entropy_NoNMS(cfg, *args, **kwargs):
@@ -385,6 +394,53 @@ def MCDropout_uncertainty(cfg, model, data_loader, **kwargs):
     """mmdet/apis/CalMCDropoutUnc.py:86-88 with the reference's name and argument order.  kwargs: n (default 25 forwards), rate (0.1), seed,
     n_cls.  Returns the CPU score tensor update_X_L takes."""
     return single_gpu_mcdropout(model, data_loader, **kwargs).cpu()
+
+
+@torch.no_grad()
+def single_gpu_descriptors(model, data_loader, **kwargs):
+    """Core-set descriptors of the whole pool on _PoolPass's loop: the pool is sharded over the ranks, batches come from the prefetch
+    workers through pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the forward (isEval=True, justFeat=True:
+    backbone + neck, no head) replays one captured graph; the descriptor launch (scoring.pool_descriptor) runs eagerly behind the replay on
+    the same stream, so it has read the graph's static neck outputs before the next replay overwrites them, and writes its rows straight
+    into the preallocated [N, D] matrix.  parallel.gather_rows makes the matrix whole on every rank.  Returns the device [N, D] fp32
+    tensor, D = levels * channels of the neck (RetinaNet: 1280); a row's bits depend on its image alone -- not on the batch size, the rank
+    count, or eager / replayed execution."""
+    from ..scoring import pool_descriptor
+    module = getattr(model, 'module', model)
+    neck = getattr(module, 'neck', None)
+    if not (hasattr(neck, 'num_outs') and isinstance(getattr(neck, 'out_channels', None), int)):
+        raise NotImplementedError(f'single_gpu_descriptors: Core-set descriptors are built for the FPN pyramid of the RetinaNet detectors, not '
+                                  f'for {type(module).__name__} / {type(neck).__name__} (SSD: its source maps do not share a channel count)')
+    model.eval()
+    dev = next(model.parameters()).device
+    pool = _PoolPass(data_loader, dev)
+    Cc, D = int(neck.out_channels), int(neck.num_outs) * int(neck.out_channels)
+    desc = torch.zeros(pool.N, D, dtype=torch.float32, device=dev)
+    gscore = _graphed(model, dev, ('just_feat',), kwargs, isEval=True, justFeat=True)
+    for idxs, image_ids, data in pool.batches():
+        feats = _replay_or_eager(gscore, data, image_ids,
+                                 lambda: model(return_loss=False, rescale=True, isEval=True, justFeat=True, **data, **kwargs))
+        pool_descriptor(feats, out=desc[idxs[0]:idxs[0] + len(idxs)], channels=Cc)          # (a batch is a run of consecutive images)
+    owned = torch.zeros(pool.N, dtype=torch.bool, device=dev)
+    owned[pool.all_ids] = True
+    return gather_rows(desc, owned)[0]
+
+
+def Coreset_uncertainty(cfg, model, data_loader, X_L=None, budget=None, **kwargs):
+    """Core-set acquisition (O. Sener, S. Savarese, "Active Learning for Convolutional Neural Networks: A Core-Set Approach", ICLR 2018;
+    the reference has none) in the form update_X_L takes: descriptors of the whole pool (single_gpu_descriptors), then k-center greedy
+    with the labelled images X_L as centers (scoring.kcenter_greedy; every rank runs it on the same matrix and gets the same picks).
+    budget: default cfg.X_S_size.  Returns a CPU [N] fp32 vector: the image picked at step t = 0 .. budget - 1 scores budget - t, every
+    other image 0 -- with a falsy zeroRate update_X_L's arg[-X_S_size:] selects exactly the picks."""
+    from ..scoring import kcenter_greedy
+    if X_L is None:
+        raise TypeError('Coreset_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are the initial centers')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    desc = single_gpu_descriptors(model, data_loader, **kwargs)
+    picks, _ = kcenter_greedy(desc, X_L, budget)
+    scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
+    scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
+    return scores.cpu()
 
 
 @torch.no_grad()

@@ -516,9 +516,10 @@ class GraphedScore:
             self._fill_img(sl, img)
             self._fill_meta(sl, img_metas, image_ids)
             sl['g'].replay()
-            if self.kw.get('isEval') and (self.kw.get('_padded') or self.kw.get('justOut')):
+            if self.kw.get('isEval') and (self.kw.get('_padded') or self.kw.get('justOut') or self.kw.get('justFeat')):
                 # evaluation form (apis/test.py single_gpu_map): the slot's STATIC (dets, labels, num) -- the caller consumes them on this
-                # stream before its next call replays over them.  justOut (single_gpu_ensemble): the static per-level classification maps
+                # stream before its next call replays over them.  justOut (single_gpu_ensemble): the static per-level classification maps;
+                # justFeat (single_gpu_descriptors): the static neck outputs
                 return sl['out']
             unc = sl['out'][1]
             return sl['out'][0], (unc.clone() if torch.is_tensor(unc) else unc)

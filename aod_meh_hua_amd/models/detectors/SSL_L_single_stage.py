@@ -52,6 +52,9 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
             assert kwargs['isEval'] and kwargs.get('justOut'), 'MC-dropout forwards return classification maps only (isEval=True, justOut=True)'
             with AF.mc_dropout(mcd.table, mcd.sites):
                 return list(self.bbox_head.forward_cls_dropout(self.extract_feat(img)))
+        if kwargs['isEval'] and kwargs.get('justFeat'):
+            # Core-set descriptors (apis/test.py single_gpu_descriptors): the neck outputs as they lie in the pyramid buffer; no head is launched
+            return self._just_feat(img)
         feat = self.extract_feat(img)
         if kwargs['isEval'] and kwargs.get('justOut'):
             # MyRetinaSingleStage.py:46-49 (honoured with isEval only): the per-level classification maps [B, A*C, h, w] fp32 of an ensemble
@@ -73,6 +76,9 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
         bbox_results = [bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes) for det_bboxes, det_labels in results_list]
         return bbox_results, uncertainties
 
+    def _just_feat(self, img):
+        return tuple(self.extract_feat(img))
+
     def aug_test(self, imgs, img_metas, rescale=False):
         raise NotImplementedError('test-time augmentation is not on the MEH/HUA path')
 
@@ -88,3 +94,7 @@ class SSL_L_RetinaNet(SSL_L_SingleStageDetector):
 @DETECTORS.register_module()
 class SSD_L_SingleStageDetector(SSL_L_SingleStageDetector):
     """mmdet/models/detectors/SSD_L_single_stage.py:10-134 (same control flow as SSL_L_SingleStageDetector)."""
+
+    def _just_feat(self, img):
+        raise NotImplementedError('justFeat / Core-set descriptors are built for the FPN pyramid of the RetinaNet detectors, not for SSD '
+                                  '(its six source maps have different channel counts and do not lie in one row buffer)')

@@ -297,6 +297,105 @@ def ensemble_mi(members, n_cls, out=None):
     return out
 
 
+def pool_descriptor(feats, out=None, channels=None, x3=None):
+    """Core-set descriptor of every image of a batch (aod_pool_descriptor): the concatenation over pyramid levels of the global average of
+    the neck output, [B, D] fp32 with D = L * C (RetinaNet: 5 * 256 = 1280).
+
+    feats: 1..8 per-level maps [B, width, h_l, w_l], bf16 channels_last device tensors as the neck hands them out (views of the pyramid
+    buffer; nothing is copied): plain bf16 (width = C) or X-layout rows (width = 2 * ceil32(C); value = head + tail).  x3: the layout,
+    default the current precision mode; channels: C of an X-layout map whose width is padded (default width / 2).  C % 8 == 0.
+    out: a [B, D] fp32 device view with unit column stride (e.g. rows of the [N, D] pool matrix).  The bits of a row depend on its image
+    alone -- not on B or on its place in the batch.  No host sync."""
+    from . import hipops as ho
+    feats = list(feats)
+    L = len(feats)
+    if not 1 <= L <= 8:
+        raise ValueError(f'pool_descriptor: 1..8 levels are supported, got {L}')
+    x3 = bool(ho.X3 if x3 is None else x3)
+    for l, t in enumerate(feats):
+        if not torch.is_tensor(t) or t.dtype != torch.bfloat16 or t.dim() != 4:
+            raise ValueError(f'pool_descriptor: level {l} is not a bf16 [B, width, h, w] tensor')
+        if t.shape[0] != feats[0].shape[0] or t.shape[1] != feats[0].shape[1] or t.numel() == 0:
+            raise ValueError(f'pool_descriptor: level {l} has shape {tuple(t.shape)}, level 0 has {tuple(feats[0].shape)}: every level needs the '
+                             'same positive batch size and width')
+        if not t.permute(0, 2, 3, 1).is_contiguous():
+            raise ValueError(f'pool_descriptor: level {l} is not channels_last-dense; no copy is made here')
+    B, Wd = int(feats[0].shape[0]), int(feats[0].shape[1])
+    if x3 and Wd % 64:
+        raise ValueError(f'pool_descriptor: X-layout rows are a multiple of 64 columns wide, got {Wd}')
+    Cc = int(channels) if channels is not None else (Wd // 2 if x3 else Wd)
+    if Cc < 8 or Cc % 8 or (ho.xw(Cc) if x3 else Cc) != Wd:
+        raise ValueError(f'pool_descriptor: {Cc} channels (a positive multiple of 8) do not make rows of {Wd} columns')
+    D = L * Cc
+    for t in feats:
+        if not t.is_cuda:
+            raise _C.AodHipError('pool_descriptor needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    dev = feats[0].device
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, D) and out.stride(1) == 1
+              and out.stride(0) >= D):
+        raise ValueError(f'pool_descriptor: out must be an fp32 device tensor of shape ({B}, {D}) with unit column stride')
+    hw = [int(t.shape[2] * t.shape[3]) for t in feats]
+    rb = Wd * 2
+    base = min(t.data_ptr() for t in feats)
+    offs = [t.data_ptr() - base for t in feats]
+    if all(o % rb == 0 for o in offs):          # the levels are row ranges of one buffer (functional.pyramid_buffer): one launch
+        groups = [(base, list(range(L)), [o // rb for o in offs])]
+    else:
+        groups = [(t.data_ptr(), [l], [0]) for l, t in enumerate(feats)]
+    for p, ls, rows in groups:
+        n = len(ls)
+        call('aod_pool_descriptor', C.c_void_p(p), n, (C.c_int64 * n)(*rows), (C.c_int32 * n)(*[hw[l] for l in ls]), Cc, int(x3), B,
+             C.c_void_p(out.data_ptr() + 4 * ls[0] * Cc), out.stride(0), stream())
+    return out
+
+
+def kcenter_chunk():
+    """labelled centers one initialisation launch of kcenter_greedy stages in LDS"""
+    return int(_C.lib.aod_kcenter_chunk())
+
+
+def kcenter_greedy(desc, labelled, budget):
+    """k-center greedy selection (Sener & Savarese, ICLR 2018, Algorithm 1) on the aod_kcenter_greedy kernels: starting from the labelled
+    rows as centers, `budget` times pick the unselected row farthest (squared Euclidean distance, direct difference form, fp32) from its
+    nearest center -- the lowest index on a tie -- and make it a center.
+
+    desc: [N, D] fp32 contiguous device tensor (D <= 2048); labelled: distinct row indices in [0, N) (sequence, array or tensor; may be
+    empty: the first pick is then row 0 with radius inf); 1 <= budget <= number of unlabelled rows.
+    Returns (picks [budget] int64, radius [budget] fp32) on the device, radius[t] = the distance of pick t at the time it was picked
+    (non-increasing).  All steps are enqueued on the current stream; no host sync.  The result does not depend on the order of `labelled`."""
+    if not (torch.is_tensor(desc) and desc.dim() == 2 and desc.dtype == torch.float32 and desc.is_contiguous() and desc.numel() > 0):
+        raise ValueError('kcenter_greedy: desc must be a non-empty contiguous 2-D fp32 tensor')
+    N, D = int(desc.shape[0]), int(desc.shape[1])
+    if D > 2048:
+        raise ValueError(f'kcenter_greedy: up to 2048 descriptor columns are supported, got {D}')
+    lab = labelled.detach().cpu().numpy() if torch.is_tensor(labelled) else np.asarray(labelled)
+    lab = lab.reshape(-1)
+    if lab.size and not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f'kcenter_greedy: labelled must hold integer indices, got {lab.dtype}')
+    lab = lab.astype(np.int64)
+    if lab.size and (lab.min() < 0 or lab.max() >= N):
+        raise ValueError(f'kcenter_greedy: labelled index outside [0, {N})')
+    if np.unique(lab).size != lab.size:
+        raise ValueError('kcenter_greedy: labelled holds a duplicated index')
+    budget = int(budget)
+    if budget < 1:
+        raise ValueError(f'kcenter_greedy: budget must be at least 1, got {budget}')
+    if budget > N - lab.size:
+        raise ValueError(f'kcenter_greedy: budget {budget} exceeds the {N - lab.size} unselected rows')
+    if not desc.is_cuda:
+        raise _C.AodHipError('kcenter_greedy needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    dev = desc.device
+    lab_d = torch.from_numpy(lab).to(dev) if lab.size else None
+    picks = torch.empty(budget, dtype=torch.int64, device=dev)
+    radius = torch.empty(budget, dtype=torch.float32, device=dev)
+    mind = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_C.lib.aod_kcenter_ws_len(N)), dtype=torch.uint8, device=dev)
+    call('aod_kcenter_greedy', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
+    return picks, radius
+
+
 def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes, scale_factors, cfg, rescale=False, with_nms=True,
                 **kwargs):
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.

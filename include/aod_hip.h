@@ -604,6 +604,32 @@ int aod_dropout2d_apply(void* x, const float* table_row0, int64_t row_stride_T, 
 int aod_dropout2d_apply_multi(void* x, const float* table, int64_t row_stride_T, int B, int nseg, const int64_t* seg_row0,
                               const int32_t* seg_hw, const int32_t* seg_off, int C, int x3, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ Core-set acquisition: pooled pyramid descriptors and k-center greedy
+ * (csrc/coreset.hip).  No reference call site: O. Sener, S. Savarese, "Active Learning for Convolutional Neural Networks: A Core-Set
+ * Approach", ICLR 2018, Algorithm 1 (k-Center-Greedy); the semantics are fixed in DESIGN 3i.
+ *   aod_pool_descriptor: the descriptor of image b = concatenation over the nseg pyramid levels of the global average of the neck output:
+ *     out[b * out_stride + s * C + c] = mean over the seg_hw[s] rows of image b in segment s of channel c, fp32.  Segment s = rows
+ *     seg_row0[s] .. + B * seg_hw[s] of the row buffer `base` (1..8 segments, HOST arrays).  x3 = 0: bf16 rows of C columns; x3 = 1:
+ *     X-layout rows of 2 * ceil32(C) columns, value = head + tail formed in fp32, pad columns are never read.  C % 8 == 0.  fp32
+ *     accumulation, one division by seg_hw[s]; the order of a sum depends on seg_hw[s] only -- not on B, on the image's position in the
+ *     batch or on another segment: an image has the same descriptor bits alone and in any batch.  16-B loads, a fixed LDS tree, no atomics.
+ *   aod_kcenter_greedy: desc [N][D] fp32 (1 <= D <= 2048, 16-B aligned), labelled [n_labelled] int64 DEVICE indices (distinct, in [0, N):
+ *     the caller validates; an index outside the matrix is skipped, never dereferenced), 1 <= budget <= N - n_labelled.
+ *       d(i, c) = sum_k (x_ik - x_ck)^2 in the direct difference form, fp32; a function of the two rows and D alone
+ *       mind[i] = min over labelled c of d(i, c) (+inf for an empty labelled set); labelled rows are selected
+ *       step t  : picks[t] = the unselected row with the largest mind, the LOWEST index on a tie; radius[t] = that mind; the pick becomes
+ *                 selected; every mind[i] takes min(mind[i], d(i, pick)).  A selected row never wins, also when every mind is 0.
+ *     picks [budget] int64, radius [budget] fp32, mind [N] fp32 (on return: the distance to the nearest labelled or picked row), ws:
+ *     aod_kcenter_ws_len(N) bytes, 8-B aligned.  All budget steps are enqueued on `stream` (one launch per pick, which first reduces the
+ *     per-workgroup partials of the launch before it); no host sync, no cross-workgroup wait inside a launch, no atomics, no trip count
+ *     that depends on data.  NaN descriptors are the caller's error.  aod_kcenter_chunk(): labelled centers per initialisation launch. */
+int aod_pool_descriptor(const void* base, int nseg, const int64_t* seg_row0, const int32_t* seg_hw, int C, int x3, int B, float* out,
+                        int64_t out_stride, aod_stream_t stream);
+int aod_kcenter_chunk(void);
+size_t aod_kcenter_ws_len(int64_t N);
+int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
+                       float* radius, float* mind, void* ws, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

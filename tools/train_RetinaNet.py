@@ -49,8 +49,8 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--bbox-head', help='head type written into cfg.model.bbox_head.type: Lambda_L2Net (default) or one of the ablation heads '
                                        'Lambda_L1Net | Lambda_MSLENet | Lambda_L2Net_ablation | Lambda_L2Net_NoL')
     p.add_argument('--uncertainty-pool', default=None,
-                   help="pool scoring rule (default: the config's uncertainty_pool): Random | Entropy_NMS | Entropy_ALL | Entropy_Avg "
-                        '(Entropy_Avg: Lambda_L2Net_NoL only)')
+                   help="pool scoring rule (default: the config's uncertainty_pool): Random | Entropy_NMS | Entropy_ALL | Entropy_Avg | Coreset "
+                        '(Entropy_Avg: Lambda_L2Net_NoL only; Coreset: k-center greedy on pooled pyramid descriptors, zeroRate off)')
     p.add_argument('--hua-score-thr', type=float, default=score_thr,
                    help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
     p.add_argument('--hua-iou-thr', type=float, default=iou_thr,
@@ -244,16 +244,23 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             data_loader = build_dataloader(dataset_al, samples_per_gpu=cfg.data.samples_per_gpu, workers_per_gpu=cfg.data.workers_per_gpu,
                                            dist=False, shuffle=False)
             poolModel = MMDataParallel(model, device_ids=cfg.gpu_ids)
+            # Coreset alone takes the labelled set (its initial centers) and selects by rank, not by score: its vector marks exactly
+            # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
+            coreset = cfg.uncertainty_pool == 'Coreset'
+            pool_kw = dict(X_L=X_L) if coreset else {}
+            if coreset and zeroRate and cycle == cfg.cycles[0]:
+                logger.info(f'uncertainty_pool=Coreset: zeroRate {zeroRate} -> 0 (the picks are the selection)')
             with torch.no_grad():
                 uncertainty = calculate_uncertainty(cfg, poolModel, data_loader, return_box=False, showNMS=False, saveUnc=False,
                                                     saveMaxConf=saveMaxConf, clsW=clsW, scaleUnc=False, score_thr=args.hua_score_thr,
-                                                    iou_thr=args.hua_iou_thr)
+                                                    iou_thr=args.hua_iou_thr, **pool_kw)
             maxconf = None
-            if saveMaxConf:                                                   # :236-240
+            if saveMaxConf and not coreset:                                   # :236-240
                 uncertainty, maxconf = uncertainty
                 maxconf = maxconf.cpu().numpy() if torch.is_tensor(maxconf) else np.asarray(maxconf)
             uncertainty = uncertainty.cpu().numpy() if torch.is_tensor(uncertainty) else np.asarray(uncertainty)
-            X_L, X_U = update_X_L(uncertainty, X_all, X_L, cfg.X_S_size, zeroRate=zeroRate, maxconf=maxconf, useMaxConf=useMaxConf)
+            X_L, X_U = update_X_L(uncertainty, X_all, X_L, cfg.X_S_size, zeroRate=0 if coreset else zeroRate, maxconf=maxconf,
+                                  useMaxConf=useMaxConf)
             if rank == 0:
                 np.save(cfg.work_dir + f'/X_L_{cycle + 1}.npy', X_L), np.save(cfg.work_dir + f'/X_U_{cycle + 1}.npy', X_U)
                 np.save(cfg.work_dir + f'/Unc_{cycle + 1}.npy', uncertainty)
