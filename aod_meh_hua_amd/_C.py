@@ -64,13 +64,18 @@ _SIGS = {
     'aod_conv2d_ws': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P, SZ, P]),
     'aod_conv2d_plan': (C.c_int, [C.POINTER(ConvDesc), I32, C.c_uint, C.POINTER(ConvPlan)]),
     'aod_conv2d_grouped': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P]),
+    'aod_conv2d_ws_map': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P, SZ, P, P, P]),
+    'aod_conv2d_grouped_map': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P, P, P]),
     'aod_halo_conv3x3_applies': (C.c_int, [C.POINTER(ConvDesc)]),
     'aod_halo_conv3x3': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P]),
     'aod_conv2d_wgrad': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P]),
     'aod_conv2d_wgrad_splits': (C.c_int, [C.POINTER(ConvDesc)]),
     'aod_conv2d_wgrad_slabs': (C.c_int, [C.POINTER(ConvDesc), P, P, P, I32, I64, P, P]),
+    'aod_conv2d_wgrad_slabs_map': (C.c_int, [C.POINTER(ConvDesc), P, P, P, I32, I64, P, P, P]),
     'aod_conv2d_wgrad_group_plan': (C.c_int, [P, I32, P]),
     'aod_conv2d_wgrad_grouped': (C.c_int, [P, I32, P, P, P, P, P, P, P]),
+    'aod_conv2d_wgrad_plan': (C.c_int, [P, I32, P, P, P]),
+    'aod_conv2d_wgrad_grouped_map': (C.c_int, [P, I32, P, P, P, P, P, P, P, P]),
     'aod_unpack_wgrad_slabs_grouped': (C.c_int, [I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_unpack_wgrad_slabs': (C.c_int, [P, I32, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P]),
     'aod_conv_row_table_bytes': (SZ, [C.POINTER(ConvDesc)]),
@@ -141,6 +146,7 @@ _SIGS = {
     'aod_x3_upsample2x_add_bwd_set': (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, P]),
     'aod_x3_act_bwd': (C.c_int, [P, P, P, P, I64, I32, I32, P]),
     'aod_x3_pad_cast_colsum': (C.c_int, [P, P, P, P, I64, I32, P]),
+    'aod_x3_pad_cast_colsum_map': (C.c_int, [P, P, P, P, I64, I32, P, P]),
     'aod_x3_nchw_f32_to_nhwc': (C.c_int, [P, P, I32, I32, I32, I32, P]),
     'aod_x3_maxpool_fwd': (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
     'aod_x3_maxpool_bwd': (C.c_int, [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),

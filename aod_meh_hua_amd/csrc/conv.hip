@@ -14,7 +14,7 @@
 #include "pointwise.h"
 #include "conv_x3p.h"
 
-struct ConvGroup { const bf16_t* x; const bf16_t* w; void* y; const float* pre_shift; const bf16_t* mask; float* colsum; };
+struct ConvGroup { const bf16_t* x; const bf16_t* w; void* y; const float* pre_shift; const bf16_t* mask; float* colsum; const unsigned char* omap; };
 struct ConvKParams {
   const bf16_t* x;
   const bf16_t* w;
@@ -34,6 +34,10 @@ struct ConvKParams {
   int perm;           // dgrad of a stride-2 conv: GEMM rows run CLASS-MAJOR inside a segment (the four (y & 1, x & 1) classes of the
                       // destination pixels one after the other), so a tile is one class and the filter taps that can never hit it are skipped
   int ngroups;        // > 1: grouped launch (aod_conv2d_grouped): grp[] replaces x / w / y / pre_shift / mask / colsum
+  int interleave;     // grouped launch that carries a map: workgroup -> (tile, group) with the GROUP fastest (see the kernel)
+  const unsigned char* omap;   // X3 stride-1 dgrad, optional (sparse backward, conv_map_setup): ROW-ACTIVITY MAP of the DESTINATION -- byte b = 0: no
+                      // row of 64 b .. 64 b + 63 can receive anything but zeros (every dZ row the filter taps reach from there is zero); a tile whose
+                      // blocks are all 0 stores zero rows and leaves.  nullptr: every tile is computed.  Grouped launches: grp[].omap
   ConvGroup grp[4];
   int stagger;        // 8-wave forms: waves 4-7 run half a K-step behind waves 0-3 (see the K loop)
   int x3;             // reference-precision mode (aod_conv_desc_t.x3): operands in the X-layout, three MFMAs per 32 channels (see X3 below)
@@ -119,7 +123,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
     const int x = blockIdx.x & 7, j = blockIdx.x >> 3, q = j & 3, k = j >> 2, tq = nwg >> 2;
     wg = q * tq + x * (tq >> 3) + k;
   } else wg = blockIdx.x;
-  const int tile = wg % nwg, zz = wg / nwg;
+  // (grouped launches with a row-activity map: tiles dealt (tile, group)-interleaved.  xcd_swizzle hands every XCD a contiguous range of `wg`;
+  // group-major, the mapped member's mostly dead tiles would all fall to half of the XCDs, which then idle beside the dense member's half)
+  const bool il = GROUPED && p.interleave;
+  const int tile = il ? wg / p.ngroups : wg % nwg, zz = il ? wg % p.ngroups : wg / nwg;
   const int kz = GROUPED ? 0 : zz;           // kz: which slice of the K-steps (split-K launches)
   // grouped launch: `ngroups` convolutions of identical geometry (the cls / reg / evidence towers at one depth) share one grid, so
   // that their tiles fill whole rounds of the CUs together; group = which operand set this workgroup uses
@@ -135,6 +142,31 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
 #define g_colsum AOD_GSEL(colsum, p.colsum)
   const int tile_n = tile % p.tiles_n, tile_m = tile / p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
+  if constexpr (X3 && (GROUPED || NT == 256)) {      // (the towers' grouped big tile and the 4-wave forms: the plain 8-wave tiles never carry a map)
+    // sparse backward: a tile that nothing but zero dZ rows can reach (the launcher: dense stride-1 dgrad, destination row = GEMM row, no bias /
+    // residual, atomic column sums -- a zero tile adds nothing to them) loads no operand and runs no K-step: it stores its zero rows, heads and
+    // tails, which the next dgrad reads as halo, and returns.  Workgroup-uniform: scalar loads of at most BM / 64 map bytes, one branch.
+    const unsigned char* const om = AOD_GSEL(omap, p.omap);
+    if (om) {
+      const int mend = m0 + BM < p.M ? m0 + BM : p.M;
+      int any = 0;
+      for (int b = m0 >> 6; b <= (mend - 1) >> 6; ++b) any |= om[b];
+      if (!any) {
+        const int NPz = ((p.N + 31) >> 5) << 6;
+        const int c0 = 2 * n0, c1 = 2 * (n0 + BN) < NPz ? 2 * (n0 + BN) : NPz;      // (BN % 32 == 0: whole head | tail bands)
+        const int cpr = (c1 - c0) >> 3, nch = (mend - m0) * cpr;
+        bf16_t* const yz = reinterpret_cast<bf16_t*>(g_y) + (long long)m0 * NPz + c0;
+        bf16x8 z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.f;
+        for (int i = (int)threadIdx.x; i < nch; i += NT) {
+          const int r = i / cpr, c = i - r * cpr;
+          *reinterpret_cast<bf16x8*>(yz + (long long)r * NPz + c * 8) = z;
+        }
+        return;
+      }
+    }
+  }
 #ifdef AOD_TILE_TIMING
   if (m0 < 0) return;      // (forces the argument loads ahead of the stamp)
   TSTAMP(8);
@@ -1058,13 +1090,13 @@ struct ConvKnobs {
   static const Once& once() { static const Once k{}; return k; }
 
   enum Call { X3P_OVER_256, X3_TILE_192, X3P_GROUPED, X3P, X3P_PRE, X3P_BN, X3P_DGRAD, X3P_LATTICE, X3P_MIN_STEPS, X3P_PRE_MIN_STEPS, X3P_MIN_TILES,
-              X3P_ROT, NCALL };
+              X3P_ROT, SPARSE_BWD, NCALL };
   const char* val[NCALL];
   unsigned seen = 0;
   const char* call(Call k) {
     static const char* const names[NCALL] = {"AOD_X3P_OVER_256", "AOD_X3_TILE_192", "AOD_X3P_GROUPED", "AOD_X3P", "AOD_X3P_PRE", "AOD_X3P_BN",
                                              "AOD_X3P_DGRAD", "AOD_X3P_LATTICE", "AOD_X3P_MIN_STEPS", "AOD_X3P_PRE_MIN_STEPS", "AOD_X3P_MIN_TILES",
-                                             "AOD_X3P_ROT"};
+                                             "AOD_X3P_ROT", "AOD_SPARSE_BWD"};
     if (!((seen >> k) & 1u)) { val[k] = getenv(names[k]); seen |= 1u << k; }
     return val[k];
   }
@@ -1176,6 +1208,71 @@ static int conv_params_grouped(const aod_conv_desc_t* desc, int ngroups, const v
     p.grp[g].pre_shift = pre_shift ? pre_shift[g] : nullptr;
     p.grp[g].mask = mask ? (const bf16_t*)mask[g] : nullptr;
     p.grp[g].colsum = colsum ? colsum[g] : nullptr;
+  }
+  return 0;
+}
+
+// ---- sparse backward: row-activity maps (one byte per 64 rows of a gradient row tensor; 0 = every row of the block is exactly zero).
+// out[b] = OR of in[] over the dZ rows that the destination rows of block b can reach through the filter taps of a dense stride-1 dgrad: the
+// linear range [first - up W - left, last + down W + right] of the segment, cut to the whole image rows and to the images the block touches.
+struct MapGeo { int nseg, M, R, S, pad, dil; int segH[8], segW[8], seg_mend[8]; };
+__global__ __launch_bounds__(256) void row_map_dilate_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, const MapGeo g) {
+  const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (b >= (g.M + 63) >> 6) return;
+  const int r0 = b << 6, r1 = r0 + 63 < g.M ? r0 + 63 : g.M - 1;
+  const int up = (g.R - 1) * g.dil - g.pad, dn = g.pad, lf = (g.S - 1) * g.dil - g.pad, rt = g.pad;
+  int any = 0;
+  for (int sg = 0; sg < g.nseg; ++sg) {
+    const int s0 = sg ? g.seg_mend[sg - 1] : 0, s1 = g.seg_mend[sg];
+    const int lo = (r0 > s0 ? r0 : s0) - s0, hi = (r1 < s1 - 1 ? r1 : s1 - 1) - s0;
+    if (lo > hi) continue;
+    const int W = g.segW[sg], hw = g.segH[sg] * W;
+    int a = lo - up * W - lf, z = hi + dn * W + rt;
+    const int qa = (lo / W - up) * W, qz = (hi / W + dn + 1) * W - 1;
+    a = a > qa ? a : qa; z = z < qz ? z : qz;
+    const int ia = (lo / hw) * hw, iz = (hi / hw + 1) * hw - 1;
+    a = a > ia ? a : ia; z = z < iz ? z : iz;
+    for (int k = (s0 + a) >> 6; k <= (s0 + z) >> 6; ++k) any |= in[k];
+  }
+  out[b] = any ? 1 : 0;
+}
+
+// in_map[g] / out_map[g] of a (grouped) dgrad launch: writes every out_map from its in_map (a small launch of its own, ahead of the conv) and
+// hands the conv kernel the OUT map of each member whose zero tiles are safe to skip.  ngroups = 0: the plain launch (p.omap).
+static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map, void* const* out_map, hipStream_t st) {
+  const int ng = ngroups ? ngroups : 1;
+  bool any = false;
+  for (int g = 0; g < ng; ++g) {
+    AOD_CHECK_ARG(!in_map[g] == !out_map[g], "conv (map): member %d needs both its incoming and its outgoing map, or neither", g);
+    any = any || in_map[g];
+  }
+  if (!any || p.M == 0) return 0;
+  AOD_CHECK_ARG(p.x3 && p.transposed && p.stride == 1 && !p.out_f32 && !p.perm && !p.up_w, "conv (map): row-activity maps exist for the x3 stride-1 dgrad with X-layout rows only");
+  AOD_CHECK_ARG((p.R - 1) * p.dil >= p.pad && (p.S - 1) * p.dil >= p.pad, "conv (map): padding beyond the filter");
+  MapGeo mg;
+  memset(&mg, 0, sizeof(mg));
+  mg.nseg = p.nseg; mg.M = p.M; mg.R = p.R; mg.S = p.S; mg.pad = p.pad; mg.dil = p.dil;
+  for (int i = 0; i < p.nseg; ++i) {
+    const long long m0 = i ? p.seg_mend[i - 1] : 0;
+    AOD_CHECK_ARG(p.segH[i] == p.segOH[i] && p.segW[i] == p.segOW[i] && p.seg_src0[i] == m0 && p.seg_dst0[i] == m0,
+                  "conv (map): segment %d is not a dense same-size map (dZ and dX rows must both be GEMM rows)", i);
+    mg.segH[i] = p.segH[i]; mg.segW[i] = p.segW[i]; mg.seg_mend[i] = p.seg_mend[i];
+  }
+  const int nblk = (p.M + 63) >> 6;
+  ConvKnobs kn;
+  const bool dense = kn.is(ConvKnobs::SPARSE_BWD, '0');      // AOD_SPARSE_BWD=0: the maps are still written, no tile is skipped
+  for (int g = 0; g < ng; ++g) {
+    if (!in_map[g]) continue;
+    hipLaunchKernelGGL(row_map_dilate_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, (const unsigned char*)in_map[g], (unsigned char*)out_map[g], mg);
+    AOD_LAUNCH_CHECK();
+    // a skipped tile stores zeros and sends no column sums: only where the epilogue of a zero accumulator IS zero (no bias / scale / residual)
+    // and the column sums are atomics (deterministic mode expects a partial row from every tile: it stays dense)
+    const float* const shift = ngroups ? p.grp[g].pre_shift : p.pre_shift;
+    float* const cs = ngroups ? p.grp[g].colsum : p.colsum;
+    const bool skip_ok = !dense && !shift && !p.pre_scale && !p.res && !p.post_scale && !p.zraw && !(cs && aod_get_deterministic());
+    if (!skip_ok) continue;
+    if (ngroups) { p.grp[g].omap = (const unsigned char*)out_map[g]; p.interleave = 1; }
+    else p.omap = (const unsigned char*)out_map[g];
   }
   return 0;
 }
@@ -1390,9 +1487,10 @@ static void x3p_args(const ConvKParams& p, const ConvPlan& plan, X3PArgs& a) {
   // the kernel reads its operands from grp[]: the groups of a grouped launch, else the one set above
   a.ngroups = p.ngroups > 1 ? p.ngroups : 1;
   a.grp[0].x = a.x; a.grp[0].w = a.w; a.grp[0].y = a.y; a.grp[0].shift = a.pre_shift; a.grp[0].mask = a.mask; a.grp[0].colsum = a.colsum;
+  a.grp[0].omap = p.omap;
   for (int g = 0; g < p.ngroups; ++g) {
     a.grp[g].x = p.grp[g].x; a.grp[g].w = p.grp[g].w; a.grp[g].y = reinterpret_cast<bf16_t*>(p.grp[g].y); a.grp[g].shift = p.grp[g].pre_shift;
-    a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum;
+    a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum; a.grp[g].omap = p.grp[g].omap;
   }
   a.lat = plan.lat; a.up_w = p.up_w; a.up_hw = p.up_hw;
   const long long rows = a.lat == 1 ? (long long)a.segB[0] * (a.segOH[0] / 2) * (a.segOW[0] / 2) : a.M;
@@ -1442,6 +1540,7 @@ static int conv_launch(const ConvPlan& pl, ConvKParams& p, void* workspace, size
       const size_t need = (size_t)pl.ksplit * p.M * p.N * 4;
       AOD_CHECK_ARG(workspace && workspace_bytes >= need, "conv: split-K workspace of %zu bytes, need %zu (aod_conv2d_ws_bytes)", workspace_bytes, need);
       p.ksplit = pl.ksplit; p.ws = (float*)workspace;
+      p.omap = nullptr;                    // (a K slice has no epilogue of its own: split launches stay dense)
       int rc = launch_igemm(pl, p, st);
       if (rc) return rc;
       AOD_LAUNCH_CHECK();
@@ -1462,10 +1561,11 @@ static int conv_launch(const ConvPlan& pl, ConvKParams& p, void* workspace, size
   return -1;
 }
 
-extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
-                             const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
-                             const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
-                             aod_stream_t stream) {
+// aod_conv2d_ws with the row-activity maps of the sparse backward (x3 stride-1 dgrad; both null: the plain launch)
+extern "C" int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
+                                 const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
+                                 const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
+                                 const void* in_map, void* out_map, aod_stream_t stream) {
   ConvKParams p;
   ConvPlan pl;
   int rc = conv_params(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, p);
@@ -1473,12 +1573,24 @@ extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const
   if (p.M == 0) return 0;
   rc = conv_plan(p, 0, workspace != nullptr, pl);
   if (rc) return rc;
+  rc = conv_map_setup(p, 0, &in_map, &out_map, (hipStream_t)stream);
+  if (rc) return rc;
   return conv_launch(pl, p, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
-                                  void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
-                                  aod_stream_t stream) {
+extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
+                             const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
+                             const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
+                             aod_stream_t stream) {
+  return aod_conv2d_ws_map(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, workspace, workspace_bytes, nullptr,
+                           nullptr, stream);
+}
+
+// aod_conv2d_grouped with per-member row-activity maps (in_map / out_map: arrays of ngroups pointers, null entries = dense members; both
+// arrays null: the plain launch)
+extern "C" int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                      void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
+                                      const void* const* in_map, void* const* out_map, aod_stream_t stream) {
   ConvKParams p;
   ConvPlan pl;
   int rc = conv_params_grouped(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, p);
@@ -1486,7 +1598,18 @@ extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, cons
   if (p.M == 0) return 0;
   rc = conv_plan(p, ngroups, false, pl);
   if (rc) return rc;
+  AOD_CHECK_ARG(!in_map == !out_map, "conv_grouped (map): incoming and outgoing maps come together");
+  if (in_map) {
+    rc = conv_map_setup(p, ngroups, in_map, out_map, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   return conv_launch(pl, p, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                  void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
+                                  aod_stream_t stream) {
+  return aod_conv2d_grouped_map(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, nullptr, nullptr, stream);
 }
 
 extern "C" int aod_conv2d(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
@@ -1593,6 +1716,8 @@ struct WgradParams {
   int tiles_n, tiles_k, splits, rows_per_split, stagger, xcd_order, x3;
   long long x_bytes, z_bytes, tab_bytes;
   long long slab_stride;     // > 0: split s STORES its partial tile into dw + s * slab_stride (deterministic, summed by the unpack); 0: fp32 atomics
+  const unsigned char* zmap; // sparse backward (the wide x3 forms' SPARSE instances): row-activity map of dZ, one byte per 64 GEMM rows (dense dZ
+                             // segments: GEMM row = dZ row); a workgroup walks only the pixel steps of its split whose block is 1.  nullptr: all
 };
 
 // byte offset of (row, 16-B chunk) in a 256-B-pitch bf16 image that serves transposed reads
@@ -1613,7 +1738,10 @@ __device__ __forceinline__ int tr_off(int row, int ch) {
 // [h32 | l32] band pairs (4-wave 128 x 128 form: 64 x 64 per wave; 8-wave 256 x 256 form: 128 x 64): its zl x xl quarter (2^-16 of the
 // result) is skipped at compile time, which leaves exactly the three products of the forward form; the unpack kernel adds the three bands
 // of every slab.
-template <int NW, int TN, int TK, bool X3>
+// SPARSE (the 4-wave x3 instance; launches that carry a row-activity map of dZ): the active 64-row blocks of the whole pixel axis are dealt to
+// the splits cyclically and a workgroup walks only its share -- see wgrad_tile_x3w below, the same scheme with one 64-pixel step per block.
+constexpr int WG_SLIST_BYTES = 8192;      // LDS behind the row-record ring of a SPARSE instance: the list of a workgroup's blocks (16-bit entries)
+template <int NW, int TN, int TK, bool X3, bool SPARSE = false>
 __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
   static_assert(!X3 || (NW == 4 && TN == 1 && TK == 1) || (NW == 8 && TN == 2 && TK == 2), "X3: wave blocks must be whole [h32 | l32] band pairs");
   constexpr int RPW = 4 * NW;          // pixel rows covered per pass of all waves
@@ -1637,9 +1765,13 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
   const int split = bid / ntile; bid -= split * ntile;
   const int tile_k = bid % p.tiles_k, tile_n = bid / p.tiles_k;
   const int n0 = tile_n * (128 * TN), k0 = tile_k * (128 * TK);
-  const int ms = split * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
-  if (ms >= me) return;
+  int ms = split * p.rows_per_split;
+  int me = min(p.M, ms + p.rows_per_split);
+  if (ms >= me) return;                                        // (never a planned split: splits = ceil(M / rows_per_split))
+  constexpr int SLIST_CAP = WG_SLIST_BYTES / 2;
+  const int nbt = (p.M + 63) >> 6;
+  const bool deal = SPARSE && p.zmap && nbt <= 65535 && (nbt + p.splits - 1) / p.splits <= SLIST_CAP;
+  if (deal) { ms = 0; me = p.M; }
   const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
   const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, (int)p.z_bytes, 0x00020000);
   const int prow = lane >> 4;                                  // pixel row inside the wave's 4-row group
@@ -1713,13 +1845,39 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nsteps = (me - ms + BKM - 1) / BKM;
-  tdma(ms, 0);
-  if (nsteps > 1) tdma(ms + BKM, 1);
-  __syncthreads();                                            // records of steps 0 and 1 are resident
-  rread(0);
-  gload(ms, 0);
-  __syncthreads();
+  unsigned short* const slist = reinterpret_cast<unsigned short*>(stab + 4096);
+  int nact = -1;                                                // -1: every step of the contiguous range
+  if constexpr (SPARSE) {
+    if (deal) {
+      int base = 0;                                             // (every wave counts, wave 0 writes)
+      for (int c = 0; c < nbt; c += 64) {
+        const int b = c + lane;
+        const bool on = b < nbt && p.zmap[b] != 0;
+        const unsigned long long bm = __ballot(on);
+        const int j = base + (int)__popcll(bm & ((1ull << lane) - 1ull));
+        if (uw == 0 && on && j % p.splits == split) slist[j / p.splits] = (unsigned short)b;
+        base += (int)__popcll(bm);
+      }
+      base = __builtin_amdgcn_readfirstlane(base);
+      nact = base > split ? (base - split + p.splits - 1) / p.splits : 0;
+      __syncthreads();
+    }
+  }
+  const int nsteps = (SPARSE && nact >= 0) ? nact : (me - ms + BKM - 1) / BKM;
+  auto mbase = [&](int stp) {
+    if constexpr (SPARSE) {
+      if (nact >= 0) return __builtin_amdgcn_readfirstlane((int)slist[stp]) * 64;
+    }
+    return ms + stp * BKM;
+  };
+  if (nsteps > 0) {
+    tdma(mbase(0), 0);
+    if (nsteps > 1) tdma(mbase(1), 1);
+    __syncthreads();                                            // records of steps 0 and 1 are resident
+    rread(0);
+    gload(mbase(0), 0);
+    __syncthreads();
+  }
   // transposed-read lane roles: group g = lane>>4 covers k rows 8g..8g+7 of a 32-row sub-step; lane 4q+pp -> row q, cols 4pp..4pp+3
   const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
   // stagger (8-wave form): waves 4-7 run half a step behind waves 0-3, with which they share their SIMDs (see conv_igemm_kernel)
@@ -1781,10 +1939,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
     if (late && carried) mfma_block();
     if (stp + 1 < nsteps) {
       rread((stp + 1) & 1);                                 // landed before the previous barrier
-      gload(ms + (stp + 1) * BKM, cur ^ 1);
+      gload(mbase(stp + 1), cur ^ 1);
     }
     // slot stp & 1 held this step's records; every wave read them one iteration ago (ahead of the barrier), so it can be refilled
-    if (stp + 2 < nsteps) tdma(ms + (stp + 2) * BKM, stp & 1);
+    if (stp + 2 < nsteps) tdma(mbase(stp + 2), stp & 1);
     const char* sz = smem + cur * STAGE;
     const char* sx = sz + TN * IMG;
     frag_read(sz, sx, 0);
@@ -1854,7 +2012,14 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
 // NW = 8, T = 4: 512 x 512 physical columns = 256 x 256 logical entries, one workgroup per CU.  NW = 4, T = 2: 256 x 256 physical = 128 x 128
 // logical (2 x 2 waves, 64 x 64 logical per wave, 16 accumulators; two workgroups per CU): the backbone layers whose dW is not whole
 // 512-column tiles or whose pixel axis is too short to fill the chip with the big form.
-template <int NW, int T>
+// SPARSE (launches that carry a row-activity map of dZ, sparse backward): the active 64-row blocks of the WHOLE pixel axis are DEALT to the
+// member's splits cyclically -- active block j goes to split j % splits -- and a workgroup compacts its share into an LDS list and runs its
+// rings (row records, LDS-DMA stages) over that list instead of over the pixel steps of a contiguous range.  The positives sit at the end of
+// the pyramid buffer (P4 - P7), so a contiguous split kept 45 - 64 % of its steps and the launch lasted as long as that split; the deal gives
+// every split the same count.  A skipped step would have added dZ = 0 products only; what changes is WHICH slab a step's products land in,
+// i.e. the fp32 summation order of the filter gradient (mapped launches only).  A split without a block stores a zero slab.  More blocks
+// than the 16-bit list entries / the list can hold: the contiguous range, every step.
+template <int NW, int T, bool SPARSE = false>
 __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in) {
   static_assert((NW == 8 && T == 4) || (NW == 4 && T == 2), "wide x3 wgrad forms");
   constexpr int TN = T, TK = T, BKM = 32;
@@ -1871,9 +2036,13 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
   const int split = bid / ntile; bid -= split * ntile;
   const int tile_k = bid % p.tiles_k, tile_n = bid / p.tiles_k;
   const int n0 = tile_n * (128 * T), k0 = tile_k * (128 * T);       // physical columns
-  const int ms = split * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
-  if (ms >= me) return;
+  int ms = split * p.rows_per_split;
+  int me = min(p.M, ms + p.rows_per_split);
+  if (ms >= me) return;                                        // (never a planned split: both plans set splits = ceil(M / rows_per_split), so no dealt share is lost here)
+  constexpr int SLIST_CAP = (2048 + WG_SLIST_BYTES) / 2;
+  const int nbt = (p.M + 63) >> 6;                             // 64-row blocks of the whole pixel axis
+  const bool deal = SPARSE && p.zmap && nbt <= 65535 && (nbt + p.splits - 1) / p.splits <= SLIST_CAP;
+  if (deal) { ms = 0; me = p.M; }                              // the workgroup's rows come from all over the axis
   const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
   const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, (int)p.z_bytes, 0x00020000);
   const auto rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void*)p.tab, 0, (int)p.tab_bytes, 0x00020000);
@@ -1942,13 +2111,41 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int nsteps = (me - ms + BKM - 1) / BKM;
-  tdma(ms, 0);
-  if (nsteps > 1) tdma(ms + BKM, 1);
-  __syncthreads();
-  rread(0);
-  gload(ms, 0);
-  __syncthreads();
+  // this split's share of the active blocks: the j-th active block of the axis (ascending) belongs to split j % splits, at list slot j / splits
+  constexpr int SPB = 64 / BKM;                                 // pixel steps per block
+  unsigned short* const slist = reinterpret_cast<unsigned short*>(stab + 2048);
+  int nact = -1;                                                // -1: every step of the contiguous range (no map, or too many blocks)
+  if constexpr (SPARSE) {
+    if (deal) {
+      int base = 0;                                             // (every wave counts, wave 0 writes: the count needs no LDS word)
+      for (int c = 0; c < nbt; c += 64) {
+        const int b = c + lane;
+        const bool on = b < nbt && p.zmap[b] != 0;
+        const unsigned long long bm = __ballot(on);
+        const int j = base + (int)__popcll(bm & ((1ull << lane) - 1ull));
+        if (uw == 0 && on && j % p.splits == split) slist[j / p.splits] = (unsigned short)b;
+        base += (int)__popcll(bm);
+      }
+      base = __builtin_amdgcn_readfirstlane(base);
+      nact = base > split ? (base - split + p.splits - 1) / p.splits : 0;
+      __syncthreads();
+    }
+  }
+  const int nsteps = (SPARSE && nact >= 0) ? SPB * nact : (me - ms + BKM - 1) / BKM;
+  auto mbase = [&](int stp) {
+    if constexpr (SPARSE) {
+      if (nact >= 0) return ms + __builtin_amdgcn_readfirstlane((int)slist[stp / SPB]) * 64 + (stp % SPB) * BKM;
+    }
+    return ms + stp * BKM;
+  };
+  if (nsteps > 0) {
+    tdma(mbase(0), 0);
+    if (nsteps > 1) tdma(mbase(1), 1);
+    __syncthreads();
+    rread(0);
+    gload(mbase(0), 0);
+    __syncthreads();
+  }
   const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
   typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
@@ -1969,9 +2166,9 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
     const int cur = stp & 1;
     if (stp + 1 < nsteps) {
       rread((stp + 1) & 1);                                 // landed before the previous barrier
-      gload(ms + (stp + 1) * BKM, cur ^ 1);
+      gload(mbase(stp + 1), cur ^ 1);
     }
-    if (stp + 2 < nsteps) tdma(ms + (stp + 2) * BKM, stp & 1);
+    if (stp + 2 < nsteps) tdma(mbase(stp + 2), stp & 1);
     const char* sz = smem + cur * STAGE;
     const char* sx = sz + TN * IMG;
     // heads of dZ, heads and tails of x
@@ -2027,41 +2224,41 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
         if (n < NL && k < KL) dwp[(long long)n * KL + k] = acc[i][j][r];
       }
 }
-template <int NW, int T>
+template <int NW, int T, bool SPARSE = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wgrad_x3w_kernel(const WgradParams p) {
-  wgrad_tile_x3w<NW, T>(p, p.xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
+  wgrad_tile_x3w<NW, T, SPARSE>(p, p.xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
 }
 
 // split of the pixel axis over workgroups: all workgroups co-resident (<= 2 per CU, no ragged second round); cost model (measured on
 // MI355X): one 64-pixel step costs ~1.45 us with one workgroup per CU and ~1.7 us with two (both share the CU); every workgroup ends with
 // 64 KB of output -- fp32 atomics at ~1.3 TB/s chip-wide (0.05 us per workgroup) or, in slab mode, plain stores at ~5.5 TB/s (0.012 us)
 // plus the unpack kernel's read of one more slab per split.
-template <int NW, int TN, int TK, bool X3 = false>
+template <int NW, int TN, int TK, bool X3 = false, bool SPARSE = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(TN * TK > 1 ? 2 : NW / 2, TN * TK > 1 ? 2 : NW / 2))) void conv_wgrad_kernel(const WgradParams p) {
-  wgrad_tile<NW, TN, TK, X3>(p, p.xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
+  wgrad_tile<NW, TN, TK, X3, SPARSE>(p, p.xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
 }
 // Grouped launch: up to WG_MAXG weight gradients (ANY geometries, one tile form) share one grid.  Alone a backbone layer needs 100+ pixel
 // splits of its few 128 x 128 tiles to fill the chip -- a 512 x 128 filter (256 KB) leaves 30 MB of partial slabs for the unpack; three
 // layers together need a third of the splits each (longer pixel runs per workgroup, a third of the slab traffic, one launch).
 constexpr int WG_MAXG = 4;
 struct WgradGroups { WgradParams g[WG_MAXG]; int wg0[WG_MAXG + 1]; int n; };
-template <int NW, int TN, int TK, bool X3 = false>
+template <int NW, int TN, int TK, bool X3 = false, bool SPARSE = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(TN * TK > 1 ? 2 : NW / 2, TN * TK > 1 ? 2 : NW / 2))) void conv_wgrad_grouped_kernel(const WgradGroups gp) {
   const int b = gp.g[0].xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
   // (selects, not an indexed read of the argument block: a run-time index would move the whole array to scratch memory)
-  if (b < gp.wg0[1]) wgrad_tile<NW, TN, TK, X3>(gp.g[0], b);
-  else if (b < gp.wg0[2]) wgrad_tile<NW, TN, TK, X3>(gp.g[1], b - gp.wg0[1]);
-  else if (b < gp.wg0[3]) wgrad_tile<NW, TN, TK, X3>(gp.g[2], b - gp.wg0[2]);
-  else wgrad_tile<NW, TN, TK, X3>(gp.g[3], b - gp.wg0[3]);
+  if (b < gp.wg0[1]) wgrad_tile<NW, TN, TK, X3, SPARSE>(gp.g[0], b);
+  else if (b < gp.wg0[2]) wgrad_tile<NW, TN, TK, X3, SPARSE>(gp.g[1], b - gp.wg0[1]);
+  else if (b < gp.wg0[3]) wgrad_tile<NW, TN, TK, X3, SPARSE>(gp.g[2], b - gp.wg0[2]);
+  else wgrad_tile<NW, TN, TK, X3, SPARSE>(gp.g[3], b - gp.wg0[3]);
 }
 
-template <int NW, int T>
+template <int NW, int T, bool SPARSE = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wgrad_grouped_x3w_kernel(const WgradGroups gp) {
   const int b = gp.g[0].xcd_order ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
-  if (b < gp.wg0[1]) wgrad_tile_x3w<NW, T>(gp.g[0], b);
-  else if (b < gp.wg0[2]) wgrad_tile_x3w<NW, T>(gp.g[1], b - gp.wg0[1]);
-  else if (b < gp.wg0[3]) wgrad_tile_x3w<NW, T>(gp.g[2], b - gp.wg0[2]);
-  else wgrad_tile_x3w<NW, T>(gp.g[3], b - gp.wg0[3]);
+  if (b < gp.wg0[1]) wgrad_tile_x3w<NW, T, SPARSE>(gp.g[0], b);
+  else if (b < gp.wg0[2]) wgrad_tile_x3w<NW, T, SPARSE>(gp.g[1], b - gp.wg0[1]);
+  else if (b < gp.wg0[3]) wgrad_tile_x3w<NW, T, SPARSE>(gp.g[2], b - gp.wg0[2]);
+  else wgrad_tile_x3w<NW, T, SPARSE>(gp.g[3], b - gp.wg0[3]);
 }
 
 // `big`: tile form -- 0 = 128 x 128, 1 = 256 x 256, 2 = the WIDE x3 form of 8 waves (512 x 512 physical columns = 256 x 256 logical entries,
@@ -2137,6 +2334,20 @@ static int wgrad_fill(const aod_conv_desc_t* d, const void* x, const void* dz, f
   return 0;
 }
 
+// the row-activity map of dZ a launch may follow (sparse backward), or nullptr: x3, dense dZ segments (GEMM row m IS dZ row m, which is how
+// the map is indexed) and AOD_SPARSE_BWD not 0
+static const unsigned char* wgrad_map(const aod_conv_desc_t* d, const void* dz_map) {
+  if (!dz_map || !d->x3) return nullptr;
+  long long m = 0;
+  for (int i = 0; i < d->nseg; ++i) {
+    if (d->seg[i].dst_row0 != m) return nullptr;
+    m += (long long)d->seg[i].B * d->seg[i].OH * d->seg[i].OW;
+  }
+  ConvKnobs kn;
+  if (kn.is(ConvKnobs::SPARSE_BWD, '0')) return nullptr;
+  return (const unsigned char*)dz_map;
+}
+
 static void wgrad_attrs() {
   static unsigned long long attr_done = 0;
   if (!aod_first_on_device(&attr_done)) return;
@@ -2153,14 +2364,21 @@ static void wgrad_attrs() {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_grouped_x3w_kernel<8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 4096);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_x3w_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_grouped_x3w_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<4, 1, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096 + WG_SLIST_BYTES);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_grouped_kernel<4, 1, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096 + WG_SLIST_BYTES);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_x3w_kernel<8, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 4096 + WG_SLIST_BYTES);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_grouped_x3w_kernel<8, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 4096 + WG_SLIST_BYTES);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_x3w_kernel<4, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096 + WG_SLIST_BYTES);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_grouped_x3w_kernel<4, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4096 + WG_SLIST_BYTES);
 }
 
 static int wgrad_launch(const aod_conv_desc_t* d, const void* x, const void* dz, float* dw, long long slab_stride, int max_slabs,
-                        const void* row_table, aod_stream_t stream) {
+                        const void* row_table, aod_stream_t stream, const void* dz_map = nullptr) {
   WgradParams p;
   int rc = wgrad_fill(d, x, dz, dw, row_table, p);
   if (rc) return rc;
   if (p.M == 0) return 0;
+  p.zmap = wgrad_map(d, dz_map);
   int splits, rps, big;
   wgrad_plan(p.M, p.N, p.K, slab_stride > 0, p.tiles_n, p.tiles_k, splits, rps, big, 49152, p.x3);
   const int tiles = p.tiles_n * p.tiles_k;
@@ -2174,9 +2392,12 @@ static int wgrad_launch(const aod_conv_desc_t* d, const void* x, const void* dz,
   static const char* dbg_w8 = getenv("AOD_WGRAD_W8");      // (debug: 0 = the 4-wave form)
   if (p.x3) {
     AOD_CHECK_ARG(slab_stride > 0, "wgrad (x3): slab form only");
-    if (big == 2) hipLaunchKernelGGL((conv_wgrad_x3w_kernel<8, 4>), dim3(tiles * splits), dim3(512), 131072 + 4096, (hipStream_t)stream, p);
+    if (big == 2 && p.zmap) hipLaunchKernelGGL((conv_wgrad_x3w_kernel<8, 4, true>), dim3(tiles * splits), dim3(512), 131072 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, p);
+    else if (big == 3 && p.zmap) hipLaunchKernelGGL((conv_wgrad_x3w_kernel<4, 2, true>), dim3(tiles * splits), dim3(256), 65536 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, p);
+    else if (big == 2) hipLaunchKernelGGL((conv_wgrad_x3w_kernel<8, 4>), dim3(tiles * splits), dim3(512), 131072 + 4096, (hipStream_t)stream, p);
     else if (big == 3) hipLaunchKernelGGL((conv_wgrad_x3w_kernel<4, 2>), dim3(tiles * splits), dim3(256), 65536 + 4096, (hipStream_t)stream, p);
     else if (big) hipLaunchKernelGGL((conv_wgrad_kernel<8, 2, 2, true>), dim3(tiles * splits), dim3(512), 131072 + 4096, (hipStream_t)stream, p);
+    else if (p.zmap) hipLaunchKernelGGL((conv_wgrad_kernel<4, 1, 1, true, true>), dim3(tiles * splits), dim3(256), 65536 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((conv_wgrad_kernel<4, 1, 1, true>), dim3(tiles * splits), dim3(256), 65536 + 4096, (hipStream_t)stream, p);
   } else if (big) hipLaunchKernelGGL((conv_wgrad_kernel<8, 2, 2>), dim3(tiles * splits), dim3(512), 131072 + 4096, (hipStream_t)stream, p);
   else if (!(dbg_w8 && dbg_w8[0] == '0')) hipLaunchKernelGGL((conv_wgrad_kernel<8, 1, 1>), dim3(tiles * splits), dim3(512), 65536 + 4096, (hipStream_t)stream, p);
@@ -2260,9 +2481,35 @@ extern "C" int aod_conv2d_wgrad_group_plan(const aod_conv_desc_t* const* descs, 
   return 0;
 }
 
-extern "C" int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz,
-                                        float* const* slabs, const int32_t* nslabs, const int64_t* slab_stride,
-                                        const void* const* row_table, aod_stream_t stream) {
+// The split plan as data: n = 1 -- what aod_conv2d_wgrad_slabs(_map) does with this descriptor; n = 2 .. 4 -- what the grouped launch does.
+// form: 0 = 128 x 128 tile, 1 = 256 x 256, 2 = wide x3 form of 8 waves, 3 = wide x3 form of 4 waves; split s of member g covers GEMM rows
+// [s * rows_per_split[g], (s + 1) * rows_per_split[g]).  Returns 1 when the members cannot share a grid.
+extern "C" int aod_conv2d_wgrad_plan(const aod_conv_desc_t* const* descs, int n, int32_t* form, int32_t* splits_out, int32_t* rows_per_split) {
+  AOD_CHECK_ARG(descs && form && splits_out && rows_per_split && n >= 1 && n <= WG_MAXG, "wgrad_plan: 1..4 descriptors");
+  int M[WG_MAXG], N[WG_MAXG], K[WG_MAXG], tn[WG_MAXG], tk[WG_MAXG], sp[WG_MAXG], rps[WG_MAXG];
+  for (int g = 0; g < n; ++g) {
+    AOD_CHECK_ARG(descs[g] && !descs[g]->transposed, "wgrad_plan: forward descriptors");
+    ConvKParams cp;
+    memset(&cp, 0, sizeof(cp));
+    int rc = fill_params(descs[g], cp);
+    if (rc) return rc;
+    AOD_CHECK_ARG(cp.M > 0, "wgrad_plan: empty member");
+    M[g] = cp.M; N[g] = cp.N; K[g] = cp.K;
+    if (descs[g]->x3 != descs[0]->x3) return 1;
+  }
+  int big;
+  if (n == 1) wgrad_plan(M[0], N[0], K[0], true, tn[0], tk[0], sp[0], rps[0], big, 49152, descs[0]->x3);
+  else big = wgrad_plan_group(n, M, N, K, tn, tk, sp, rps, descs[0]->x3);
+  if (big < 0) return 1;
+  *form = big;
+  for (int g = 0; g < n; ++g) { splits_out[g] = sp[g]; rows_per_split[g] = rps[g]; }
+  return 0;
+}
+
+// aod_conv2d_wgrad_grouped with the row-activity maps of the members' dZ (dz_map: n pointers, null entries = dense members; null: none)
+extern "C" int aod_conv2d_wgrad_grouped_map(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz,
+                                            float* const* slabs, const int32_t* nslabs, const int64_t* slab_stride,
+                                            const void* const* row_table, const void* const* dz_map, aod_stream_t stream) {
   AOD_CHECK_ARG(descs && x && dz && slabs && nslabs && slab_stride && row_table && n >= 1 && n <= WG_MAXG, "wgrad_grouped: 1..4 members");
   WgradGroups gp;
   memset(&gp, 0, sizeof(gp));
@@ -2273,7 +2520,10 @@ extern "C" int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int
     AOD_CHECK_ARG(gp.g[g].M > 0, "wgrad_grouped: empty member");
     M[g] = gp.g[g].M; N[g] = gp.g[g].N; K[g] = gp.g[g].K;
     AOD_CHECK_ARG(gp.g[g].x3 == gp.g[0].x3, "wgrad_grouped: members of different precision modes");
+    gp.g[g].zmap = dz_map ? wgrad_map(descs[g], dz_map[g]) : nullptr;
   }
+  bool sparse = false;
+  for (int g = 0; g < n; ++g) sparse = sparse || gp.g[g].zmap;
   const int x3 = gp.g[0].x3;
   const int big = wgrad_plan_group(n, M, N, K, tn, tk, sp, rps, x3);
   AOD_CHECK_ARG(big >= 0, "wgrad_grouped: the members take different tile forms (aod_conv2d_wgrad_group_plan tells)");
@@ -2289,14 +2539,23 @@ extern "C" int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int
   for (int g = n; g <= WG_MAXG; ++g) gp.wg0[g] = g == n ? wg : 0x7fffffff;
   gp.n = n;
   wgrad_attrs();
-  if (x3 && big == 2) hipLaunchKernelGGL((conv_wgrad_grouped_x3w_kernel<8, 4>), dim3(wg), dim3(512), 131072 + 4096, (hipStream_t)stream, gp);
+  if (x3 && big == 2 && sparse) hipLaunchKernelGGL((conv_wgrad_grouped_x3w_kernel<8, 4, true>), dim3(wg), dim3(512), 131072 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, gp);
+  else if (x3 && big == 3 && sparse) hipLaunchKernelGGL((conv_wgrad_grouped_x3w_kernel<4, 2, true>), dim3(wg), dim3(256), 65536 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, gp);
+  else if (x3 && big == 2) hipLaunchKernelGGL((conv_wgrad_grouped_x3w_kernel<8, 4>), dim3(wg), dim3(512), 131072 + 4096, (hipStream_t)stream, gp);
   else if (x3 && big == 3) hipLaunchKernelGGL((conv_wgrad_grouped_x3w_kernel<4, 2>), dim3(wg), dim3(256), 65536 + 4096, (hipStream_t)stream, gp);
   else if (x3 && big) hipLaunchKernelGGL((conv_wgrad_grouped_kernel<8, 2, 2, true>), dim3(wg), dim3(512), 131072 + 4096, (hipStream_t)stream, gp);
+  else if (x3 && big == 0 && sparse) hipLaunchKernelGGL((conv_wgrad_grouped_kernel<4, 1, 1, true, true>), dim3(wg), dim3(256), 65536 + 4096 + WG_SLIST_BYTES, (hipStream_t)stream, gp);
   else if (x3) hipLaunchKernelGGL((conv_wgrad_grouped_kernel<4, 1, 1, true>), dim3(wg), dim3(256), 65536 + 4096, (hipStream_t)stream, gp);
   else if (big) hipLaunchKernelGGL((conv_wgrad_grouped_kernel<8, 2, 2>), dim3(wg), dim3(512), 131072 + 4096, (hipStream_t)stream, gp);
   else hipLaunchKernelGGL((conv_wgrad_grouped_kernel<8, 1, 1>), dim3(wg), dim3(512), 65536 + 4096, (hipStream_t)stream, gp);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz,
+                                        float* const* slabs, const int32_t* nslabs, const int64_t* slab_stride,
+                                        const void* const* row_table, aod_stream_t stream) {
+  return aod_conv2d_wgrad_grouped_map(descs, n, x, dz, slabs, nslabs, slab_stride, row_table, nullptr, stream);
 }
 
 extern "C" int aod_conv2d_wgrad(const aod_conv_desc_t* d, const void* x, const void* dz, float* dw, const void* row_table,
@@ -2318,6 +2577,13 @@ extern "C" int aod_conv2d_wgrad_slabs(const aod_conv_desc_t* d, const void* x, c
                                       const void* row_table, aod_stream_t stream) {
   AOD_CHECK_ARG(nslabs >= 1 && slab_stride > 0, "wgrad_slabs: nslabs / slab_stride");
   return wgrad_launch(d, x, dz, slabs, slab_stride, nslabs, row_table, stream);
+}
+
+// ... following the row-activity map of dZ (sparse backward; the wide x3 forms -- other launches ignore it; null: aod_conv2d_wgrad_slabs)
+extern "C" int aod_conv2d_wgrad_slabs_map(const aod_conv_desc_t* d, const void* x, const void* dz, float* slabs, int nslabs, int64_t slab_stride,
+                                          const void* row_table, const void* dz_map, aod_stream_t stream) {
+  AOD_CHECK_ARG(nslabs >= 1 && slab_stride > 0, "wgrad_slabs: nslabs / slab_stride");
+  return wgrad_launch(d, x, dz, slabs, slab_stride, nslabs, row_table, stream, dz_map);
 }
 
 // =====================================================================================

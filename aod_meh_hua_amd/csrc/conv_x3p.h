@@ -24,7 +24,9 @@ struct X3PArgs {
                             // (b, y, x) is stored at destination row b * up_hw + 2y * up_w + 2x
   int up_w, up_hw;
   int ngroups;              // >= 1: grp[] holds the operands (grp[0] repeats the fields above for a plain launch)
-  struct { const bf16_t* x; const bf16_t* w; bf16_t* y; const float* shift; const bf16_t* mask; float* colsum; } grp[4];
+  // omap (optional, the 3x3 / 256-column dense form): row-activity map of the DESTINATION rows, one byte per 64 (conv.hip, conv_map_setup) -- a tile
+  // whose two blocks are 0 issues and consumes no stage and stores zero rows
+  struct { const bf16_t* x; const bf16_t* w; bf16_t* y; const float* shift; const bf16_t* mask; float* colsum; const unsigned char* omap; } grp[4];
   long long x_bytes, w_bytes;
   int segH[8], segW[8], segOH[8], segOW[8], segB[8];
   long long seg_src0[8], seg_dst0[8];

@@ -98,8 +98,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int cls = (tile % tpg) / tpc;
     return ((cls >> 1) ? 2 : 1) * ((cls & 1) ? 2 : 1);
   };
+  // SPARSE (the head towers' 3x3 / 256-column dgrad, sparse backward): with a row-activity map of the destination (grp[].omap) a tile whose two
+  // 64-row blocks are 0 is DEAD -- the loaders issue no stage for it, the consumers run no K-step and store zero rows.  Both sides take the
+  // decision from the same two map bytes (written by an earlier launch), so the ring, which does not know about tiles, stays in step.
+  constexpr bool SPARSE = TAPS == 9 && NBW == 8 && LAT == 0 && PRE == 0;
+  auto tile_live = [&](int tile) {
+    if constexpr (!SPARSE) return true;
+    else {
+      const int gi = tile / tpg, m0 = ((tile - gi * tpg) / p.tiles_n) * XP_BM;
+      const unsigned char* const om = XP_GSEL(omap);
+      if (!om) return true;
+      const int mend = m0 + XP_BM < p.M ? m0 + XP_BM : p.M;
+      return __builtin_amdgcn_readfirstlane((int)om[m0 >> 6] | (int)om[(mend - 1) >> 6]) != 0;
+    }
+  };
   int total = 0;
   if (LAT == 1) { for (int j = 0; j < nmine; ++j) total += taps_of(tile_of(j)) * CC; }
+  else if (SPARSE) { for (int j = 0; j < nmine; ++j) total += tile_live(tile_of(j)) ? TAPS * CC : 0; }
   else total = nmine * TAPS * CC;
   auto seg_of = [&](int m) {
     int sg = 0;
@@ -128,6 +143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     char* const lds_w = smem + (8 * w) * 128;
     for (int j = 0; j < nmine; ++j) {
       const int tile = tile_of(j);
+      if (!tile_live(tile)) continue;
       const int gi = tile / tpg, tl0 = tile - gi * tpg;
       const int cls = LAT == 1 ? tl0 / tpc : 0, tl = tl0 - cls * tpc;
       const int py = cls >> 1, px = cls & 1;                      // class-major form: parity of the destination pixels of this tile
@@ -258,6 +274,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tm = tl / p.tiles_n, tn = tl - tm * p.tiles_n;
     const int m0 = tm * XP_BM, n0 = tn * BN;
     const int nk = taps_of(tile) * CC;
+    if constexpr (SPARSE) {
+      if (!tile_live(tile)) {
+        // dense destination (launcher): row m of the tile is destination row m; BN columns = 2 BN elements of the X-layout row, in 16-B pieces
+        const int mend = m0 + XP_BM < p.M ? m0 + XP_BM : p.M;
+        constexpr int CPR = 2 * BN / 8;
+        bf16_t* const yz = XP_GSEL(y) + (long long)m0 * NP + 2 * n0;
+        bf16x8 z;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) z[q] = (bf16_t)0.f;
+        for (int i = (int)threadIdx.x; i < (mend - m0) * CPR; i += 256)
+          *reinterpret_cast<bf16x8*>(yz + (long long)(i / CPR) * NP + (i % CPR) * 8) = z;
+        continue;
+      }
+    }
     f32x4 acc[NBW][4];
 #pragma unroll
     for (int nb = 0; nb < NBW; ++nb)

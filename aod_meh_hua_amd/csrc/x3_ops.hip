@@ -273,7 +273,7 @@ extern "C" int aod_x3_act_bwd(const void* g, const void* a, void* dz, float* col
 // g fp32 [M][N] (N = 180 / 36 / 9) -> dz X rows of 2 * ceil32(N) columns, zero in the pad channels; colsum fp32 [ceil32(N)]
 __global__ __launch_bounds__(256) void x3_pad_cast_colsum_kernel(const float* __restrict__ g, const float* __restrict__ a, bf16_t* __restrict__ dz,
                                                                  float* __restrict__ colsum, long long M, int N, int Np, int rows_per_block, int TC,
-                                                                 float* __restrict__ cs_ws) {
+                                                                 float* __restrict__ cs_ws, unsigned char* __restrict__ map) {
   __shared__ float red[256];
   const int RP = 256 / TC;
   const int c0 = threadIdx.x % TC, rl = threadIdx.x / TC;
@@ -288,6 +288,7 @@ __global__ __launch_bounds__(256) void x3_pad_cast_colsum_kernel(const float* __
         if (c < N) {
           v = g[m * N + c];
           if (a && !(a[m * N + c] > 0.f)) v = 0.f;
+          if (map && !(v == 0.f)) map[m >> 6] = 1;      // row-activity map (zeroed by the launcher): NaN counts as active, -0 does not
         }
         const bf16_t h = (bf16_t)v;
         dz[m * 2 * Np + col] = h;
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256) void x3_pad_cast_colsum_kernel(const float* __
 // 8 c8 .. + 7 of a band of 32; a chunk that straddles N (176 .. 183 of 180) reads its valid half only.
 __global__ __launch_bounds__(256) void x3_pad_cast_colsum_v8_kernel(const float* __restrict__ g, const float* __restrict__ a, bf16_t* __restrict__ dz,
                                                                     float* __restrict__ colsum, long long M, int N, int Np, int rows_per_block, int TC8,
-                                                                    float* __restrict__ cs_ws) {
+                                                                    float* __restrict__ cs_ws, unsigned char* __restrict__ map) {
   __shared__ float red[256][9];
   const int RP = 256 / TC8;
   const int c8 = threadIdx.x % TC8, rl = threadIdx.x / TC8;
@@ -336,6 +337,12 @@ __global__ __launch_bounds__(256) void x3_pad_cast_colsum_v8_kernel(const float*
       float v[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) { v[j] = v0[j]; v[4 + j] = v1[j]; }
+      if (map) {
+        bool nz = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) nz = nz || !(v[j] == 0.f);
+        if (nz) map[m >> 6] = 1;
+      }
       xstore(dz + m * 2 * Np + col, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) s[j] += v[j];
@@ -353,9 +360,14 @@ __global__ __launch_bounds__(256) void x3_pad_cast_colsum_v8_kernel(const float*
   }
 }
 
-extern "C" int aod_x3_pad_cast_colsum(const float* g, const float* relu_out_f32, void* dz, float* colsum, int64_t M, int N, aod_stream_t stream) {
+// ... with `map` (optional, (M + 63) / 64 bytes): also the ROW-ACTIVITY MAP of dz -- byte b = 1 when any value of rows 64 b .. 64 b + 63 fails
+// v == 0 (a NaN counts as something), else 0.  The sparse backward of the reg / MEH towers starts from it (conv.hip, aod_conv2d_ws_map).
+extern "C" int aod_x3_pad_cast_colsum_map(const float* g, const float* relu_out_f32, void* dz, float* colsum, int64_t M, int N, void* map_,
+                                          aod_stream_t stream) {
   if (M == 0) return 0;
+  unsigned char* const map = (unsigned char*)map_;
   AOD_CHECK_ARG(g && dz && colsum && N >= 1, "x3_pad_cast_colsum: bad args");
+  if (map && hipMemsetAsync(map, 0, (size_t)((M + 63) / 64), (hipStream_t)stream) != hipSuccess) return aod_set_err(-3, "x3_pad_cast_colsum: memset of the map failed");
   const int Np = (N + 31) / 32 * 32;
   if ((N & 3) == 0 && Np <= 256 && (((size_t)g | (size_t)(relu_out_f32 ? relu_out_f32 : g)) & 15) == 0) {
     int tc8 = 4;                                   // chunks per row, a power of two (idle lanes past Np / 8)
@@ -365,7 +377,7 @@ extern "C" int aod_x3_pad_cast_colsum(const float* g, const float* relu_out_f32,
     const int nb = (int)((M + rpb - 1) / rpb);
     float* const cs_ws = aod_det_scratch((size_t)nb * N);
     hipLaunchKernelGGL(x3_pad_cast_colsum_v8_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g, relu_out_f32, (bf16_t*)dz, colsum, (long long)M, N, Np,
-                       rpb, tc8, cs_ws);
+                       rpb, tc8, cs_ws, map);
     AOD_LAUNCH_CHECK();
     if (cs_ws) return aod_colsum_finalize(cs_ws, nb, N, N, colsum, nullptr, 0, (hipStream_t)stream);
     return 0;
@@ -377,10 +389,14 @@ extern "C" int aod_x3_pad_cast_colsum(const float* g, const float* relu_out_f32,
   const int nb = (int)((M + rpb - 1) / rpb);
   float* const cs_ws = aod_det_scratch((size_t)nb * N);
   hipLaunchKernelGGL(x3_pad_cast_colsum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g, relu_out_f32, (bf16_t*)dz, colsum,
-                     (long long)M, N, Np, rpb, tc, cs_ws);
+                     (long long)M, N, Np, rpb, tc, cs_ws, map);
   AOD_LAUNCH_CHECK();
   if (cs_ws) return aod_colsum_finalize(cs_ws, nb, N, N, colsum, nullptr, 0, (hipStream_t)stream);
   return 0;
+}
+
+extern "C" int aod_x3_pad_cast_colsum(const float* g, const float* relu_out_f32, void* dz, float* colsum, int64_t M, int N, aod_stream_t stream) {
+  return aod_x3_pad_cast_colsum_map(g, relu_out_f32, dz, colsum, M, N, nullptr, stream);
 }
 
 // ---------------------------------------------------------------- SSD300-VGG16 in the reference-precision mode (BASELINE config 0)

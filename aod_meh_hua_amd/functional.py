@@ -446,6 +446,24 @@ def _grad_slice(w, device):
 
 
 _S1_OF = {}      # data_ptr of a masked gradient handed to a residual branch -> (its column sums, the tensor); emptied after every pass
+# Sparse backward (hipops.sparse_bwd): data_ptr of a gradient row tensor -> (its row-activity map, the tensor); emptied after every pass.  The
+# box-regression and MEH gradients are zero at every non-positive anchor: retina_reg / retina_L's backward builds the map of its dZ
+# (pad_cast_colsum), every tower dgrad hands the map of its dX on to the layer below, whose dgrad skips the tiles that only zero rows reach.
+_ROW_MAPS = {}
+MAP_LOG = None       # tests: a list that receives every (gradient rows shape, map) pair in the order the backward pass produced them
+
+
+def _map_of(dz):
+    e = _ROW_MAPS.get(dz.data_ptr())
+    return e[0] if e is not None and e[1].shape == dz.shape and e[1].dtype == dz.dtype and ho.sparse_bwd() else None
+
+
+def _keep_map(dx, rmap):
+    if rmap is not None:
+        if MAP_LOG is not None:
+            MAP_LOG.append((tuple(dx.shape), rmap))
+        _WgradQueue.begin_pass()        # (registers the callback that empties the table at the end of the pass)
+        _ROW_MAPS[dx.data_ptr()] = (rmap, dx)
 
 
 class _WgradQueue:
@@ -457,15 +475,24 @@ class _WgradQueue:
       * autograd installs a returned tensor as .grad without reading it only if .grad is None and nothing else refers to the tensor (the job
         keeps aliases); a parameter whose .grad exists, or that is used twice in one pass (the engine adds the two gradients when the second
         arrives), is not deferred -- and the second use flushes the queue first;
-      * segmented backward passes (data parallelism) are separate engine runs: every segment's gradients are complete when its run returns."""
+      * segmented backward passes (data parallelism) are separate engine runs: every segment's gradients are complete when its run returns.
+    Sparse backward: jobs whose dZ carries a row-activity map (retina_reg / retina_L and the reg / MEH tower convs) wait in a queue of their
+    OWN.  A grouped launch is one round of co-resident workgroups and lasts as long as its slowest one, so a mapped member beside a dense one
+    would save nothing; mapped members together finish after their share of the few active pixel blocks.  The four cls tower filters left in
+    the dense queue are the same four geometries as before (cls, reg, cls, reg), so their group plan -- slab count, summation order -- is
+    unchanged; retina_cls loses its launch partner retina_reg and runs on its stand-alone plan (other slab boundaries: another fp32
+    summation order of the same products)."""
     jobs, seen, task, deferred = [], set(), -1, []
+    sparse_jobs = []
     enabled = _os.environ.get('AOD_WGRAD_GROUP', '1') != '0'
 
     @classmethod
     def flush(cls):
-        jobs, cls.jobs = cls.jobs, []
-        if jobs:
-            ho.wgrad_unpack_group(jobs)
+        for name in ('jobs', 'sparse_jobs'):
+            jobs = getattr(cls, name)
+            setattr(cls, name, [])
+            if jobs:
+                ho.wgrad_unpack_group(jobs)
 
     @classmethod
     def _verify(cls):
@@ -486,6 +513,7 @@ class _WgradQueue:
         cls.task = -1
         cls.seen.clear()
         _S1_OF.clear()
+        _ROW_MAPS.clear()
         cls.flush()
         cls._verify()
 
@@ -502,6 +530,7 @@ class _WgradQueue:
             cls.task = tid
             cls.seen.clear()
             _S1_OF.clear()
+            _ROW_MAPS.clear()
             if tid >= 0:
                 torch.autograd.Variable._execution_engine.queue_callback(cls._end_of_pass)
 
@@ -520,15 +549,20 @@ class _WgradQueue:
             cls.seen.add(wid)
             return False
         cls.seen.add(wid)
-        if cls.jobs and ho.wgrad_group_splits(cls.jobs + [job]) is None:
-            cls.flush()
-        cls.jobs.append(job)
-        if len(cls.jobs) == 4:
-            cls.flush()
+        name = 'sparse_jobs' if job.zmap is not None else 'jobs'
+        q = getattr(cls, name)
+        if q and ho.wgrad_group_splits(q + [job]) is None:
+            setattr(cls, name, [])
+            ho.wgrad_unpack_group(q)
+            q = getattr(cls, name)
+        q.append(job)
+        if len(q) == 4:
+            setattr(cls, name, [])
+            ho.wgrad_unpack_group(q)
         return True
 
 
-def _wgrad(x_rows, x_segs, dz, dsegs, R, S, stride, pad, dil, alg, w, O, I, dst, scale=None, bn=None, gamma=None):
+def _wgrad(x_rows, x_segs, dz, dsegs, R, S, stride, pad, dil, alg, w, O, I, dst, scale=None, bn=None, gamma=None, zmap=None):
     """weight gradient (+ BN weight gradient when bn = (s1, mean, invstd)) of one conv through the queue -> (gw, ggamma)"""
     dev = dz.device
     gw = dst if dst is not None else torch.empty(O, I, R, S, dtype=torch.float32, device=dev)
@@ -537,7 +571,7 @@ def _wgrad(x_rows, x_segs, dz, dsegs, R, S, stride, pad, dil, alg, w, O, I, dst,
     # one reference to it; otherwise it clones, one tiny copy launch per vector)
     job = ho.WgradJob(x_rows, x_segs, dz, dsegs, R, S, stride, pad, dil, alg, O, I, gw.detach(), scale=scale,
                       w=w.detach() if bn is not None else None, wdot=wdot.detach() if wdot is not None else None,
-                      bn=tuple(t.detach() for t in bn) if bn is not None else None)
+                      bn=tuple(t.detach() for t in bn) if bn is not None else None, zmap=zmap)
     # deferral hands autograd tensors that are written LATER (see _WgradQueue): only when nothing can read a gradient before the end-of-pass
     # flush -- no hooks on the parameters, no anomaly mode (it checks every returned gradient for NaNs), no graph being built on the backward
     hooked = lambda p: p is not None and bool(p._backward_hooks or getattr(p, '_post_accumulate_grad_hooks', None))
@@ -610,7 +644,11 @@ class ConvFn(Function):
         gw = ggamma = gbeta = gbias = gres = None
         if (meta['out_f32'] and X) or (Opad != O and not X):
             # prediction convs (N = 180 / 36 / 9, fp32 outputs): pad + cast + column sums in one pass
-            dz, gbias_v = ho.pad_cast_colsum(g_rows, Opad, a_rows if meta['relu'] else None)
+            if meta.get('sparse_grad') and X and ho.sparse_bwd():
+                dz, gbias_v, rmap = ho.pad_cast_colsum(g_rows, Opad, a_rows if meta['relu'] else None, want_map=True)
+                _keep_map(dz, rmap)
+            else:
+                dz, gbias_v = ho.pad_cast_colsum(g_rows, Opad, a_rows if meta['relu'] else None)
             gm = None
         else:
             # gm = g * [y > 0] (bf16) and its column sums S1.  With y = z*scale + shift the gradient w.r.t. z is gm*scale[n]; it is never
@@ -650,7 +688,8 @@ class ConvFn(Function):
         if need_w or need_bn:
             dst = _grad_slice(w, dz.device) if need_w else None
             gw, ggamma = _wgrad(x_rows, x_segs, dz, dsegs, R, S, meta['stride'], meta['pad'], meta['dil'], (I, O), w, O, I, dst,
-                                scale=scale if ctx.has_bn else None, bn=(s1, mean, invstd) if need_bn else None, gamma=gamma if need_bn else None)
+                                scale=scale if ctx.has_bn else None, bn=(s1, mean, invstd) if need_bn else None, gamma=gamma if need_bn else None,
+                                zmap=_map_of(dz))
             if need_bn:
                 gbeta = s1
             if not need_w:
@@ -701,9 +740,13 @@ class ConvFn(Function):
                 # PLACE: only the (even, even) pixels change, and the library then runs a plain GEMM over the dZ pixels (conv.hip, lattice launch)
                 inplace = (acc is not None and res_g is not None and jslot is None and not fuse and R == 1 and S == 1 and meta['stride'] == 2
                            and meta['pad'] == 0 and res_g.dtype == torch.bfloat16 and _os.environ.get('AOD_DGRAD_INPLACE', '1') != '0')
+                rmap = _map_of(dz) if (res_g is None and not inplace) else None
                 dx = ho.conv2d_dgrad_rows(dz, dsegs, xd, wd, I, R, S, meta['stride'], meta['pad'], meta['dil'],
                                           res=res_g, mask=x_rows if (fuse or jslot is not None) else None, colsum=s1_in, alg=(I, O),
-                                          out=res_g if inplace else None)
+                                          out=res_g if inplace else None, in_map=rmap)
+                if rmap is not None:
+                    dx, omap = dx
+                    _keep_map(dx, omap)
             if fuse:
                 in_slot.masked, in_slot.s1, in_slot.res_grad = True, s1_in, None
             if jslot is not None:
@@ -738,14 +781,17 @@ def _chain_ready(ch, meta3):
 
 
 def conv_bn_act(xs, w, bn=None, bias=None, res=None, stride=1, pad=0, dil=1, relu=False, out_f32=False, out=None, sole_consumer=False,
-                shared_input=False, pre=None, chain=None):
+                shared_input=False, pre=None, chain=None, sparse_grad=False):
     """xs: tensor or list of tensors (levels).  bn: object with weight/bias/running_mean/running_var/eps.
     sole_consumer: the caller guarantees that every x is the ReLU output of a conv_bn_act call and feeds NOTHING but this conv, which
     lets this conv's dgrad epilogue perform that producer's activation backward (ActSlot).  sole_consumer='res': x additionally feeds
-    the `res` input of ONE later conv_bn_act call (ResNet identity block), whose residual gradient is then routed through this conv."""
+    the `res` input of ONE later conv_bn_act call (ResNet identity block), whose residual gradient is then routed through this conv.
+    sparse_grad (fp32 prediction convs): the caller knows the output's gradient to be zero in most rows (box regression, MEH: zero at every
+    anchor that is not positive) -- the backward then carries a row-activity map down the tower (hipops.sparse_bwd)."""
     single = torch.is_tensor(xs)
     xl = [xs] if single else list(xs)
-    meta = dict(stride=stride, pad=pad, dil=dil, relu=relu, out_f32=out_f32, eps=bn.eps if bn is not None else 0.0, out=out, pre=pre)
+    meta = dict(stride=stride, pad=pad, dil=dil, relu=relu, out_f32=out_f32, eps=bn.eps if bn is not None else 0.0, out=out, pre=pre,
+                sparse_grad=bool(sparse_grad and out_f32))
     if chain is not None and torch.is_grad_enabled():
         meta['chain'] = chain
     if torch.is_grad_enabled():
@@ -829,7 +875,8 @@ class ConvPairFn(Function):
             gbs.append(s1[:O] if ctx.needs_input_grad[2 + 2 * gi] else None)
             gw = None
             if ctx.needs_input_grad[1 + 2 * gi]:
-                gw, _ = _wgrad(x_rows, x_segs, dz, dsegs, R, S, 1, meta['pad'], meta['dil'], (I, O), w, O, I, _grad_slice(w, dz.device))
+                gw, _ = _wgrad(x_rows, x_segs, dz, dsegs, R, S, 1, meta['pad'], meta['dil'], (I, O), w, O, I, _grad_slice(w, dz.device),
+                               zmap=_map_of(dz))
             gws.append(gw)
         gxs = [None] * (2 * nl)
         need = [any(ctx.needs_input_grad[5 + gi * nl:5 + (gi + 1) * nl]) for gi in range(2)]
@@ -841,8 +888,14 @@ class ConvPairFn(Function):
             fuse = [sl is not None and dense for sl in in_slots]
             assert all(sl is None or sl.res_grad is None for sl in in_slots)
             s1_in = [ho.zeros_f32(I, dzs[0].device) if f else None for f in fuse]
+            rmaps = [_map_of(dz) for dz in dzs]
             dxs = ho.conv2d_dgrad_rows_grouped(dzs, dsegs, xd, wds, I, R, S, 1, meta['pad'], meta['dil'],
-                                               masks=[xA if fuse[0] else None, xB if fuse[1] else None], colsums=s1_in, alg=(I, O))
+                                               masks=[xA if fuse[0] else None, xB if fuse[1] else None], colsums=s1_in, alg=(I, O),
+                                               in_maps=rmaps if any(m is not None for m in rmaps) else None)
+            if any(m is not None for m in rmaps):
+                dxs, omaps = dxs
+                for dx, om in zip(dxs, omaps):
+                    _keep_map(dx, om)
             for gi in range(2):
                 if fuse[gi]:
                     in_slots[gi].masked, in_slots[gi].s1 = True, s1_in[gi]

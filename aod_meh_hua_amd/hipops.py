@@ -244,31 +244,66 @@ def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pr
     return outs, dst_segs
 
 
-def conv2d_dgrad_rows_grouped(dzs, dz_segs, x_segs, wds, Cin, R, S, stride=1, pad=0, dil=1, *, masks=None, colsums=None, alg=None):
-    """G dgrads of identical geometry in one launch: dX_g = conv_T(dZ_g, W_g) (* [mask_g > 0], column sums into colsums[g])."""
+def sparse_bwd():
+    """Sparse backward of the reg / MEH towers (reference-precision mode): row-activity maps travel with the gradient rows and the dgrad
+    kernels skip the tiles nothing but zero rows can reach.  AOD_SPARSE_BWD=0: every map is None.  Deterministic mode stays dense."""
+    return X3 and not DETERMINISTIC and os.environ.get('AOD_SPARSE_BWD', '1') != '0'
+
+
+def row_map(rows, device):
+    """an (unwritten) row-activity map for `rows` gradient rows: one byte per 64 rows, 0 = all of them exactly zero"""
+    return torch.empty((rows + 63) // 64, dtype=torch.uint8, device=device)
+
+
+def _maps_apply(dz_segs, x_segs, stride, out_f32):
+    """maps exist for x3 stride-1 dgrads between dense maps of one size (dZ row = dX row = GEMM row): the head towers"""
+    r = 0
+    for a, b in zip(dz_segs, x_segs):
+        if (a.B, a.H, a.W) != (b.B, b.H, b.W) or a.row0 != r or b.row0 != r:
+            return False
+        r += a.rows
+    return X3 and stride == 1 and not out_f32
+
+
+def conv2d_dgrad_rows_grouped(dzs, dz_segs, x_segs, wds, Cin, R, S, stride=1, pad=0, dil=1, *, masks=None, colsums=None, alg=None,
+                              in_maps=None, outs=None):
+    """G dgrads of identical geometry in one launch: dX_g = conv_T(dZ_g, W_g) (* [mask_g > 0], column sums into colsums[g]).
+    in_maps (list of G row-activity maps of the dZ_g, None entries = dense members): returns (outs, out_maps) -- the maps of the dX_g."""
     G = len(dzs)
     Npad = dzs[0].shape[1]
     rows = sum(s.rows for s in x_segs)
-    outs = [torch.empty(rows, width(Cin), dtype=torch.bfloat16, device=dzs[0].device) for _ in range(G)]
+    if outs is None:
+        outs = [torch.empty(rows, width(Cin), dtype=torch.bfloat16, device=dzs[0].device) for _ in range(G)]
     d = make_desc(Npad, Cin, R, S, stride, pad, dil, dz_segs, x_segs, True, False, False)
     arr = lambda ts: (C.c_void_p * G)(*[(t.data_ptr() if t is not None else None) for t in ts])
     for t in list(dzs) + list(wds) + outs:
         ptr(t)
     keep = [arr(dzs), arr(wds), arr(outs), arr(masks) if masks is not None else None, arr(colsums) if colsums is not None else None]
-    fn = lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], stream())
+    out_maps = None
+    if in_maps is not None and any(m is not None for m in in_maps) and _maps_apply(dz_segs, x_segs, stride, False):
+        out_maps = [row_map(rows, outs[0].device) if m is not None else None for m in in_maps]
+        for m in in_maps:
+            assert m is None or (m.dtype == torch.uint8 and m.numel() == (rows + 63) // 64)
+        keep += [arr(in_maps), arr(out_maps)]
+        fn = lambda: call('aod_conv2d_grouped_map', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], keep[5], keep[6], stream())
+    else:
+        fn = lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], stream())
     if PROFILE is None:
         fn()
     else:
         _prof('dgrad', d, fn, (alg[0] * G, alg[1]) if alg is not None else (Npad * G, Cin))
+    if in_maps is not None:
+        return outs, (out_maps if out_maps is not None else [None] * G)
     return outs
 
 
 
 
 def conv2d_dgrad_rows(dz_rows, dz_segs, x_segs, w_dgrad, Cin, R, S, stride=1, pad=0, dil=1, *, res=None, mask=None,
-                      post_scale=None, out=None, x_rows_total=None, colsum=None, alg=None, out_f32=False):
+                      post_scale=None, out=None, x_rows_total=None, colsum=None, alg=None, out_f32=False, in_map=None):
     """dX = conv_transpose(dZ, W).  dz_rows [rows_out, Npad]; w_dgrad [Cin][R][S][Npad].
-    res / mask / colsum: fused activation backward of the producer of x (see aod_conv2d)."""
+    res / mask / colsum: fused activation backward of the producer of x (see aod_conv2d).
+    in_map: row-activity map of dZ (pad_cast_colsum / an earlier dgrad) -- then returns (dX, the map of dX or None when maps do not apply)."""
     Npad = dz_rows.shape[1]
     rows = x_rows_total if x_rows_total is not None else sum(s.rows for s in x_segs)
     if out is None:
@@ -278,6 +313,15 @@ def conv2d_dgrad_rows(dz_rows, dz_segs, x_segs, w_dgrad, Cin, R, S, stride=1, pa
         _prof('dgrad', d, lambda: call('aod_halo_conv3x3', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, ptr(mask), ptr(colsum), stream()), alg)
         return out
     ws, wsb = _splitk_ws(d, dz_rows.device)
+    if in_map is not None:
+        out_map = None
+        if x_rows_total is None and _maps_apply(dz_segs, x_segs, stride, out_f32):
+            assert in_map.dtype == torch.uint8 and in_map.numel() == (rows + 63) // 64
+            out_map = row_map(rows, out.device)
+        _prof('dgrad', d, lambda: call('aod_conv2d_ws_map', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, None, ptr(res), ptr(mask),
+                                       ptr(post_scale), None, ptr(colsum), ptr(ws), wsb, ptr(in_map) if out_map is not None else None,
+                                       ptr(out_map), stream()), alg)
+        return out, out_map
     _prof('dgrad', d, lambda: call('aod_conv2d_ws', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, None, ptr(res), ptr(mask),
                                    ptr(post_scale), None, ptr(colsum), ptr(ws), wsb, stream()), alg)
     return out
@@ -298,9 +342,10 @@ def _row_table(d, x_segs, dz_segs, Cin, Npad, R, S, stride, pad, dil, device):
 class WgradJob:
     """One weight gradient waiting for its launch: operands of conv2d_wgrad_rows + destinations of unpack_wgrad (all preallocated)."""
     __slots__ = ('x_rows', 'x_segs', 'dz', 'dz_segs', 'R', 'S', 'stride', 'pad', 'dil', 'alg', 'O', 'I', 'gw', 'scale', 'w', 'wdot', 'bn',
-                 'desc', 'scope')
+                 'desc', 'scope', 'zmap')
 
-    def __init__(self, x_rows, x_segs, dz, dz_segs, R, S, stride, pad, dil, alg, O, I, gw, scale=None, w=None, wdot=None, bn=None):
+    def __init__(self, x_rows, x_segs, dz, dz_segs, R, S, stride, pad, dil, alg, O, I, gw, scale=None, w=None, wdot=None, bn=None, zmap=None):
+        self.zmap = zmap          # row-activity map of dz (sparse backward): the wide x3 wgrad forms walk only the active pixel steps
         self.x_rows, self.x_segs, self.dz, self.dz_segs = x_rows, x_segs, dz, dz_segs
         self.R, self.S, self.stride, self.pad, self.dil, self.alg, self.O, self.I = R, S, stride, pad, dil, alg, O, I
         self.gw, self.scale, self.w, self.wdot, self.bn = gw, scale, w, wdot, bn
@@ -312,7 +357,8 @@ class WgradJob:
             self._run_alone()
 
     def _run_alone(self):
-        dw = conv2d_wgrad_rows(self.x_rows, self.x_segs, self.dz, self.dz_segs, self.R, self.S, self.stride, self.pad, self.dil, alg=self.alg)
+        dw = conv2d_wgrad_rows(self.x_rows, self.x_segs, self.dz, self.dz_segs, self.R, self.S, self.stride, self.pad, self.dil, alg=self.alg,
+                               zmap=self.zmap)
         unpack_wgrad(dw, self.O, self.I, grad_oihw=self.gw, scale=self.scale, w_oihw=self.w, want_wdot=self.wdot is not None, bn=self.bn,
                      wdot=self.wdot)
 
@@ -352,6 +398,10 @@ def wgrad_unpack_group(jobs):
     pv = lambda ts: PA(*[(ptr(t).value if t is not None else None) for t in ts])
 
     def launch():
+        if any(j.zmap is not None for j in jobs):
+            call('aod_conv2d_wgrad_grouped_map', PA(*[C.addressof(j.desc) for j in jobs]), n, pv([j.x_rows for j in jobs]),
+                 pv([j.dz for j in jobs]), pv(slabs), I32A(*splits), I64A(*strides), pv(tabs), pv([j.zmap for j in jobs]), stream())
+            return
         call('aod_conv2d_wgrad_grouped', PA(*[C.addressof(j.desc) for j in jobs]), n, pv([j.x_rows for j in jobs]), pv([j.dz for j in jobs]),
              pv(slabs), I32A(*splits), I64A(*strides), pv(tabs), stream())
     ms = [sum(sg.B * sg.H * sg.W for sg in j.dz_segs) for j in jobs]
@@ -368,7 +418,7 @@ def wgrad_unpack_group(jobs):
     SCOPE = prev_scope
 
 
-def conv2d_wgrad_rows(x_rows, x_segs, dz_rows, dz_segs, R, S, stride=1, pad=0, dil=1, dw=None, alg=None):
+def conv2d_wgrad_rows(x_rows, x_segs, dz_rows, dz_segs, R, S, stride=1, pad=0, dil=1, dw=None, alg=None, zmap=None):
     """dW of a conv: with `dw` given, [Npad][R][S][C] fp32 ACCUMULATED into it (fp32 atomics); otherwise the deterministic slab form --
     returns [nslabs][Npad][R][S][C] partial sums in a per-device scratch (valid until the next wgrad launch; unpack_wgrad adds them)."""
     Cin, Npad = x_rows.shape[1], dz_rows.shape[1]
@@ -385,6 +435,11 @@ def conv2d_wgrad_rows(x_rows, x_segs, dz_rows, dz_segs, R, S, stride=1, pad=0, d
         lg = 2 if X3 else 1                   # (x3: logical slabs, see wgrad_unpack_group)
         stride_ = (Npad // lg) * R * S * (Cin // lg)
         slabs = _slab_scratch(nslabs * stride_, x_rows.device).view(nslabs, Npad // lg, R, S, Cin // lg)
+        if zmap is not None:
+            assert zmap.dtype == torch.uint8 and zmap.numel() == (dz_rows.shape[0] + 63) // 64
+            _prof('wgrad', d, lambda: call('aod_conv2d_wgrad_slabs_map', C.byref(d), ptr(x_rows), ptr(dz_rows), ptr(slabs), nslabs, stride_, ptr(tab),
+                                           ptr(zmap), stream()), alg)
+            return slabs
         _prof('wgrad', d, lambda: call('aod_conv2d_wgrad_slabs', C.byref(d), ptr(x_rows), ptr(dz_rows), ptr(slabs), nslabs, stride_, ptr(tab), stream()), alg)
         return slabs
     _prof('wgrad', d, lambda: call('aod_conv2d_wgrad', C.byref(d), ptr(x_rows), ptr(dz_rows), ptr(dw), ptr(tab), stream()), alg)
@@ -785,15 +840,21 @@ def meh_loss_levels_bwd(lam, loss_noR, bbox_w4, level_rows, g, grad, A, form='l2
     return grad
 
 
-def pad_cast_colsum(g, npad, relu_out=None):
+def pad_cast_colsum(g, npad, relu_out=None, want_map=False):
+    """want_map (reference-precision mode): also the row-activity map of dz -> (dz, column sums, map)"""
     M, N = g.shape
     assert relu_out is None or relu_out.dtype == torch.float32
     if X3:          # fp32 head gradients -> X rows of xw(N) columns (npad is that width)
         assert g.dtype == torch.float32 and npad == xw(N)
         dz = torch.empty(M, npad, dtype=torch.bfloat16, device=g.device)
         cs = zeros_f32(npad // 2, g.device)
+        if want_map:
+            rmap = row_map(M, g.device)
+            call('aod_x3_pad_cast_colsum_map', ptr(g), ptr(relu_out), ptr(dz), ptr(cs), M, N, ptr(rmap), stream())
+            return dz, cs, rmap
         call('aod_x3_pad_cast_colsum', ptr(g), ptr(relu_out), ptr(dz), ptr(cs), M, N, stream())
         return dz, cs
+    assert not want_map, 'row-activity maps exist in the reference-precision mode only'
     dz = torch.empty(M, npad, dtype=torch.bfloat16, device=g.device)
     cs = zeros_f32(npad, g.device)
     call('aod_pad_cast_colsum', ptr(g), ptr(relu_out), ptr(dz), ptr(cs), M, N, npad, int(g.dtype == torch.float32), stream())

@@ -85,7 +85,7 @@ class Lambda_L2Net(L_AnchorHead):
             for i, conv in enumerate(self.reg_convs):
                 reg_feat = conv(reg_feat, sole_consumer=i > 0)
         return (self.retina_cls(cls_feat, out_f32=True, sole_consumer=len(self.cls_convs) > 0),
-                self.retina_reg(reg_feat, out_f32=True, sole_consumer=len(self.reg_convs) > 0))
+                self.retina_reg(reg_feat, out_f32=True, sole_consumer=len(self.reg_convs) > 0, sparse_grad=True))
 
     def forward_cls_dropout(self, feats):
         """The classification maps of one MC-dropout forward (functional.mc_dropout active, no autograd): the cls tower alone, level-batched
@@ -108,7 +108,7 @@ class Lambda_L2Net(L_AnchorHead):
             pre = None                  # another pyramid, or the tower's weights changed since forward(): compute it here
         for i, conv in enumerate(self.L_convs):
             L_feat = conv(L_feat, sole_consumer=i > 0, pre=pre[3][i] if pre is not None else None)
-        return self.retina_L(L_feat, relu=True, out_f32=True, sole_consumer=len(self.L_convs) > 0)
+        return self.retina_L(L_feat, relu=True, out_f32=True, sole_consumer=len(self.L_convs) > 0, sparse_grad=True)
 
     def forward_single(self, x):
         c, r = self.forward([x])

@@ -198,6 +198,22 @@ int aod_bottleneck256f_bwd(const void* g, int B, int H, int W, const void* wd3f,
 int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
                        const float* const* pre_shift, const void* const* mask, float* const* colsum, aod_stream_t stream);
 
+/* Sparse backward (reference-precision mode, stride-1 dgrad between dense same-size maps -- the head towers).  A ROW-ACTIVITY MAP is one byte
+ * per 64 rows of a gradient row tensor, (rows + 63) / 64 bytes: 0 = every row of the block is exactly zero, 1 = the block may hold
+ * something; a NULL map = everything may.  The box-regression and MEH gradients are zero at every anchor that is not positive, i.e. in
+ * ~99 % of the pyramid rows.  in_map describes dZ; the launch writes out_map, the map of dX (block b is 1 when a dZ block that the filter
+ * taps reach from its rows is: never 0 for a block that receives a non-zero value, never looser than the linear row range
+ * [first - W - 1, last + W + 1] of a 3x3), and a tile of the convolution whose dX blocks are all 0 loads nothing, multiplies nothing and stores
+ * zero rows (heads and tails).  Active tiles run the dense code: same bits.  Members with a bias / scale / residual operand, split-K launches,
+ * launches on kernels without the check and column sums in deterministic mode are computed densely (out_map is still written).
+ * in_map and out_map come together (grouped: per member; a member without maps is dense). */
+int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst, const float* pre_scale,
+                      const float* pre_shift, const void* res, const void* mask, const float* post_scale, void* zraw, float* colsum,
+                      void* workspace, size_t workspace_bytes, const void* in_map, void* out_map, aod_stream_t stream);
+int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
+                           const float* const* pre_shift, const void* const* mask, float* const* colsum, const void* const* in_map,
+                           void* const* out_map, aod_stream_t stream);
+
 /* replaces: the weight-gradient half of autograd's conv backward (cuDNN wgrad) for the same
  * call sites.  dw_f32 is [N][R][S][C] fp32 and is ACCUMULATED into (caller zeroes it);
  * x: forward input [rows, C] bf16; dz: [rows_out, N] bf16. */
@@ -218,6 +234,21 @@ int aod_conv2d_wgrad_slabs(const aod_conv_desc_t* desc, const void* x, const voi
 int aod_conv2d_wgrad_group_plan(const aod_conv_desc_t* const* descs, int n, int32_t* splits_out);
 int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz, float* const* slabs,
                              const int32_t* nslabs, const int64_t* slab_stride, const void* const* row_table, aod_stream_t stream);
+/* Sparse backward (see aod_conv2d_ws_map): the same launches following the row-activity map of each member's dZ.  The x3 forms with a SPARSE
+ * instance (the two wide forms and the 4-wave 128 x 128 form) deal the active 64-row blocks of the pixel axis to the member's splits
+ * cyclically -- active block j goes to split j mod splits -- and a workgroup walks only its share.  A skipped step would have added
+ * products of dZ = 0 only; the slabs hold OTHER partial sums than those of the launch without a map, their total is the same gradient in
+ * another fp32 summation order.  Other tile forms, non-dense dZ segments and AOD_SPARSE_BWD=0 ignore the map.
+ * dz_map: (rows + 63) / 64 bytes per member; NULL (or NULL entries): dense. */
+int aod_conv2d_wgrad_grouped_map(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz, float* const* slabs,
+                                 const int32_t* nslabs, const int64_t* slab_stride, const void* const* row_table, const void* const* dz_map,
+                                 aod_stream_t stream);
+/* The split plan of a weight-gradient launch as data (host logic only): n = 1 -- aod_conv2d_wgrad_slabs(_map); n = 2 .. 4 -- the grouped launch.
+ * form: 0 = 128 x 128 tile, 1 = 256 x 256, 2 / 3 = the wide x3 forms of 8 / 4 waves; split s of member g covers GEMM rows
+ * [s * rows_per_split[g], (s + 1) * rows_per_split[g]).  Returns 1 when the members cannot share a grid. */
+int aod_conv2d_wgrad_plan(const aod_conv_desc_t* const* descs, int n, int32_t* form, int32_t* splits, int32_t* rows_per_split);
+int aod_conv2d_wgrad_slabs_map(const aod_conv_desc_t* desc, const void* x, const void* dz, float* slabs, int nslabs, int64_t slab_stride,
+                               const void* row_table, const void* dz_map, aod_stream_t stream);
 /* Row table of a forward descriptor (32 B per destination pixel: source block origin, top-left tap, extents,
  * dZ row).  Depends only on segment geometry / stride / pad / filter size: build once, reuse for every wgrad
  * launch with that geometry. */
@@ -649,6 +680,10 @@ int aod_x3_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, 
 int aod_x3_act_bwd(const void* g, const void* a, void* dz, float* colsum, int64_t M, int C, int relu, aod_stream_t stream);
 /* aod_pad_cast_colsum: fp32 head gradients [M][N] (* [relu_out > 0]) -> X rows of 2*ceil32(N) columns + column sums fp32 [ceil32(N)] */
 int aod_x3_pad_cast_colsum(const float* g, const float* relu_out_f32, void* dz, float* colsum, int64_t M, int N, aod_stream_t stream);
+/* ... and the row-activity map of dz ((M + 63) / 64 bytes, see aod_conv2d_ws_map): a block is 1 when any of its values fails v == 0 (NaN counts,
+ * -0 does not).  dz and the column sums are those of the call without a map.  map NULL: aod_x3_pad_cast_colsum. */
+int aod_x3_pad_cast_colsum_map(const float* g, const float* relu_out_f32, void* dz, float* colsum, int64_t M, int N, void* map,
+                               aod_stream_t stream);
 
 /* aod_bottleneck64_fwd on X rows (reference-precision mode; csrc/bottleneck_x3.hip): x [B*H*W][2*Cin], w1 / w2 / w3 = the X filter images of
  * aod_param_prep (flags bit 0), res / y [B*H*W][512]; Cin = LOGICAL input channels (64 or 256). */
