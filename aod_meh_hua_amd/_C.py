@@ -164,6 +164,10 @@ _SIGS = {
     'aod_kcenter_chunk': (C.c_int, []),
     'aod_kcenter_ws_len': (SZ, [I64]),
     'aod_kcenter_greedy': (C.c_int, [P, I64, I32, P, I64, I64, P, P, P, P, P]),
+    'aod_kcenter_greedy_ex': (C.c_int, [P, I64, I32, P, I64, I64, P, P, P, P, P, I32]),
+    'aod_cdal_chunk': (C.c_int, []),
+    'aod_cdal_ws_len': (SZ, [I32, P, I32, I32]),
+    'aod_cdal_descriptor': (C.c_int, [P, I32, P, I32, I32, F32, P, I64, P, I64, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -51,6 +51,16 @@ class Uncertainty_fns:
         return Coreset_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'))
 
     @staticmethod
+    def CDAL(cfg, *args, **kwargs):
+        # contextual diversity (Agarwal et al., ECCV 2020), core-set form: like Coreset it needs the labelled set as the initial centers and
+        # reads none of the HUA options -- but score_thr, which is its own region threshold too (default 0.3, the same foreground threshold)
+        if kwargs.get('X_L') is None:
+            raise TypeError("Uncertainty_fns.CDAL needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
+        model, dataloader = args
+        thr = kwargs.get('score_thr')
+        return CDAL_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr)
+
+    @staticmethod
     def Entropy_NoNMS(cfg, *args, **kwargs):
         # the reference's own Entropy_NoNMS path calls ComputeScaleUnc with L_scores=None (Lambda_L2.py:404-405,364) and raises a
         # TypeError on the first batch: there is no behaviour to reproduce
@@ -438,6 +448,58 @@ def Coreset_uncertainty(cfg, model, data_loader, X_L=None, budget=None, **kwargs
     budget = int(cfg.X_S_size if budget is None else budget)
     desc = single_gpu_descriptors(model, data_loader, **kwargs)
     picks, _ = kcenter_greedy(desc, X_L, budget)
+    scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
+    scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
+    return scores.cpu()
+
+
+@torch.no_grad()
+def single_gpu_cdal_descriptors(model, data_loader, score_thr=0.3, **kwargs):
+    """CDAL descriptors of the whole pool on _PoolPass's loop: the pool is sharded over the ranks, batches come from the prefetch workers
+    through pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the forward (isEval=True, justOut=True: the
+    classification maps only) replays one captured graph -- the one single_gpu_ensemble keeps for a single member; the descriptor launch
+    (scoring.cdal_descriptor) runs eagerly behind the replay on the same stream, so it has read the graph's static maps before the next
+    replay overwrites them, and writes its rows straight into the preallocated [N, D] matrix.  parallel.gather_rows makes the matrix whole
+    on every rank.  Returns the device [N, D] fp32 tensor, D = 2 * cls_out_channels^2 (VOC: 800) = [P | ln P]; a row's bits depend on its
+    image alone -- not on the batch size, the rank count, or eager / replayed execution."""
+    from ..scoring import CDAL_MAX_CLASSES, cdal_descriptor
+    module = getattr(model, 'module', model)
+    head = getattr(module, 'bbox_head', None)
+    n_cls = getattr(head, 'cls_out_channels', None)
+    if not isinstance(n_cls, int) or n_cls != getattr(head, 'num_classes', None):
+        raise NotImplementedError(f'single_gpu_cdal_descriptors: CDAL descriptors are built for the RetinaNet heads (a softmax over the '
+                                  f'foreground classes), not for {type(module).__name__} / {type(head).__name__} (SSD: its rows carry a '
+                                  'background column)')
+    if n_cls > CDAL_MAX_CLASSES:
+        raise ValueError(f'single_gpu_cdal_descriptors: up to {CDAL_MAX_CLASSES} classes are supported (2 * C^2 <= 2048 descriptor columns), '
+                         f'the head has {n_cls}')
+    model.eval()
+    dev = next(model.parameters()).device
+    pool = _PoolPass(data_loader, dev)
+    desc = torch.zeros(pool.N, 2 * n_cls * n_cls, dtype=torch.float32, device=dev)
+    gscore = _graphed(model, dev, ('just_out', 0), kwargs, isEval=True, justOut=True)
+    for idxs, image_ids, data in pool.batches():
+        maps = _replay_or_eager(gscore, data, image_ids,
+                                lambda: model(return_loss=False, rescale=True, isEval=True, justOut=True, **data, **kwargs))
+        cdal_descriptor(maps, n_cls, score_thr, out=desc[idxs[0]:idxs[0] + len(idxs)])          # (a batch is a run of consecutive images)
+    owned = torch.zeros(pool.N, dtype=torch.bool, device=dev)
+    owned[pool.all_ids] = True
+    return gather_rows(desc, owned)[0]
+
+
+def CDAL_uncertainty(cfg, model, data_loader, X_L=None, budget=None, score_thr=0.3, **kwargs):
+    """CDAL acquisition (S. Agarwal, H. Arora, S. Anand, C. Arora, "Contextual Diversity for Active Learning", ECCV 2020, core-set form;
+    the reference has none) in the form update_X_L takes: class-mixture descriptors of the whole pool (single_gpu_cdal_descriptors), then
+    k-center greedy under the symmetrised KL divergence with the labelled images X_L as centers (scoring.kcenter_greedy(metric='symkl');
+    every rank runs it on the same matrix and gets the same picks).  budget: default cfg.X_S_size.  Returns a CPU [N] fp32 vector: the
+    image picked at step t = 0 .. budget - 1 scores budget - t, every other image 0 -- with a falsy zeroRate update_X_L's
+    arg[-X_S_size:] selects exactly the picks."""
+    from ..scoring import kcenter_greedy
+    if X_L is None:
+        raise TypeError('CDAL_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are the initial centers')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    desc = single_gpu_cdal_descriptors(model, data_loader, score_thr=score_thr, **kwargs)
+    picks, _ = kcenter_greedy(desc, X_L, budget, metric='symkl')
     scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
     scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
     return scores.cpu()

@@ -16,6 +16,8 @@
 //                               workgroup sweeps its rows against the picked center and writes its partial into the other partial buffer.
 //    d(i, c) = sum_k (x_ik - x_ck)^2 in the direct form; ONE wave per row, lane j owns the elements 4j + 256m (+0..3) (D % 4 == 0; else
 //    j + 64m), four running sums per lane, ((s0 + s1) + (s2 + s3)), xor butterfly: a function of the two rows and D alone.
+//    aod_kcenter_greedy_ex(..., metric = 1): the same kernels instantiated for the symmetrised KL divergence of [P | ln P] rows (CDAL,
+//    DESIGN 3j; kc_dists); metric 0 keeps the arithmetic above.
 //    Non-negative floats order like their bit patterns as unsigned integers (+inf included) and ~i makes the LOWEST index win a tie.
 #include <hip/hip_runtime.h>
 #include "../../include/aod_hip.h"
@@ -151,37 +153,66 @@ __device__ __forceinline__ u64 kc_block_max(u64 k, u64* red) {
   return m;
 }
 
-// squared distances of row x to NC centers staged in LDS (cen[c * D + k]); every lane returns all NC values
-template <int NC>
+// distances of row x to NC centers staged in LDS (cen[c * D + k]); every lane returns all NC values.
+// METRIC 0: the squared Euclidean distance.  METRIC 1 (CDAL): a row is [P | ln P], two halves of H = D / 2 columns, and
+// d = 1/2 sum_k max((P_k - Q_k)(ln P_k - ln Q_k), 0): the symmetrised KL divergence (every term is non-negative; the max only guards
+// against rounding).  The same lane ownership over the H columns of a half (4j + 256m (+0..3) when H % 4 == 0, else j + 64m), the same four
+// running sums and the same butterfly as metric 0 over its D columns; the halving is exact.
+template <int NC, int METRIC>
 __device__ __forceinline__ void kc_dists(const float* __restrict__ x, const float* cen, int D, int lane, float (&d)[NC]) {
   float s[NC][4];
 #pragma unroll
   for (int c = 0; c < NC; ++c) s[c][0] = s[c][1] = s[c][2] = s[c][3] = 0.f;
-  if ((D & 3) == 0) {
-    for (int k = 4 * lane; k < D; k += 256) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(x + k);
+  if constexpr (METRIC == 0) {
+    if ((D & 3) == 0) {
+      for (int k = 4 * lane; k < D; k += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + k);
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(cen + c * D + k);
+        for (int c = 0; c < NC; ++c) {
+          const f32x4 q = *reinterpret_cast<const f32x4*>(cen + c * D + k);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float t = v[u] - q[u];
-          s[c][u] += t * t;
+          for (int u = 0; u < 4; ++u) {
+            const float t = v[u] - q[u];
+            s[c][u] += t * t;
+          }
+        }
+      }
+    } else {
+      for (int k = lane; k < D; k += 64) {
+        const float v = x[k];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const float t = v - cen[c * D + k];
+          s[c][0] += t * t;
         }
       }
     }
-  } else {
-    for (int k = lane; k < D; k += 64) {
-      const float v = x[k];
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const float t = v - cen[c * D + k];
-        s[c][0] += t * t;
+    for (int c = 0; c < NC; ++c) d[c] = wave_sum((s[c][0] + s[c][1]) + (s[c][2] + s[c][3]));
+  } else {
+    const int H = D >> 1;                                          // (the entry refuses an odd D)
+    if ((H & 3) == 0) {
+      for (int k = 4 * lane; k < H; k += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + k);
+        const f32x4 lv = *reinterpret_cast<const f32x4*>(x + H + k);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const f32x4 q = *reinterpret_cast<const f32x4*>(cen + c * D + k);
+          const f32x4 lq = *reinterpret_cast<const f32x4*>(cen + c * D + H + k);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) s[c][u] += fmaxf((v[u] - q[u]) * (lv[u] - lq[u]), 0.f);
+        }
+      }
+    } else {
+      for (int k = lane; k < H; k += 64) {
+        const float v = x[k], lv = x[H + k];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) s[c][0] += fmaxf((v - cen[c * D + k]) * (lv - cen[c * D + H + k]), 0.f);
       }
     }
-  }
 #pragma unroll
-  for (int c = 0; c < NC; ++c) d[c] = wave_sum((s[c][0] + s[c][1]) + (s[c][2] + s[c][3]));
+    for (int c = 0; c < NC; ++c) d[c] = 0.5f * wave_sum((s[c][0] + s[c][1]) + (s[c][2] + s[c][3]));
+  }
 }
 
 __global__ __launch_bounds__(256) void kcenter_prepare_kernel(float* __restrict__ mind, unsigned char* __restrict__ sel, long long N) {
@@ -198,6 +229,7 @@ __global__ __launch_bounds__(256) void kcenter_mark_kernel(const long long* __re
   }
 }
 
+template <int METRIC>
 __global__ __launch_bounds__(256) void kcenter_centers_kernel(const float* __restrict__ desc, long long N, int D, const long long* __restrict__ lab,
                                                               int nc, float* __restrict__ mind) {
   extern __shared__ __align__(16) float cen[];                   // [KC_CHUNK][D]
@@ -213,7 +245,7 @@ __global__ __launch_bounds__(256) void kcenter_centers_kernel(const float* __res
   const long long wave = blockIdx.x * (long long)KC_WAVES + (threadIdx.x >> 6), nwaves = (long long)gridDim.x * KC_WAVES;
   for (long long i = wave; i < N; i += nwaves) {
     float d[KC_CHUNK];
-    kc_dists<KC_CHUNK>(desc + i * D, cen, D, lane, d);
+    kc_dists<KC_CHUNK, METRIC>(desc + i * D, cen, D, lane, d);
     if (lane == 0) {
       float m = mind[i];
 #pragma unroll
@@ -238,6 +270,7 @@ __global__ __launch_bounds__(256) void kcenter_keys_kernel(const float* __restri
 }
 
 // launch t = 1 .. budget: pick t - 1 (0-based) comes out of keys_in, is recorded, and every mind takes the distance to it
+template <int METRIC>
 __global__ __launch_bounds__(256) void kcenter_step_kernel(const float* __restrict__ desc, long long N, int D, float* __restrict__ mind,
                                                            unsigned char* __restrict__ sel, const u64* __restrict__ keys_in, int nkeys,
                                                            u64* __restrict__ keys_out, long long* __restrict__ picks, float* __restrict__ radius,
@@ -268,7 +301,7 @@ __global__ __launch_bounds__(256) void kcenter_step_kernel(const float* __restri
   u64 key = 0;
   for (long long i = wave; i < N; i += nwaves) {
     float d[1];
-    kc_dists<1>(desc + i * D, cen, D, lane, d);
+    kc_dists<1, METRIC>(desc + i * D, cen, D, lane, d);
     if (lane == 0) {
       const float m = fminf(mind[i], d[0]);
       mind[i] = m;
@@ -295,8 +328,9 @@ extern "C" size_t aod_kcenter_ws_len(int64_t N) {
   return (size_t)2 * KC_MAX_GRID * sizeof(u64) + (((size_t)N + 15) & ~(size_t)15);
 }
 
-extern "C" int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
-                                  float* radius, float* mind, void* ws, aod_stream_t stream) {
+template <int METRIC>
+static int kc_greedy(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks, float* radius,
+                     float* mind, void* ws, aod_stream_t stream) {
   AOD_CHECK_ARG(N >= 1 && N <= 0x7fffffffll, "kcenter_greedy: 1 .. 2^31 - 1 rows (got %lld)", (long long)N);
   AOD_CHECK_ARG(D >= 1 && D <= KC_MAX_D, "kcenter_greedy: 1 .. %d descriptor columns (got %d)", KC_MAX_D, D);
   AOD_CHECK_ARG(n_labelled >= 0 && n_labelled <= N, "kcenter_greedy: labelled count %lld outside 0 .. N = %lld", (long long)n_labelled, (long long)N);
@@ -316,17 +350,31 @@ extern "C" int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int
                        (int)n_labelled, sel, (long long)N);
     for (int64_t c0 = 0; c0 < n_labelled; c0 += KC_CHUNK) {
       const int nc = (int)(n_labelled - c0 < KC_CHUNK ? n_labelled - c0 : KC_CHUNK);
-      hipLaunchKernelGGL(kcenter_centers_kernel, dim3(grid), dim3(256), (size_t)KC_CHUNK * D * sizeof(float), st, desc, (long long)N, D,
+      hipLaunchKernelGGL(kcenter_centers_kernel<METRIC>, dim3(grid), dim3(256), (size_t)KC_CHUNK * D * sizeof(float), st, desc, (long long)N, D,
                          (const long long*)labelled + c0, nc, mind);
     }
   }
   hipLaunchKernelGGL(kcenter_keys_kernel, dim3(egrid), dim3(256), 0, st, (const float*)mind, (const unsigned char*)sel, (long long)N, keys[0]);
   int nkeys = egrid;
   for (int64_t t = 1; t <= budget; ++t) {
-    hipLaunchKernelGGL(kcenter_step_kernel, dim3(grid), dim3(256), (size_t)D * sizeof(float), st, desc, (long long)N, D, mind, sel,
+    hipLaunchKernelGGL(kcenter_step_kernel<METRIC>, dim3(grid), dim3(256), (size_t)D * sizeof(float), st, desc, (long long)N, D, mind, sel,
                        (const u64*)keys[(t - 1) & 1], nkeys, keys[t & 1], (long long*)picks, radius, (int)t);
     nkeys = grid;
   }
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+// metric 0: the squared Euclidean distance (Core-set); 1: the symmetrised KL divergence of [P | ln P] rows (CDAL)
+extern "C" int aod_kcenter_greedy_ex(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget,
+                                     int64_t* picks, float* radius, float* mind, void* ws, aod_stream_t stream, int metric) {
+  AOD_CHECK_ARG(metric == 0 || metric == 1, "kcenter_greedy: metric %d (0: squared Euclidean, 1: symmetrised KL)", metric);
+  if (metric == 0) return kc_greedy<0>(desc, N, D, labelled, n_labelled, budget, picks, radius, mind, ws, stream);
+  AOD_CHECK_ARG(D < 1 || D > KC_MAX_D || (D & 1) == 0, "kcenter_greedy: the symmetrised KL metric reads a row as two halves [P | ln P]: D = %d is odd", D);
+  return kc_greedy<1>(desc, N, D, labelled, n_labelled, budget, picks, radius, mind, ws, stream);
+}
+
+extern "C" int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
+                                  float* radius, float* mind, void* ws, aod_stream_t stream) {
+  return aod_kcenter_greedy_ex(desc, N, D, labelled, n_labelled, budget, picks, radius, mind, ws, stream, 0);
 }

@@ -356,20 +356,29 @@ def kcenter_chunk():
     return int(_C.lib.aod_kcenter_chunk())
 
 
-def kcenter_greedy(desc, labelled, budget):
+KCENTER_METRICS = {'sqeuclid': 0, 'symkl': 1}
+
+
+def kcenter_greedy(desc, labelled, budget, metric='sqeuclid'):
     """k-center greedy selection (Sener & Savarese, ICLR 2018, Algorithm 1) on the aod_kcenter_greedy kernels: starting from the labelled
     rows as centers, `budget` times pick the unselected row farthest (squared Euclidean distance, direct difference form, fp32) from its
     nearest center -- the lowest index on a tie -- and make it a center.
+    metric: 'sqeuclid' (Core-set) or 'symkl' (CDAL): a row is [P | ln P], two halves of D / 2 columns (D even), and
+    d(i, j) = 1/2 sum_k max((P_ik - P_jk)(ln P_ik - ln P_jk), 0), the symmetrised KL divergence summed over the classes.
 
     desc: [N, D] fp32 contiguous device tensor (D <= 2048); labelled: distinct row indices in [0, N) (sequence, array or tensor; may be
     empty: the first pick is then row 0 with radius inf); 1 <= budget <= number of unlabelled rows.
     Returns (picks [budget] int64, radius [budget] fp32) on the device, radius[t] = the distance of pick t at the time it was picked
     (non-increasing).  All steps are enqueued on the current stream; no host sync.  The result does not depend on the order of `labelled`."""
+    if metric not in KCENTER_METRICS:
+        raise ValueError(f"kcenter_greedy: unknown metric {metric!r} (expected 'sqeuclid' or 'symkl')")
     if not (torch.is_tensor(desc) and desc.dim() == 2 and desc.dtype == torch.float32 and desc.is_contiguous() and desc.numel() > 0):
         raise ValueError('kcenter_greedy: desc must be a non-empty contiguous 2-D fp32 tensor')
     N, D = int(desc.shape[0]), int(desc.shape[1])
     if D > 2048:
         raise ValueError(f'kcenter_greedy: up to 2048 descriptor columns are supported, got {D}')
+    if metric == 'symkl' and D % 2:
+        raise ValueError(f"kcenter_greedy: metric 'symkl' reads a row as two halves [P | ln P]; D = {D} is odd")
     lab = labelled.detach().cpu().numpy() if torch.is_tensor(labelled) else np.asarray(labelled)
     lab = lab.reshape(-1)
     if lab.size and not np.issubdtype(lab.dtype, np.integer):
@@ -392,8 +401,75 @@ def kcenter_greedy(desc, labelled, budget):
     radius = torch.empty(budget, dtype=torch.float32, device=dev)
     mind = torch.empty(N, dtype=torch.float32, device=dev)
     ws = torch.empty(int(_C.lib.aod_kcenter_ws_len(N)), dtype=torch.uint8, device=dev)
-    call('aod_kcenter_greedy', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
+    if metric == 'sqeuclid':
+        call('aod_kcenter_greedy', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
+    else:
+        call('aod_kcenter_greedy_ex', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream(),
+             KCENTER_METRICS[metric])
     return picks, radius
+
+
+CDAL_MAX_CLASSES = 32      # 2 C^2 <= 2048 columns, the k-center kernels' LDS limit
+
+
+def cdal_descriptor(maps, n_cls, score_thr=0.3, out=None):
+    """CDAL class-mixture descriptor of every image of a batch (aod_cdal_descriptor; Agarwal et al., "Contextual Diversity for Active
+    Learning", ECCV 2020): [B, 2 * n_cls^2] fp32 = [P | ln P].  Per anchor row p = softmax(logits); a row is a region iff
+    max p > score_thr (strict), its class the argmax (lowest index on a tie), its weight H(p) + 2^-10; P[c] = (1 - 2^-10) * (the weighted
+    mean of p over the regions of class c, uniform where there is none) + 2^-10 / n_cls.
+
+    maps: 1..8 per-level fp32 device logit maps, either [B, A * n_cls, h, w] channels_last-dense as the head hands them out (the n_cls
+    logits of an anchor are then contiguous: nhwc_view's [B, A_l, n_cls] without a copy) or [B, rows, n_cls] contiguous.  n_cls <= 32.
+    out: a [B, D] fp32 device view with unit column stride (e.g. rows of the [N, D] pool matrix).  The bits of a row depend on its image
+    alone -- not on B or on its place in the batch.  No host sync."""
+    maps = list(maps)
+    L = len(maps)
+    if not 1 <= L <= 8:
+        raise ValueError(f'cdal_descriptor: 1..8 levels are supported, got {L}')
+    n_cls = int(n_cls)
+    if n_cls < 1:
+        raise ValueError(f'cdal_descriptor: n_cls must be positive, got {n_cls}')
+    if n_cls > CDAL_MAX_CLASSES:
+        raise ValueError(f'cdal_descriptor: up to {CDAL_MAX_CLASSES} classes are supported (2 * n_cls^2 <= 2048 descriptor columns, the k-center '
+                         f'kernels\' limit), got n_cls = {n_cls}')
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('cdal_descriptor: score_thr is NaN')
+    rows = []
+    for l, t in enumerate(maps):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in (3, 4):
+            raise ValueError(f'cdal_descriptor: level {l} is not an fp32 [B, A * n_cls, h, w] or [B, rows, n_cls] tensor')
+        if t.shape[0] != maps[0].shape[0] or t.numel() == 0:
+            raise ValueError(f'cdal_descriptor: level {l} has shape {tuple(t.shape)}, level 0 has {tuple(maps[0].shape)}: every level needs the '
+                             'same positive batch size')
+        if t.dim() == 3:
+            if t.shape[2] != n_cls:
+                raise ValueError(f'cdal_descriptor: level {l} has rows of {t.shape[2]} columns, not n_cls = {n_cls}')
+            dense = t.is_contiguous()
+        else:
+            if t.shape[1] % n_cls:
+                raise ValueError(f'cdal_descriptor: level {l} has {t.shape[1]} channels, not a multiple of n_cls = {n_cls}')
+            dense = t.permute(0, 2, 3, 1).is_contiguous()
+        if not dense:
+            raise ValueError(f'cdal_descriptor: level {l} is not dense with the classes of a row contiguous (channels_last for a 4-D map); no '
+                             'copy is made here')
+        rows.append(t.numel() // int(t.shape[0]) // n_cls)
+    B, D = int(maps[0].shape[0]), 2 * n_cls * n_cls
+    for t in maps:
+        if not t.is_cuda:
+            raise _C.AodHipError('cdal_descriptor needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    dev = maps[0].device
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, D) and out.stride(1) == 1
+              and out.stride(0) >= D):
+        raise ValueError(f'cdal_descriptor: out must be an fp32 device tensor of shape ({B}, {D}) with unit column stride')
+    sizes = (C.c_int64 * L)(*rows)
+    cap = int(_C.lib.aod_cdal_ws_len(L, sizes, n_cls, B))
+    ws = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    call('aod_cdal_descriptor', (C.c_void_p * L)(*[t.data_ptr() for t in maps]), L, sizes, n_cls, B, score_thr, ptr(out), out.stride(0), ptr(ws),
+         cap, stream())
+    return out
 
 
 def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes, scale_factors, cfg, rescale=False, with_nms=True,

@@ -661,6 +661,31 @@ size_t aod_kcenter_ws_len(int64_t N);
 int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
                        float* radius, float* mind, void* ws, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ CDAL acquisition: class-mixture descriptors and the symmetrised-KL
+ * k-center metric (csrc/cdal.hip, csrc/coreset.hip).  No reference call site: S. Agarwal, H. Arora, S. Anand, C. Arora, "Contextual
+ * Diversity for Active Learning", ECCV 2020, in its core-set form (CDAL-CS); the semantics are fixed in DESIGN 3j.
+ *   aod_cdal_descriptor: maps = L HOST-array device pointers (1..8 levels; they travel as kernel arguments), level l = fp32 [B][rows_l][C]
+ *     logits, the C classes of an anchor row contiguous (rows_per_level: HOST array), 1 <= C <= 32 (2 C^2 <= 2048 descriptor columns).
+ *     Per row: p = softmax(x) as exp(x - max) / sum; a region iff max p > score_thr (strict), its class the argmax (lowest index on a
+ *     tie), its weight w = H(p) + 2^-10 (0 ln 0 = 0).  Per image and class c: M[c] = sum w p / sum w over the regions of class c (1 / C
+ *     for a class without one), P[c] = (1 - 2^-10) M[c] + 2^-10 / C;  out[b * out_stride + ...] = [P (C * C) | ln P (C * C)].
+ *     Two launches (per-chunk partial accumulators into ws, then one workgroup per image and class), no atomics, no host sync; expf / log1pf /
+ *     logf.  The association of every sum depends on a row's index inside its own image only: an image has the same descriptor bits
+ *     alone, at any position of any batch, eager or replayed.  16-B loads where an image's base is 16-B aligned.
+ *     ws: aod_cdal_ws_len(L, rows_per_level, C, B) floats (0: bad shape), ws_capacity = the floats it holds; aod_cdal_chunk(): rows per
+ *     partial accumulator.
+ *   aod_kcenter_greedy_ex: aod_kcenter_greedy with a metric.  0: the squared Euclidean distance (the same arithmetic and bits as
+ *     aod_kcenter_greedy, which forwards here).  1: a row is [P | ln P], two halves of D / 2 columns (D even, else refused):
+ *       d(i, j) = 1/2 sum_k max((P_ik - P_jk)(ln P_ik - ln P_jk), 0), the symmetrised KL divergence summed over the classes;
+ *     the lane ownership, the four running sums per lane and the butterfly of metric 0 over the D / 2 columns of a half: a function of
+ *     the two rows and D alone.  Every term is non-negative, so the 64-bit keys order it as they order metric 0. */
+int aod_cdal_chunk(void);
+size_t aod_cdal_ws_len(int L, const int64_t* rows_per_level, int C, int B);
+int aod_cdal_descriptor(const void* const* maps, int L, const int64_t* rows_per_level, int C, int B, float score_thr, float* out,
+                        int64_t out_stride, float* ws, int64_t ws_capacity, aod_stream_t stream);
+int aod_kcenter_greedy_ex(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
+                          float* radius, float* mind, void* ws, aod_stream_t stream, int metric);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

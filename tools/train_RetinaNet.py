@@ -50,9 +50,11 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                                        'Lambda_L1Net | Lambda_MSLENet | Lambda_L2Net_ablation | Lambda_L2Net_NoL')
     p.add_argument('--uncertainty-pool', default=None,
                    help="pool scoring rule (default: the config's uncertainty_pool): Random | Entropy_NMS | Entropy_ALL | Entropy_Avg | Coreset "
-                        '(Entropy_Avg: Lambda_L2Net_NoL only; Coreset: k-center greedy on pooled pyramid descriptors, zeroRate off)')
+                        '| CDAL (Entropy_Avg: Lambda_L2Net_NoL only; Coreset: k-center greedy on pooled pyramid descriptors, zeroRate off; '
+                        'CDAL: k-center greedy on class-mixture descriptors under the symmetrised KL divergence, zeroRate off)')
     p.add_argument('--hua-score-thr', type=float, default=score_thr,
-                   help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
+                   help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL and, as the region '
+                        'threshold, by the CDAL pool')
     p.add_argument('--hua-iou-thr', type=float, default=iou_thr,
                    help='iou_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
     p.add_argument('--uncertainty', help='uncertainty type (accepted like the reference accepts it, tools/train_RetinaNet.py:56: never read there either)')
@@ -244,12 +246,12 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             data_loader = build_dataloader(dataset_al, samples_per_gpu=cfg.data.samples_per_gpu, workers_per_gpu=cfg.data.workers_per_gpu,
                                            dist=False, shuffle=False)
             poolModel = MMDataParallel(model, device_ids=cfg.gpu_ids)
-            # Coreset alone takes the labelled set (its initial centers) and selects by rank, not by score: its vector marks exactly
+            # Coreset and CDAL take the labelled set (their initial centers) and select by rank, not by score: their vector marks exactly
             # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
-            coreset = cfg.uncertainty_pool == 'Coreset'
+            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL')
             pool_kw = dict(X_L=X_L) if coreset else {}
             if coreset and zeroRate and cycle == cfg.cycles[0]:
-                logger.info(f'uncertainty_pool=Coreset: zeroRate {zeroRate} -> 0 (the picks are the selection)')
+                logger.info(f'uncertainty_pool={cfg.uncertainty_pool}: zeroRate {zeroRate} -> 0 (the picks are the selection)')
             with torch.no_grad():
                 uncertainty = calculate_uncertainty(cfg, poolModel, data_loader, return_box=False, showNMS=False, saveUnc=False,
                                                     saveMaxConf=saveMaxConf, clsW=clsW, scaleUnc=False, score_thr=args.hua_score_thr,
