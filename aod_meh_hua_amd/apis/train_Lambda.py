@@ -22,6 +22,7 @@ def RemoveParamFromOptim(optimizer, model, param_name):
 
 def build_optimizers(model, cfg):
     """The two optimizers of run_iter (train_Lambda.py:54-61): SGD over everything but the MEH parameters, and `optimizer_L` over those.
+    A head without `L_names` (the plain RetinaNet baseline) gets (optimizer, None).
     `optimizer_config.grad_clip` (mmcv OptimizerHook's argument; the hook itself is removed below, as in the reference) and
     `optimizer_config.skip_nonfinite` go to BOTH: each clips the parameter set it steps -- the main and the MEH step follow separate
     backward passes."""
@@ -30,7 +31,9 @@ def build_optimizers(model, cfg):
     module = model.module if hasattr(model, 'module') else model
     optimizer = build_optimizer(model, cfg.optimizer, **clip)
     head = module.bbox_head
-    meh_names = getattr(head, 'L_names', ['retina_L', 'L_convs'])      # train_Lambda.py:55-56 / train_SSD_L.py:42
+    if not hasattr(head, 'L_names'):      # no Model Evidence Head (MyRetinaHead): ONE optimizer over every parameter, no MEH step in run_iter
+        return optimizer, None
+    meh_names = head.L_names              # train_Lambda.py:55-56 / train_SSD_L.py:42
     for name in meh_names:
         RemoveParamFromOptim(optimizer, module, name)
     meh_params = [p for n in meh_names for p in getattr(head, n).parameters()]

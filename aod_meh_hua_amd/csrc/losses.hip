@@ -75,6 +75,35 @@ __device__ __forceinline__ float edl_row_fwd(const float* x, int n, int c0, long
   return grp_sum<LPR>(tot);
 }
 
+// FORM (compile-time, on the row cores and kernels below): what stands between the logits and mmcv's sigmoid focal term
+//   0  EDL    softmax -> log(p / (1 - p + 1e-9) + 1e-9) -> focal               EDL_Softmax_FocalLoss.py:51-69
+//   1  plain  the focal term on the raw logits, per class, no softmax          focal_loss.py:85 (FocalLoss of MyRetinaHead)
+// Both share the LDS staging, the lane split, the level table, the block partials and the finalize; the box term is the same code.
+constexpr int FORM_EDL = 0, FORM_SIGMOID = 1;
+
+// mmcv-full 1.3.8's sigmoid focal term on one logit (the reference's GPU path; FocalLoss at focal_loss.py:85): q = 1 / (1 + exp(-x)),
+// target class -alpha (1-q)^gamma log(max(q, FLT_MIN)), other classes -(1-alpha) q^gamma log(max(1-q, FLT_MIN)).  Not the softplus form:
+// q rounds to 0 / 1 at |x| >~ 17 and the clamp then bounds the term at -log(FLT_MIN) = 87.3, as in the reference.
+// gz (optional) = d l / d x with the clamps as written (mmcv's backward kernel).
+__device__ __forceinline__ float sig_focal_term(float x, bool pos, float gamma, float alpha, float* gz) {
+  const float q = l_div(1.f, 1.f + l_exp(-x));
+  const float lg = l_log(fmaxf(pos ? q : 1.f - q, FLT_MIN_F));
+  if (gz) {
+    if (pos) *gz = -alpha * focal_pow(1.f - q, gamma) * (1.f - q - gamma * q * lg);
+    else *gz = -(1.f - alpha) * focal_pow(q, gamma) * (gamma * (1.f - q) * lg - q);
+  }
+  return pos ? -alpha * focal_pow(1.f - q, gamma) * lg : -(1.f - alpha) * focal_pow(q, gamma) * lg;
+}
+
+// per-row forward core of the plain form: the row loss (a label of C, background, makes every column negative)
+template <int CT, int LPR>
+__device__ __forceinline__ float sig_row_fwd(const float* x, int n, int c0, long long label, float gamma, float alpha) {
+  float tot = 0.f;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) if (c < n) tot += sig_focal_term(x[c], label == c0 + c, gamma, alpha, nullptr);
+  return grp_sum<LPR>(tot);
+}
+
 // One launch over ALL pyramid levels (Lambda_L2.py:105-121 runs loss_single once per level through multi_apply): the levels' anchor rows are
 // adjacent row ranges of the same buffers (level-batched prediction convs, level-major targets), and a block belongs to exactly one level --
 // level l owns the blocks [blk_end[l-1], blk_end[l]) and the rows [row_end[l-1], row_end[l]), its blocks start at its first row.  Blocks, rows
@@ -100,7 +129,7 @@ static int fill_levels(LossLevels& lv, int nlevels, const int64_t* level_rows, i
   return (int)b;
 }
 
-template <int CT, int LPR>
+template <int FORM, int CT, int LPR>
 __global__ __launch_bounds__(LB) void edl_l1_fwd_kernel(const float* __restrict__ cls, const long long* __restrict__ labels,
                                                         const float* __restrict__ lw, const float* __restrict__ bp,
                                                         const float* __restrict__ bt, const float* __restrict__ bw, const LossLevels lv, int C,
@@ -125,7 +154,8 @@ __global__ __launch_bounds__(LB) void edl_l1_fwd_kernel(const float* __restrict_
     float x[CT], p[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) x[c] = c < n ? srow[row * P + c0 + c] : 0.f;
-    const float l = edl_row_fwd<CT, LPR>(x, n, c0, labels[r], gamma, alpha, p);
+    const float l = FORM == FORM_SIGMOID ? sig_row_fwd<CT, LPR>(x, n, c0, labels[r], gamma, alpha)
+                                         : edl_row_fwd<CT, LPR>(x, n, c0, labels[r], gamma, alpha, p);
     if (live && part == 0) {
       loss_noR[r] = l;
       s_nor = l;
@@ -210,24 +240,40 @@ static inline long long edl_blocks(int64_t nrows, int C) { const int rb = LB / e
 // (sized for the LPR = 4 form: 64 rows per block)
 extern "C" size_t aod_loss_partials_len(int64_t nrows) { return (size_t)((nrows + LB / 4 - 1) / (LB / 4)) * 3; }
 
-extern "C" int aod_edl_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
-                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
-                                    float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
+// (one body per entry pair: `form` picks the kernel instantiation, `nm` names the entry in the error text)
+#define AOD_FOCAL_FWD_(FORM_, LPR_)                                                                                                        \
+  hipLaunchKernelGGL((edl_l1_fwd_kernel<FORM_, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
+                     (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials)
+#define AOD_FOCAL_FWD()                                                                                                                    \
+  do {                                                                                                                                     \
+    if (form == FORM_SIGMOID) { if (C <= 24) AOD_FOCAL_FWD_(FORM_SIGMOID, 1); else AOD_FOCAL_FWD_(FORM_SIGMOID, 4); }                      \
+    else { if (C <= 24) AOD_FOCAL_FWD_(FORM_EDL, 1); else AOD_FOCAL_FWD_(FORM_EDL, 4); }                                                   \
+  } while (0)
+static int focal_l1_fwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                        const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, float* loss_noR,
+                        float* sums3, float* partials, aod_stream_t stream) {
+  AOD_CHECK_ARG(nrows >= 0, "%s: negative row count", nm);
   if (nrows == 0) return 0;
-  AOD_CHECK_ARG(cls && labels && label_w && loss_noR && sums3 && partials, "edl_fwd: null pointer");
-  AOD_CHECK_ARG(C >= 1 && C <= MAXC, "edl_fwd: C=%d out of range", C);
-  AOD_CHECK_ARG(!bbox_pred || (bbox_tgt && bbox_w), "edl_fwd: bbox_pred needs targets and weights");
+  AOD_CHECK_ARG(cls && labels && label_w && loss_noR && sums3 && partials, "%s: null pointer", nm);
+  AOD_CHECK_ARG(C >= 1 && C <= MAXC, "%s: C=%d out of range", nm, C);
+  AOD_CHECK_ARG(!bbox_pred || (bbox_tgt && bbox_w), "%s: bbox_pred needs targets and weights", nm);
   LossLevels lv; long long tot;
   const long long nb = fill_levels(lv, 1, &nrows, LB / edl_lpr(C), tot);
-  if (C <= 24)
-    hipLaunchKernelGGL((edl_l1_fwd_kernel<24, 1>), dim3((unsigned)nb), dim3(LB), (size_t)LB * (C | 1) * 4, (hipStream_t)stream, cls, (const long long*)labels,
-                       label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials);
-  else
-    hipLaunchKernelGGL((edl_l1_fwd_kernel<24, 4>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / 4) * (C | 1) * 4, (hipStream_t)stream, cls, (const long long*)labels,
-                       label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials);
+  AOD_FOCAL_FWD();
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nb, 3, sums3);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int aod_edl_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
+                                    float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
+  return focal_l1_fwd(FORM_EDL, "edl_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR, sums3, partials, stream);
+}
+extern "C" int aod_sigmoid_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                        const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
+                                        float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
+  return focal_l1_fwd(FORM_SIGMOID, "sigmoid_focal_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR, sums3,
+                      partials, stream);
 }
 
 extern "C" size_t aod_loss_levels_partials_len(int nlevels, const int64_t* level_rows) {
@@ -236,35 +282,49 @@ extern "C" size_t aod_loss_levels_partials_len(int nlevels, const int64_t* level
   return n;
 }
 
-extern "C" int aod_edl_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
-                                           const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
-                                           float alpha, float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
-                                           float* divisors, float* num_total, aod_stream_t stream) {
-  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "edl_levels_fwd: 1..8 levels");
-  AOD_CHECK_ARG(!num_pos || (num_images >= 1 && divisors), "edl_levels_fwd: num_pos needs the image count and a divisor buffer");
-  AOD_CHECK_ARG(cls && labels && label_w && loss_noR && sums && partials, "edl_levels_fwd: null pointer");
-  AOD_CHECK_ARG(C >= 1 && C <= MAXC, "edl_levels_fwd: C=%d out of range", C);
-  AOD_CHECK_ARG(!bbox_pred || (bbox_tgt && bbox_w), "edl_levels_fwd: bbox_pred needs targets and weights");
+static bool level_rows_ok(int nlevels, const int64_t* level_rows) {
+  for (int l = 0; l < nlevels; ++l) if (level_rows[l] < 0) return false;
+  return true;
+}
+static int focal_l1_levels_fwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                               const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                               float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images, float* divisors,
+                               float* num_total, aod_stream_t stream) {
+  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "%s: 1..8 levels", nm);
+  AOD_CHECK_ARG(level_rows_ok(nlevels, level_rows), "%s: negative row count", nm);
+  AOD_CHECK_ARG(!num_pos || (num_images >= 1 && divisors), "%s: num_pos needs the image count and a divisor buffer", nm);
+  AOD_CHECK_ARG(cls && labels && label_w && loss_noR && sums && partials, "%s: null pointer", nm);
+  AOD_CHECK_ARG(C >= 1 && C <= MAXC, "%s: C=%d out of range", nm, C);
+  AOD_CHECK_ARG(!bbox_pred || (bbox_tgt && bbox_w), "%s: bbox_pred needs targets and weights", nm);
   LossLevels lv; long long tot;
   const int nb = fill_levels(lv, nlevels, level_rows, LB / edl_lpr(C), tot);
-  if (nb) {
-    if (C <= 24)
-      hipLaunchKernelGGL((edl_l1_fwd_kernel<24, 1>), dim3((unsigned)nb), dim3(LB), (size_t)LB * (C | 1) * 4, (hipStream_t)stream, cls, (const long long*)labels,
-                         label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials);
-    else
-      hipLaunchKernelGGL((edl_l1_fwd_kernel<24, 4>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / 4) * (C | 1) * 4, (hipStream_t)stream, cls, (const long long*)labels,
-                         label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials);
-  }
+  if (nb) AOD_FOCAL_FWD();
   // sums[3][nlevels]: row 0 = sum l * w, row 1 = sum |d| * bw, row 2 = sum l, one column per level (an empty level: zeros)
   hipLaunchKernelGGL(reduce_partials_levels_kernel, dim3(nlevels), dim3(256), 0, (hipStream_t)stream, partials, lv, 3, sums, 1, nlevels, (const int*)num_pos,
                      num_images, divisors, num_total);
   AOD_LAUNCH_CHECK();
   return 0;
 }
+#undef AOD_FOCAL_FWD
+#undef AOD_FOCAL_FWD_
+extern "C" int aod_edl_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                           const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
+                                           float alpha, float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
+                                           float* divisors, float* num_total, aod_stream_t stream) {
+  return focal_l1_levels_fwd(FORM_EDL, "edl_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma, alpha, loss_noR,
+                             sums, partials, num_pos, num_images, divisors, num_total, stream);
+}
+extern "C" int aod_sigmoid_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                               const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
+                                               float alpha, float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
+                                               float* divisors, float* num_total, aod_stream_t stream) {
+  return focal_l1_levels_fwd(FORM_SIGMOID, "sigmoid_focal_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
+                             alpha, loss_noR, sums, partials, num_pos, num_images, divisors, num_total, stream);
+}
 
 // backward.  Output element (row r, class c) lives at (r / A) * pitch + (r % A) * C + c so that the
 // gradient lands directly in the conv's [pixels, A*C (padded)] dZ layout, bf16 or fp32.
-template <bool OUT_BF16, int CT, int LPR>
+template <int FORM, bool OUT_BF16, int CT, int LPR>
 __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict__ cls, const long long* __restrict__ labels,
                                                         const float* __restrict__ lw, const float* __restrict__ bp,
                                                         const float* __restrict__ bt, const float* __restrict__ bw, const LossLevels lv, int C,
@@ -295,44 +355,57 @@ __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict_
     float x[CT], p[CT], gp[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) x[c] = c < n ? srow[row * P + c0 + c] : 0.f;
-    float m = -INFINITY;
+    float m = -INFINITY, S = 0.f;
+    if (FORM == FORM_EDL) {
 #pragma unroll
-    for (int c = 0; c < CT; ++c) if (c < n) m = fmaxf(m, x[c]);
-    m = grp_max<LPR>(m);
-    float S = 0.f;
+      for (int c = 0; c < CT; ++c) if (c < n) m = fmaxf(m, x[c]);
+      m = grp_max<LPR>(m);
 #pragma unroll
-    for (int c = 0; c < CT; ++c) if (c < n) { p[c] = l_exp(x[c] - m); S += p[c]; }
-    S = grp_sum<LPR>(S);
+      for (int c = 0; c < CT; ++c) if (c < n) { p[c] = l_exp(x[c] - m); S += p[c]; }
+      S = grp_sum<LPR>(S);
+    }
     const long long label = labels[r];
     // (g_div: the upstream gradients are those of the DIVIDED sums -- the quotient is what autograd's division backward forms)
     const float gc_ = g_div ? g_cls[gl] / g_div[gl] : g_cls[gl];
     const float gn_ = g_noR ? (g_noR_bcast ? (g_div ? g_noR[gl] / g_div[2 * nlv + gl] : g_noR[gl]) : g_noR[r]) : g_noR_s;
     const float coef = gc_ * lw[r] + gn_;
     float dot = 0.f;
+    if (FORM == FORM_SIGMOID) {
+      // per class, no softmax Jacobian: d/dx_c = coef * d l_c / d x_c, back into the LDS row like the EDL form's below
+      if (live) {
 #pragma unroll
-    for (int c = 0; c < CT; ++c) if (c < n) {
-      const float pr = l_div(p[c], S);
-      p[c] = pr;
-      const float om = 1.f - pr + 1e-9f;
-      const float u = l_div(pr, om);
-      const float z = l_log(u + 1e-9f);
-      const float q = l_div(1.f, 1.f + l_exp(-z));
-      const bool pos = label == c0 + c;
-      const float lg = l_log(fmaxf(pos ? q : 1.f - q, FLT_MIN_F));
-      float gz;   // d l / d z  (mmcv sigmoid_focal_loss backward)
-      if (pos) gz = -alpha * focal_pow(1.f - q, gamma) * (1.f - q - gamma * q * lg);
-      else gz = -(1.f - alpha) * focal_pow(q, gamma) * (gamma * (1.f - q) * lg - q);
-      // dz/dp = (1+eps) / ((1-p+eps)^2 (u+eps))
-      const float g = l_div(coef * gz * (1.f + 1e-9f), om * om * (u + 1e-9f));
-      gp[c] = g;
-      dot += pr * g;
-    }
-    dot = grp_sum<LPR>(dot);
-    // the row's gradient goes back into its LDS row; the block then stores all rows with consecutive lanes on consecutive elements
-    // (one thread storing its own 20 values writes 4 B per lane at an 80-B lane stride)
-    if (live) {
+        for (int c = 0; c < CT; ++c) if (c < n) {
+          float gz;
+          sig_focal_term(x[c], label == c0 + c, gamma, alpha, &gz);
+          srow[row * P + c0 + c] = coef * gz;
+        }
+      }
+    } else {
 #pragma unroll
-      for (int c = 0; c < CT; ++c) if (c < n) srow[row * P + c0 + c] = p[c] * (gp[c] - dot);
+      for (int c = 0; c < CT; ++c) if (c < n) {
+        const float pr = l_div(p[c], S);
+        p[c] = pr;
+        const float om = 1.f - pr + 1e-9f;
+        const float u = l_div(pr, om);
+        const float z = l_log(u + 1e-9f);
+        const float q = l_div(1.f, 1.f + l_exp(-z));
+        const bool pos = label == c0 + c;
+        const float lg = l_log(fmaxf(pos ? q : 1.f - q, FLT_MIN_F));
+        float gz;   // d l / d z  (mmcv sigmoid_focal_loss backward)
+        if (pos) gz = -alpha * focal_pow(1.f - q, gamma) * (1.f - q - gamma * q * lg);
+        else gz = -(1.f - alpha) * focal_pow(q, gamma) * (gamma * (1.f - q) * lg - q);
+        // dz/dp = (1+eps) / ((1-p+eps)^2 (u+eps))
+        const float g = l_div(coef * gz * (1.f + 1e-9f), om * om * (u + 1e-9f));
+        gp[c] = g;
+        dot += pr * g;
+      }
+      dot = grp_sum<LPR>(dot);
+      // the row's gradient goes back into its LDS row; the block then stores all rows with consecutive lanes on consecutive elements
+      // (one thread storing its own 20 values writes 4 B per lane at an 80-B lane stride)
+      if (live) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) if (c < n) srow[row * P + c0 + c] = p[c] * (gp[c] - dot);
+      }
     }
     if (live && part == 0 && bp && grad_bbox) {
       const float gb = g_div ? g_bbox[gl] / g_div[nlv + gl] : g_bbox[gl];
@@ -361,39 +434,63 @@ __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict_
   }
 }
 
-extern "C" int aod_edl_focal_l1_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
-                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
-                                    const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
-                                    void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+#define AOD_FOCAL_BWD_(FORM_, BF, LPR_)                                                                                                    \
+  hipLaunchKernelGGL((edl_l1_bwd_kernel<FORM_, BF, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
+                     (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, g_cls, g_bbox, g_noR, \
+                     g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, A, pitch_cls, pitch_box, g_lstride, g_div, nlv_)
+#define AOD_FOCAL_BWD_F(FORM_)                                                                                                             \
+  do {                                                                                                                                     \
+    if (out_bf16) { if (C <= 24) AOD_FOCAL_BWD_(FORM_, true, 1); else AOD_FOCAL_BWD_(FORM_, true, 4); }                                    \
+    else { if (C <= 24) AOD_FOCAL_BWD_(FORM_, false, 1); else AOD_FOCAL_BWD_(FORM_, false, 4); }                                           \
+  } while (0)
+#define AOD_FOCAL_BWD()                                                                                                                    \
+  do {                                                                                                                                     \
+    if (form == FORM_SIGMOID) AOD_FOCAL_BWD_F(FORM_SIGMOID); else AOD_FOCAL_BWD_F(FORM_EDL);                                               \
+  } while (0)
+static int focal_l1_bwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                        const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, const float* g_cls,
+                        const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar, void* grad_cls, void* grad_bbox,
+                        int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  AOD_CHECK_ARG(nrows >= 0, "%s: negative row count", nm);
   if (nrows == 0) return 0;
-  AOD_CHECK_ARG(cls && labels && label_w && g_cls && grad_cls, "edl_bwd: null pointer");
-  AOD_CHECK_ARG(C >= 1 && C <= MAXC && A >= 1 && pitch_cls >= A * C, "edl_bwd: bad C/A/pitch");
-  AOD_CHECK_ARG(!grad_bbox || (bbox_pred && bbox_tgt && bbox_w && g_bbox && pitch_box >= A * 4), "edl_bwd: bbox args");
+  AOD_CHECK_ARG(cls && labels && label_w && g_cls && grad_cls, "%s: null pointer", nm);
+  AOD_CHECK_ARG(C >= 1 && C <= MAXC && A >= 1 && pitch_cls >= A * C, "%s: bad C/A/pitch", nm);
+  AOD_CHECK_ARG(!grad_bbox || (bbox_pred && bbox_tgt && bbox_w && g_bbox && pitch_box >= A * 4), "%s: bbox args", nm);
   LossLevels lv; long long tot;
   const long long nb = fill_levels(lv, 1, &nrows, LB / edl_lpr(C), tot);
   const int g_lstride = 0, nlv_ = 1;
   const float* const g_div = nullptr;
-#define AOD_EDL_BWD(BF, LPR_)                                                                                                              \
-  hipLaunchKernelGGL((edl_l1_bwd_kernel<BF, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
-                     (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, g_cls, g_bbox, g_noR, \
-                     g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, A, pitch_cls, pitch_box, g_lstride, g_div, nlv_)
-  if (out_bf16) { if (C <= 24) AOD_EDL_BWD(true, 1); else AOD_EDL_BWD(true, 4); }
-  else { if (C <= 24) AOD_EDL_BWD(false, 1); else AOD_EDL_BWD(false, 4); }
+  AOD_FOCAL_BWD();
   AOD_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int aod_edl_focal_l1_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
+                                    const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
+                                    void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  return focal_l1_bwd(FORM_EDL, "edl_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR, g_noR_scalar,
+                      g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+}
+extern "C" int aod_sigmoid_focal_l1_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                        const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
+                                        const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
+                                        void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  return focal_l1_bwd(FORM_SIGMOID, "sigmoid_focal_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR,
+                      g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 
 // g_sums[3][nlevels] = the gradients of aod_edl_focal_l1_levels_fwd's sums (row 0: classification sums, row 1: box sums, row 2: row sums) --
 // of the DIVIDED sums when `divisors` (the forward's) is given: the kernel forms g / divisor itself;
 // g_noR_rows (optional): a gradient per anchor row of loss_noR, replaces row 2.
-extern "C" int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
-                                           const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
-                                           float alpha, const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls,
-                                           void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
-  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "edl_levels_bwd: 1..8 levels");
-  AOD_CHECK_ARG(cls && labels && label_w && g_sums && grad_cls, "edl_levels_bwd: null pointer");
-  AOD_CHECK_ARG(C >= 1 && C <= MAXC && A >= 1 && pitch_cls >= A * C, "edl_levels_bwd: bad C/A/pitch");
-  AOD_CHECK_ARG(!grad_bbox || (bbox_pred && bbox_tgt && bbox_w && pitch_box >= A * 4), "edl_levels_bwd: bbox args");
+static int focal_l1_levels_bwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                               const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                               const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox, int out_bf16,
+                               int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  AOD_CHECK_ARG(nlevels >= 1 && nlevels <= MAXLV && level_rows, "%s: 1..8 levels", nm);
+  AOD_CHECK_ARG(level_rows_ok(nlevels, level_rows), "%s: negative row count", nm);
+  AOD_CHECK_ARG(cls && labels && label_w && g_sums && grad_cls, "%s: null pointer", nm);
+  AOD_CHECK_ARG(C >= 1 && C <= MAXC && A >= 1 && pitch_cls >= A * C, "%s: bad C/A/pitch", nm);
+  AOD_CHECK_ARG(!grad_bbox || (bbox_pred && bbox_tgt && bbox_w && pitch_box >= A * 4), "%s: bbox args", nm);
   LossLevels lv; long long tot;
   const int nb = fill_levels(lv, nlevels, level_rows, LB / edl_lpr(C), tot);
   if (nb == 0) return 0;
@@ -401,11 +498,26 @@ extern "C" int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labe
   const float* g_noR = g_noR_rows ? g_noR_rows : g_sums + 2 * nlevels;
   const float g_noR_scalar = 0.f; const int g_noR_is_scalar = g_noR_rows ? 0 : 1, g_lstride = 1, nlv_ = nlevels;
   const float* const g_div = divisors;
-  if (out_bf16) { if (C <= 24) AOD_EDL_BWD(true, 1); else AOD_EDL_BWD(true, 4); }
-  else { if (C <= 24) AOD_EDL_BWD(false, 1); else AOD_EDL_BWD(false, 4); }
-#undef AOD_EDL_BWD
+  AOD_FOCAL_BWD();
   AOD_LAUNCH_CHECK();
   return 0;
+}
+#undef AOD_FOCAL_BWD
+#undef AOD_FOCAL_BWD_F
+#undef AOD_FOCAL_BWD_
+extern "C" int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                           const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
+                                           float alpha, const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls,
+                                           void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  return focal_l1_levels_bwd(FORM_EDL, "edl_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma, alpha, g_sums,
+                             divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+}
+extern "C" int aod_sigmoid_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                               const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
+                                               float alpha, const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls,
+                                               void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  return focal_l1_levels_bwd(FORM_SIGMOID, "sigmoid_focal_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
+                             alpha, g_sums, divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 
 // ---------------------------------------------------------------- MEH loss
@@ -566,11 +678,21 @@ __device__ __forceinline__ float edl_elem_terms(float pr, bool pos, float gamma,
   return pos ? -alpha * focal_pow(1.f - q, gamma) * lg : -(1.f - alpha) * focal_pow(q, gamma) * lg;
 }
 
+template <int FORM>
 __global__ __launch_bounds__(256) void edl_elem_kernel(const float* __restrict__ cls, const long long* __restrict__ labels, long long nrows, int C,
                                                       float gamma, float alpha, const float* __restrict__ g, float* __restrict__ out) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= nrows) return;
   const float* x = cls + r * C;
+  if (FORM == FORM_SIGMOID) {      // per class: out[r][c] = l_c (forward) or g[r][c] * d l_c / d x_c (backward)
+    const long long label = labels[r];
+    for (int c = 0; c < C; ++c) {
+      float gz;
+      const float l = sig_focal_term(x[c], label == c, gamma, alpha, g ? &gz : nullptr);
+      out[r * C + c] = g ? g[r * C + c] * gz : l;
+    }
+    return;
+  }
   float m = -INFINITY;
   for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
   float S = 0.f;
@@ -601,8 +723,21 @@ extern "C" int aod_edl_focal_elem(const float* cls, const int64_t* labels, int64
   if (nrows == 0) return 0;
   AOD_CHECK_ARG(cls && labels && out, "edl_elem: null pointer");
   AOD_CHECK_ARG(C >= 1, "edl_elem: C=%d out of range", C);
-  hipLaunchKernelGGL(edl_elem_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cls, (const long long*)labels,
+  hipLaunchKernelGGL(edl_elem_kernel<FORM_EDL>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cls, (const long long*)labels,
                      (long long)nrows, C, gamma, alpha, grad_out, out);
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+
+// the plain form's [rows, C] loss: FocalLoss.forward(reduction='none') (focal_loss.py:85 -> mmcv sigmoid_focal_loss(..., 'none'))
+extern "C" int aod_sigmoid_focal_elem(const float* cls, const int64_t* labels, int64_t nrows, int C, float gamma, float alpha,
+                                      const float* grad_out, float* out, aod_stream_t stream) {
+  AOD_CHECK_ARG(nrows >= 0, "sigmoid_focal_elem: negative row count");
+  if (nrows == 0) return 0;
+  AOD_CHECK_ARG(cls && labels && out, "sigmoid_focal_elem: null pointer");
+  AOD_CHECK_ARG(C >= 1 && C <= MAXC, "sigmoid_focal_elem: C=%d out of range", C);
+  hipLaunchKernelGGL(edl_elem_kernel<FORM_SIGMOID>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cls,
+                     (const long long*)labels, (long long)nrows, C, gamma, alpha, grad_out, out);
   AOD_LAUNCH_CHECK();
   return 0;
 }

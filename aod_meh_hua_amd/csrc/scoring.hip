@@ -62,6 +62,16 @@ __device__ __forceinline__ void row_scores(const float* __restrict__ x, int C, f
   for (int c = 0; c < CT; ++c) if (c < C) { s[c] = s[c] / den; max_score = fmaxf(max_score, s[c]); }
 }
 
+// sigmoid rows (the plain RetinaNet baseline, anchor_head.py:535-553 with use_sigmoid_cls): s_c = 1 / (1 + exp(-x_c)) per class, no sum;
+// both maxima run over all C columns.  Selected by has_bg == 2 in the row-max kernels and by normalize == 3 in the gather.
+template <int CT>
+__device__ __forceinline__ void row_scores_sigmoid(const float* __restrict__ x, int C, float* s, float& max_alpha, float& max_score) {
+  max_score = 0.f;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) if (c < C) { s[c] = 1.0f / (1.0f + expf(-x[c])); max_score = fmaxf(max_score, s[c]); }
+  max_alpha = max_score;
+}
+
 // ---------------------------------------------------------------- S1: row max of normalised scores + level gate
 template <int CT>
 __device__ __forceinline__ void rowmax_block(const float* __restrict__ cls, long long rows_per_img, int b, int bx, int C, float fg_thr,
@@ -77,7 +87,8 @@ __device__ __forceinline__ void rowmax_block(const float* __restrict__ cls, long
     float x[CT], s[CT], ma, ms;
 #pragma unroll
     for (int c = 0; c < CT; ++c) x[c] = c < C ? srow[threadIdx.x * P + c] : 0.f;
-    if (has_bg) row_scores_bg<CT>(x, C, s, ma, ms); else row_scores<CT>(x, C, s, ma, ms);
+    if (has_bg == 2) row_scores_sigmoid<CT>(x, C, s, ma, ms);
+    else if (has_bg) row_scores_bg<CT>(x, C, s, ma, ms); else row_scores<CT>(x, C, s, ma, ms);
     rowmax[(long long)b * rows_per_img + r0 + threadIdx.x] = ms;
     fg = ma > fg_thr;
   }
@@ -94,6 +105,7 @@ extern "C" int aod_softmax_rowmax(const float* cls, int B, int64_t rows_per_img,
                                   int has_bg, aod_stream_t stream) {
   if (B == 0 || rows_per_img == 0) return 0;
   AOD_CHECK_ARG(cls && rowmax && any_fg && C >= 1 && C <= MAXC, "softmax_rowmax: bad args");
+  AOD_CHECK_ARG(has_bg >= 0 && has_bg <= 2, "softmax_rowmax: has_bg must be 0, 1 (last column is background) or 2 (sigmoid rows)");
   dim3 grid((unsigned)((rows_per_img + 255) / 256), B);
   if (C <= 24)
     hipLaunchKernelGGL(softmax_rowmax_kernel<24>, grid, dim3(256), (size_t)256 * (C | 1) * 4, (hipStream_t)stream, cls, (long long)rows_per_img, B, C,
@@ -313,7 +325,8 @@ __device__ __forceinline__ void gather_one(const GatherArgs& p, int b, int j, lo
   float x[CT], s[CT], ma, ms;
 #pragma unroll
   for (int c = 0; c < CT; ++c) x[c] = c < p.C ? p.cls[row * p.C + c] : 0.f;
-  if (p.normalize == 2) row_scores_bg<CT>(x, p.C, s, ma, ms); else row_scores<CT>(x, p.C, s, ma, ms);
+  if (p.normalize == 3) row_scores_sigmoid<CT>(x, p.C, s, ma, ms);
+  else if (p.normalize == 2) row_scores_bg<CT>(x, p.C, s, ma, ms); else row_scores<CT>(x, p.C, s, ma, ms);
   if (p.normalize == 0) {   // raw softmax: undo nothing, recompute without the (S + 1e-20 + 1e-9) division
     float m = x[0];
 #pragma unroll
@@ -372,6 +385,7 @@ extern "C" int aod_gather_decode(const float* cls, const float* reg, const float
                                  int32_t* cand_anchor, int64_t n_total, int64_t cand0, int64_t anchor0, int normalize, aod_stream_t stream) {
   if (B == 0 || k == 0) return 0;
   AOD_CHECK_ARG(cls && reg && lam_map && anchors && img_hw && boxes && scores && lam && cand_anchor && C <= MAXC, "gather_decode: bad args");
+  AOD_CHECK_ARG(normalize >= 0 && normalize <= 3, "gather_decode: normalize must be 0..3");
   GatherArgs p;
   p.cls = cls; p.reg = reg; p.lam_map = lam_map; p.anchors = anchors; p.idx = idx; p.B = B; p.A = A; p.k = k; p.C = C; p.idx_pitch = idx_pitch;
   p.img_hw = img_hw; p.scale4 = scale4;
@@ -431,6 +445,7 @@ extern "C" int aod_pre_nms_levels(int L, const float* const* cls, const float* c
   if (B == 0 || L == 0) return 0;
   AOD_CHECK_ARG(L >= 1 && L <= MAXL && cls && reg && lam_map && anchors && A && k && C >= 1 && C <= MAXC, "pre_nms_levels: bad args");
   AOD_CHECK_ARG(img_hw && rowmax && any_fg && boxes && scores && lam && cand_anchor, "pre_nms_levels: null pointer");
+  AOD_CHECK_ARG(normalize >= 0 && normalize <= 3 && !(normalize == 3 && has_bg), "pre_nms_levels: normalize must be 0..3 (3 = sigmoid: no background column)");
   LevelsArgs p;
   memset(&p, 0, sizeof(p));
   long long a0 = 0, c0 = 0, i0 = 0, amax = 0;
@@ -449,7 +464,7 @@ extern "C" int aod_pre_nms_levels(int L, const float* const* cls, const float* c
   }
   p.blk0[L] = nb;
   AOD_CHECK_ARG(c0 == n_total, "pre_nms_levels: n_total must be the sum of k");
-  p.L = L; p.B = B; p.C = C; p.has_bg = has_bg; p.normalize = normalize; p.fg_thr = fg_thr; p.any_fg = any_fg;
+  p.L = L; p.B = B; p.C = C; p.has_bg = normalize == 3 ? 2 : has_bg; p.normalize = normalize; p.fg_thr = fg_thr; p.any_fg = any_fg;
   p.cache_n = (int)(amax < 36864 ? amax : 36864);
   GatherArgs& g = p.g;
   g.B = B; g.C = C; g.idx = nullptr; g.idx_pitch = 0; g.img_hw = img_hw; g.scale4 = scale4;

@@ -62,13 +62,16 @@ class GraphedTrainStep:
     registration): parameters, momentum buffers and BN buffers are snapshotted before and restored after, so the batch that triggers a
     capture is applied exactly ONCE (by the first replay), like every other batch.  Under data parallelism gradients live in the static
     slices of GradSync's flat buffer and the all-reduces run eagerly between the captured segments; building a graph issues NO collective
-    (warm-up runs without communication), so capture / replay / eager are interchangeable per rank and per iteration."""
+    (warm-up runs without communication), so capture / replay / eager are interchangeable per rank and per iteration.
+    optimizer_L=None (a detector without a Model Evidence Head: MyRetinaNet, one optimizer): segments a and c only, single process only."""
     MAX_GRAPHS = 16
 
     def __init__(self, model, optimizer, optimizer_L, grad_sync=None, gmax=64, warmup=2, **step_kwargs):
         self.model, self.module = model, _unwrap(model)
         self.opt, self.opt_L, self.sync = optimizer, optimizer_L, grad_sync
         self.gmax, self.warmup, self.kw = gmax, warmup, step_kwargs
+        if optimizer_L is None and grad_sync is not None:
+            raise NotImplementedError('graph replay of the one-optimizer iteration is built for a single process; under data parallelism it runs eagerly')
         self.cache = {}                   # signature -> dict(graphs, static, live, live_L, keep, src, src_L), insertion order = LRU
         self.cur = None
         self.last_sig = None              # signature of the previous call to maybe()
@@ -178,12 +181,17 @@ class GraphedTrainStep:
         self.opt_L.step()
 
     def _params(self, opt):
-        return [p for g in opt.param_groups for p in g['params']]
+        return [] if opt is None else [p for g in opt.param_groups for p in g['params']]
+
+    def _opts(self):
+        return [o for o in (self.opt, self.opt_L) if o is not None]
 
     def _segments(self, dist_mode):
         """(tag, callable) in execution order.  One process: everything is ONE graph.  Data parallelism: a0 (forward + heads / neck
         backward), a1 .. aK (backbone stages, deepest first), b (MEH forward / backward), c, d (the two SGD steps) are graphs of their
         own with the eager bucket all-reduces between them."""
+        if self.opt_L is None:
+            return [('a', self._seg_a), ('c', self._seg_c)]
         if not dist_mode:
             return [('a', self._seg_a), ('b', self._seg_b), ('c', self._seg_c), ('d', self._seg_d)]
         segs = [('a0', lambda: self._seg_a(cuts=True))]
@@ -241,7 +249,7 @@ class GraphedTrainStep:
     def _snapshot(self):
         ps = self._params(self.opt) + self._params(self.opt_L)
         snap = dict(p=[p.detach().clone() for p in ps], m=[], b=[b.detach().clone() for b in self.module.buffers()])
-        for opt in (self.opt, self.opt_L):
+        for opt in self._opts():
             for p in self._params(opt):
                 mb = opt.state.get(p, {}).get('momentum_buffer')
                 snap['m'].append(None if mb is None else mb.detach().clone())
@@ -254,7 +262,7 @@ class GraphedTrainStep:
             for b, v in zip(self.module.buffers(), snap['b']):
                 b.copy_(v)
             i = 0
-            for opt in (self.opt, self.opt_L):
+            for opt in self._opts():
                 for p in self._params(opt):
                     mb = opt.state.get(p, {}).get('momentum_buffer')
                     if mb is not None:
@@ -273,7 +281,8 @@ class GraphedTrainStep:
             self.sync.attach(self._params(self.opt_L))
         self.cur = dict(static=self._alloc(d), live=None, live_L=None, loaded=True)
         self._load(d)
-        self.opt.device_lr(), self.opt_L.device_lr()
+        for opt in self._opts():
+            opt.device_lr()
         self.module.train()
         snap = self._snapshot()
         side = torch.cuda.Stream()
@@ -340,7 +349,8 @@ class GraphedTrainStep:
         self.cache[sig] = self.cur = ent
         if not ent.pop('loaded', False):          # (a capture has just loaded this batch: the graphs only read their static inputs)
             self._load(d)
-        self.opt.device_lr(), self.opt_L.device_lr()
+        for opt in self._opts():
+            opt.device_lr()
         AF.PREP.refresh_if_stale()
         self.inflight = []
         for i, g in enumerate(ent['graphs']):
@@ -351,9 +361,10 @@ class GraphedTrainStep:
         torch._C._autograd._unsafe_set_version_counter(tp, [p._version + 1 for p in tp])
         out, loss_L = ent['live'][0], ent['live_L']
         # static tensors: hand out copies (two device copies: the packed vectors of segments A and B)
-        pa, pb = self.cur['pack'].clone(), self.cur['pack_L'].clone()
+        pa = self.cur['pack'].clone()
         log_vars = type(out['log_vars'])(zip(out['log_vars'].keys(), pa[1:].unbind(0)))
-        log_vars.update(zip(loss_L['log_vars'].keys(), pb.unbind(0)))
+        if loss_L is not None:
+            log_vars.update(zip(loss_L['log_vars'].keys(), self.cur['pack_L'].clone().unbind(0)))
         return dict(loss=pa[0], log_vars=log_vars, num_samples=out['num_samples'])
 
 

@@ -124,6 +124,9 @@ class Lambda_L2Net(L_AnchorHead):
     _hua_lam = 'scaled'          # 'scaled': alpha = score * mean(lambda) / (lambda + 1e-7) * 25; 'none': alpha = score
     _hua_thr_kwargs = False      # True: the score_thr / iou_thr kwargs replace HUA's 0.3 / 0.5 (this head ignores them, as its reference does)
     _hua_entropy_avg = False     # True: uncertainty_pool = 'Entropy_Avg' is offered
+    # what the plain RetinaNet baseline head changes (models/dense_heads/MyRetinaHead.py borrows loss_single / loss_all_levels below):
+    _focal_form = 'edl'          # focal form of the fused loss launches: 'edl' | 'sigmoid' (hipops.FOCAL_FORMS)
+    _loss_cls_type = 'EDL_Softmax_FocalLoss'
 
     @force_fp32(apply_to=('cls_score', 'bbox_pred'))
     def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights, sIdx, num_total_samples, **kwargs):
@@ -131,10 +134,10 @@ class Lambda_L2Net(L_AnchorHead):
         entered by the AL driver (SURVEY 3.2 iv) and is not built."""
         if not (kwargs.get('Labeled', True) and not kwargs.get('Pseudo', False)):
             raise NotImplementedError('pseudo-label branch (Lambda_L2.py:122-232) is dead code in the reference driver')
-        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == 'EDL_Softmax_FocalLoss'
+        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == self._loss_cls_type
         sum_cls, sum_box, loss_noR, sum_noR = AF.RetinaLossFn.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
                                                                     float(self.loss_cls.gamma), float(self.loss_cls.alpha), self.cls_out_channels,
-                                                                    kwargs.get('grad_arena'), int(sIdx))
+                                                                    kwargs.get('grad_arena'), int(sIdx), self._focal_form)
         wc, wb = self.loss_cls.loss_weight, self.loss_bbox.loss_weight
         scaled = lambda w, t: t if w == 1.0 else w * t          # (1.0 * t == t exactly: no launch for the default weights)
         if kwargs.get('defer_avg'):                               # loss() divides all levels by their counts in one launch
@@ -152,7 +155,7 @@ class Lambda_L2Net(L_AnchorHead):
             raise NotImplementedError('pseudo-label branch (Lambda_L2.py:122-232) is dead code in the reference driver')
         if self.loss_cls.loss_weight != 1.0 or self.loss_bbox.loss_weight != 1.0:
             return None
-        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == 'EDL_Softmax_FocalLoss'
+        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == self._loss_cls_type
         C = self.cls_out_channels
         cls_d, box_d = AF.dense_levels(cls_scores), AF.dense_levels(bbox_preds)
         flat = [AF.dense_concat([t.reshape(-1, *t.shape[2:]) for t in ts]) for ts in (labels_list, lw_list, bt_list, bw_list)]
@@ -162,7 +165,7 @@ class Lambda_L2Net(L_AnchorHead):
         level_rows = [c.shape[0] * c.shape[2] * c.shape[3] * A for c in cls_scores]
         out = AF.RetinaLossLevelsFn.apply(cls_d.view(-1, C), box_d.view(-1, 4), flat[0], flat[1], flat[2], flat[3],
                                           float(self.loss_cls.gamma), float(self.loss_cls.alpha), level_rows,
-                                          (A, cls_d.shape[1], box_d.shape[1]), num_pos)
+                                          (A, cls_d.shape[1], box_d.shape[1]), num_pos, self._focal_form)
         return (out[0], list(out[1].split(level_rows))) + tuple(out[2:])
 
     def loss_all_levels_L(self, L_scores, losses, bw_list, **kwargs):

@@ -1,5 +1,6 @@
 """SSL_L_SingleStageDetector / SSL_L_RetinaNet / SSD_L_SingleStageDetector plugins
-(mmdet/models/detectors/SSL_L_single_stage.py:10-98, SSL_L_retinanet.py, SSD_L_single_stage.py)."""
+(mmdet/models/detectors/SSL_L_single_stage.py:10-98, SSL_L_retinanet.py, SSD_L_single_stage.py) and the plain baseline detectors
+MyRetinaSingleStageDetector / MyRetinaNet (MyRetinaSingleStage.py:10-75, MyRetinanet.py)."""
 import warnings
 
 from ...core.bbox import bbox2result, unc2result
@@ -98,3 +99,28 @@ class SSD_L_SingleStageDetector(SSL_L_SingleStageDetector):
     def _just_feat(self, img):
         raise NotImplementedError('justFeat / Core-set descriptors are built for the FPN pyramid of the RetinaNet detectors, not for SSD '
                                   '(its six source maps have different channel counts and do not lie in one row buffer)')
+
+
+@DETECTORS.register_module()
+class MyRetinaSingleStageDetector(SSL_L_SingleStageDetector):
+    """mmdet/models/detectors/MyRetinaSingleStage.py:10-75: the plain single-stage detector of the baselines (MyRetinaHead: no Model
+    Evidence Head).  On SSLBase_L_Detector -- MyRetinaBase._parse_losses (MyRetinaBase.py:128-156) is the base's, `loss_noR` in the total
+    included, and train_step returns the same 4-tuple -- with the control flow of SSL_L_SingleStageDetector: justOut (the classification
+    maps of an ensemble member), justFeat, _padded, isUnc=False and mc_dropout are honoured there.  What it does not have is lambda: the
+    HUA pools and detUnc raise before anything is launched, and there is no MEH step (train_step_L)."""
+
+    def simple_test(self, img, img_metas, rescale=False, **kwargs):
+        from ...scoring import refuse_hua
+        refuse_hua(self.bbox_head, **kwargs)
+        return super().simple_test(img, img_metas, rescale=rescale, **kwargs)
+
+    def forward_train_L(self, loss, head_out, feat_out, **kwargs):
+        raise ValueError(f'{type(self.bbox_head).__name__} has no lambda (no Model Evidence Head): there is no MEH step to train')
+
+
+@DETECTORS.register_module()
+class MyRetinaNet(MyRetinaSingleStageDetector):
+    """mmdet/models/detectors/MyRetinanet.py."""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

@@ -101,7 +101,12 @@ class Candidates:
 
 
 def pre_nms(mlvl_cls, mlvl_reg, mlvl_L, mlvl_anchors, img_shapes, scale_factors, nms_pre, C_, means, stds, rescale=True,
-            fg_thr=0.3, wh_ratio_clip=16 / 1000, normalize=True, has_bg=False):
+            fg_thr=0.3, wh_ratio_clip=16 / 1000, normalize=True, has_bg=False, activation=None):
+    """activation='sigmoid' (the plain RetinaNet baseline, anchor_head.py:535-553): mode 3 of the kernels -- s_c = 1 / (1 + exp(-x_c)) per
+    class, the row key is the maximum over all C columns, C score columns (+ the zero background column) are written."""
+    assert activation in (None, 'sigmoid') and not (activation == 'sigmoid' and has_bg)
+    mode = 3 if activation == 'sigmoid' else (2 if has_bg else int(bool(normalize)))
+    row_mode = 2 if activation == 'sigmoid' else int(has_bg)      # the row-max kernels: 0 EDL-normalised, 1 last column is background, 2 sigmoid
     dev = mlvl_cls[0].device
     B = mlvl_cls[0].shape[0]
     L = len(mlvl_cls)
@@ -129,7 +134,7 @@ def pre_nms(mlvl_cls, mlvl_reg, mlvl_L, mlvl_anchors, img_shapes, scale_factors,
         PA = C.c_void_p * L
         call('aod_pre_nms_levels', L, PA(*[ptr(t).value for t in cls]), PA(*[ptr(t).value for t in reg]), PA(*[ptr(t).value for t in lam]),
              PA(*[ptr(t).value for t in anch]), (C.c_int64 * L)(*A), (C.c_int32 * L)(*ks), B, C_, fg_thr, int(has_bg),
-             2 if has_bg else int(bool(normalize)), ptr(img_hw), ptr(sc4), _F4(*means), _F4(*stds), float(wh_ratio_clip), ptr(rm), ptr(any_fg),
+             mode, ptr(img_hw), ptr(sc4), _F4(*means), _F4(*stds), float(wh_ratio_clip), ptr(rm), ptr(any_fg),
              ptr(ix), ptr(boxes), ptr(scores), ptr(lam_o), ptr(cand_anchor), n, stream())
         rowmaxes, idxs, r0, i0 = [], [], 0, 0
         for l in range(L):
@@ -147,7 +152,7 @@ def pre_nms(mlvl_cls, mlvl_reg, mlvl_L, mlvl_anchors, img_shapes, scale_factors,
         rowmax = torch.empty(B, A[l], device=dev)
         from .hipops import prof_bytes
         prof_bytes('softmax_rowmax', B * A[l] * (C_ * 4 + 4),
-                   lambda: call('aod_softmax_rowmax', ptr(cls[l]), B, A[l], C_, fg_thr, ptr(rowmax), ptr(any_fg[l]), int(has_bg), stream()))
+                   lambda: call('aod_softmax_rowmax', ptr(cls[l]), B, A[l], C_, fg_thr, ptr(rowmax), ptr(any_fg[l]), row_mode, stream()))
         idx = None
         if ks[l] < A[l]:
             idx = torch.empty(B, ks[l], dtype=torch.int32, device=dev)
@@ -156,7 +161,7 @@ def pre_nms(mlvl_cls, mlvl_reg, mlvl_L, mlvl_anchors, img_shapes, scale_factors,
         rowmaxes.append(rowmax)
         call('aod_gather_decode', ptr(cls[l]), ptr(reg[l]), ptr(lam[l]), ptr(mlvl_anchors[l].contiguous()), ptr(idx), B, A[l], ks[l], C_,
              ks[l], ptr(img_hw), ptr(sc4), _F4(*means), _F4(*stds), float(wh_ratio_clip), ptr(boxes), ptr(scores), ptr(lam_o),
-             ptr(cand_anchor), n, c0, a0, 2 if has_bg else int(bool(normalize)), stream())
+             ptr(cand_anchor), n, c0, a0, mode, stream())
         c0 += ks[l]
         a0 += A[l]
     return Candidates(boxes, scores, lam_o, cand_anchor, level_start, any_fg, idxs, rowmaxes)
@@ -472,6 +477,18 @@ def cdal_descriptor(maps, n_cls, score_thr=0.3, out=None):
     return out
 
 
+HUA_POOLS = ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg')
+
+
+def refuse_hua(head, **kwargs):
+    """A head without a Model Evidence Head (MyRetinaHead) has no lambda: HUA -- the Entropy_* pools of a scoring pass (isEval=False) and the
+    per-detection uncertainties (detUnc) -- is not defined for it."""
+    if (not kwargs.get('isEval') and kwargs.get('uPool') in HUA_POOLS) or kwargs.get('detUnc'):
+        what = 'detUnc' if kwargs.get('detUnc') else f"uncertainty_pool={kwargs.get('uPool')}"
+        raise ValueError(f'{type(head).__name__} has no lambda (no Model Evidence Head): {what} (HUA) is not defined for it; '
+                         'use Random, Coreset, CDAL, or the Ensemble / MC-dropout scores')
+
+
 def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes, scale_factors, cfg, rescale=False, with_nms=True,
                 **kwargs):
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.
@@ -491,12 +508,16 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     reproduced: an image without a foreground row on any level scores 0 here (there: mean of an empty list = NaN, which update_X_L's
     argsort ranks most uncertain), and a level counts iff it has a foreground row (there `if sUncs:` also drops a level whose mean is
     exactly 0.0)."""
-    assert head.last_activation in ('relu', 'softmax')
+    assert head.last_activation in ('relu', 'softmax', 'sigmoid')
     has_bg = head.last_activation == 'softmax'         # SSD: 21 logits incl. background (My_L_ssd_head.py:331-345)
+    # the plain RetinaNet baseline (MyRetinaHead; anchor_head.py:535-596): per-class sigmoid scores, detection paths only -- it has no lambda
+    sigmoid = head.last_activation == 'sigmoid'
     C_ = head.cls_out_channels
     na = head.num_anchors if isinstance(head.num_anchors, (list, tuple)) else [head.num_anchors] * len(mlvl_cls_scores)
     isUnc = kwargs.get('isUnc')
     uPool = kwargs.get('uPool')
+    if sigmoid:
+        refuse_hua(head, **kwargs)
     if isUnc and uPool == 'Entropy_NoNMS':
         raise NotImplementedError('uncertainty_pool=Entropy_NoNMS crashes in the reference too (ComputeScaleUnc with L_scores=None)')
     lam_mode = getattr(head, '_hua_lam', 'scaled')
@@ -533,7 +554,8 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                     for c, a in zip(mlvl_cls_scores, na)]
     nms_pre = cfg.get('nms_pre', -1)
     cand = pre_nms(mlvl_cls_scores, mlvl_bbox_preds, L_scores, mlvl_anchors, img_shapes, scale_factors, nms_pre, C_,
-                   head.bbox_coder.means, head.bbox_coder.stds, rescale=rescale, has_bg=has_bg, fg_thr=obj_thr)
+                   head.bbox_coder.means, head.bbox_coder.stds, rescale=rescale, has_bg=has_bg, fg_thr=obj_thr,
+                   activation='sigmoid' if sigmoid else None)
     if not with_nms:
         return [(cand.boxes[b], cand.scores[b]) for b in range(cand.boxes.shape[0])]
     max_num = cfg.max_per_img

@@ -53,14 +53,21 @@ class MyEpochBasedRunnerLambda(BaseRunner):
             # The MEH step reads only detached features / losses and its own parameters (train_step_L), so the main update may be
             # applied after it: the main network's last all-reduce buckets then run under the whole MEH forward/backward.  Same values as
             # the reference order (optimizer.step() before train_step_L, Epoch_Based_Runner_Lambda.py:27-35).
-            loss_L = self._module().train_step_L(prev_loss, head_out, feat_out, _data=data_batch, **kwargs)
-            self.optimizer_L.zero_grad()
-            loss_L['loss'].backward()
-            pending.wait()
-            self.optimizer.step()
-            self._sync(self.optimizer_L)
-            self.optimizer_L.step()
-            loss['log_vars'].update(loss_L['log_vars'])
+            if getattr(self, 'optimizer_L', None) is None:
+                # a detector without a Model Evidence Head (MyRetinaNet; build_optimizers gave one optimizer): the iteration ends with the
+                # main step -- MyRetinaBase.py / the reference's plain runner: train_step -> backward -> step
+                loss_L = None
+                pending.wait()
+                self.optimizer.step()
+            else:
+                loss_L = self._module().train_step_L(prev_loss, head_out, feat_out, _data=data_batch, **kwargs)
+                self.optimizer_L.zero_grad()
+                loss_L['loss'].backward()
+                pending.wait()
+                self.optimizer.step()
+                self._sync(self.optimizer_L)
+                self.optimizer_L.step()
+                loss['log_vars'].update(loss_L['log_vars'])
             # keep only the value: a loss that still owns its autograd graph keeps the parameters' AccumulateGrad nodes (bound to
             # this stream) alive, which makes a later HIP-graph capture of the iteration illegal -- and pins the activations
             loss['loss'] = loss['loss'].detach()
@@ -96,6 +103,11 @@ class MyEpochBasedRunnerLambda(BaseRunner):
             if not hasattr(self, '_gsync'):
                 self._gsync = GradSync()
             sync = self._gsync if is_dist() else None
+            if self.optimizer_L is None and sync is not None:
+                if not getattr(self, '_plain_eager_said', False):
+                    self._plain_eager_said = True
+                    self.logger.info('one-optimizer iteration under data parallelism: running eagerly (graph replay is single-process)')
+                return False
             gs = self._graph_step = (key, GraphedTrainStep(self.model, self.optimizer, self.optimizer_L, grad_sync=sync, **dict(key)))
         out = gs[1].maybe(data_batch)
         if out is None:

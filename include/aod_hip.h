@@ -400,6 +400,36 @@ int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const f
                                 int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
                                 const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox, int out_bf16,
                                 int A, int pitch_cls, int pitch_box, aod_stream_t stream);
+/* The plain RetinaNet baseline's loss (MyRetinaHead.py:91-109 -> FocalLoss, mmdet/models/losses/focal_loss.py:85 -> mmcv.ops.sigmoid_focal_loss)
+ * + the same L1 box term: mmcv-full 1.3.8's focal term applied to the RAW logits, per class, no softmax in front of it:
+ *   q = 1 / (1 + exp(-x_c));  target class: -alpha (1-q)^gamma log(max(q, FLT_MIN));  others: -(1-alpha) q^gamma log(max(1-q, FLT_MIN))
+ * (a label of C = background makes every column negative).  The gradient is that expression's derivative per class, clamps as written.
+ * Each entry takes exactly the arguments of its aod_edl_focal_l1_* / aod_edl_focal_elem counterpart above -- sums, partials, num_pos /
+ * divisors, g_noR_rows, the (A, pitch) dZ layout in bf16 or fp32 -- and is the same kernel with another compile-time form: same blocks,
+ * same summation orders, the level-fused launches bit-identical to per-level ones. */
+int aod_sigmoid_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w,
+                             const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                             int64_t nrows, int C, float gamma, float alpha,
+                             float* loss_noR, float* sums3, float* partials, aod_stream_t stream);
+int aod_sigmoid_focal_l1_bwd(const float* cls, const int64_t* labels, const float* label_w,
+                             const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                             int64_t nrows, int C, float gamma, float alpha,
+                             const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
+                             void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box,
+                             aod_stream_t stream);
+int aod_sigmoid_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w,
+                                    const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                                    int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                                    float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
+                                    float* divisors, float* num_total, aod_stream_t stream);
+int aod_sigmoid_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w,
+                                    const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                                    int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                                    const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox,
+                                    int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream);
+/* FocalLoss.forward(reduction='none') (focal_loss.py:85): out[r][c] = l_c, or with grad_out the gradient grad_out[r][c] * d l_c / d x_c */
+int aod_sigmoid_focal_elem(const float* cls, const int64_t* labels, int64_t nrows, int C, float gamma, float alpha,
+                           const float* grad_out, float* out, aod_stream_t stream);
 int aod_meh_loss_levels_fwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
                             float* out_sums, float* partials, aod_stream_t stream);
 int aod_meh_loss_levels_bwd(const float* lam, const float* loss_noR, const float* bbox_w4, int nlevels, const int64_t* level_rows,
@@ -440,7 +470,8 @@ int aod_max_iou_assign(const float* anchors, const uint8_t* valid, int64_t A, in
  * replaces Lambda_L2.py:264-304: alphas = softmax; scores = alphas / (sum(alphas) + 1e-20 + 1e-9); row max; level gate
  * (any anchor of the level with max alpha > fg_thr, Lambda_L2.py:497-502).  cls [B, rows_per_img, C] fp32 (one level);
  * rowmax [B, rows_per_img]; any_fg [B] int32 (OR-ed into; caller zeroes).  has_bg = 1 (SSD, My_L_ssd_head.py:331-345): plain softmax
- * over C logits whose last column is background, maxima over the C-1 foreground columns. */
+ * over C logits whose last column is background, maxima over the C-1 foreground columns.  has_bg = 2 (the plain RetinaNet baseline,
+ * anchor_head.py:535-554 with last_activation == 'sigmoid'): s_c = 1 / (1 + exp(-x_c)) per class, both maxima over all C columns. */
 int aod_softmax_rowmax(const float* cls, int B, int64_t rows_per_img, int C, float fg_thr, float* rowmax, int32_t* any_fg,
                        int has_bg, aod_stream_t stream);
 /* per image stable top-k (k <= 1024; descending score, ties -> lower index) of score [B, A] -> idx [B, out_pitch] int32
@@ -451,7 +482,8 @@ int aod_topk_stable(const float* score, int B, int64_t A, int k, int32_t* idx, i
  * boxes [B, n_total, 4] (clipped to img_hw[b] = (H, W), divided by scale4[b] when given), scores [B, n_total, C+1]
  * (normalised softmax + zero background column), lam [B, n_total], cand_anchor [B, n_total] = anchor0 + anchor index,
  * written at candidate offset cand0.  normalize: 1 normalised evidence scores, 0 raw softmax (Entropy_ALL), 2 softmax incl. a
- * background logit (SSD: C logits -> C score columns, no padding column). */
+ * background logit (SSD: C logits -> C score columns, no padding column), 3 per-class sigmoid scores (anchor_head.py:535-536,592-596:
+ * C score columns + the zero background column; aod_pre_nms_levels(normalize = 3) scans with has_bg = 2 itself and refuses has_bg != 0). */
 int aod_gather_decode(const float* cls, const float* reg, const float* lam_map, const float* anchors, const int32_t* idx,
                       int B, int64_t A, int k, int C, int64_t idx_pitch, const float* img_hw, const float* scale4,
                       const float* means4, const float* stds4, float wh_ratio_clip, float* boxes, float* scores, float* lam,
