@@ -42,6 +42,29 @@ class Uncertainty_fns:
     Entropy_Avg = Entropy_NMS          # CalMCDropoutUnc.py:65-76: same loop again (Lambda_L2Net_NoL: ComputeAvgUnc + AggregateAvgUnc)
 
     @staticmethod
+    @torch.no_grad()
+    def _posterior(pool, cfg, *args, **kwargs):
+        # posterior uncertainty pools: the Entropy_NMS loop (sharding, prefetch, captured scoring graph, one gather) with the
+        # pool's own name; the head reads `unc_aggregate` ('max' | 'mean' | 'sum', default 'max') and `score_thr` (default 0.3).  No lambda
+        # and no uPool2 are read: every head offers these pools, MyRetinaHead and the SSD head included
+        model, dataloader = args
+        model.eval()
+        unc = single_gpu_uncertainty(model, dataloader, isUnc=getattr(cfg, 'uncertainty_type', None) or 'Epistemic', uPool=pool, **kwargs)
+        return unc.cpu() if torch.is_tensor(unc) else [u.cpu() if torch.is_tensor(u) else u for u in unc]
+
+    @staticmethod
+    def Entropy(cfg, *args, **kwargs):
+        return Uncertainty_fns._posterior('Entropy', cfg, *args, **kwargs)
+
+    @staticmethod
+    def Margin(cfg, *args, **kwargs):
+        return Uncertainty_fns._posterior('Margin', cfg, *args, **kwargs)
+
+    @staticmethod
+    def LeastConf(cfg, *args, **kwargs):
+        return Uncertainty_fns._posterior('LeastConf', cfg, *args, **kwargs)
+
+    @staticmethod
     def Coreset(cfg, *args, **kwargs):
         # diversity-based selection (Sener & Savarese, ICLR 2018): needs the labelled set as the initial centers.  The HUA options that
         # calculate_uncertainty's callers pass for the Entropy_* pools (score_thr, clsW, ...) have no meaning for a descriptor pass
@@ -503,6 +526,26 @@ def CDAL_uncertainty(cfg, model, data_loader, X_L=None, budget=None, score_thr=0
     scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
     scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
     return scores.cpu()
+
+
+def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, **kwargs):
+    """Uncertainty sampling on the detector's own class posterior ("Entropy" in the paper's tables, margin and least confidence
+    after Brust et al., VISAPP 2019, and Roy et al., BMVC 2018; the reference has none) in the form update_X_L takes: per detection whose
+    score exceeds score_thr the entropy / 1-vs-2 margin / least confidence of its class posterior, aggregated over the image's detections
+    by max / mean / sum; an image without such a detection scores 0.  One forward per image; the pool pass is single_gpu_uncertainty's
+    (sharded, prefetched, one captured graph while the batch shape repeats, one gather).  Every detector has it: the evidence heads (their
+    EDL-normalised scores), the plain RetinaNet (sigmoid scores) and SSD (softmax with background); the config's uncertainty_pool is not
+    read.  Returns the CPU [N] fp32 vector; these are ordinary scores, zeroRate stays on."""
+    from ..scoring import UNC_AGGREGATES, UNC_MEASURES
+    if measure not in UNC_MEASURES:
+        raise ValueError(f"Posterior_uncertainty: unknown measure {measure!r} (expected 'entropy', 'margin' or 'leastconf')")
+    if aggregate not in UNC_AGGREGATES:
+        raise ValueError(f"Posterior_uncertainty: unknown aggregate {aggregate!r} (expected 'max', 'mean' or 'sum')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('Posterior_uncertainty: score_thr is NaN')
+    pool = {'entropy': 'Entropy', 'margin': 'Margin', 'leastconf': 'LeastConf'}[measure]
+    return getattr(Uncertainty_fns, pool)(cfg, model, data_loader, unc_aggregate=aggregate, score_thr=score_thr, **kwargs)
 
 
 @torch.no_grad()

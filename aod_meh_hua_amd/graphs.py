@@ -392,8 +392,11 @@ class GraphedScore:
         self.cache, self.pending = {}, None          # shape -> entry (insertion order = LRU); shape seen once
         self.dev = next(_unwrap(model).parameters()).device
         m = _unwrap(model)
+        from .scoring import POSTERIOR_POOLS
+        # the posterior pools are named by the call's own uPool (apis.Posterior_uncertainty scores them whatever the config's pool is)
+        self.posterior = bool(score_kwargs.get('isUnc')) and score_kwargs.get('uPool') in POSTERIOR_POOLS
         two_phase = (hasattr(m, 'extract_feat') and hasattr(getattr(m, 'bbox_head', None), 'test_heads') and not score_kwargs.get('isEval')
-                     and getattr(m.test_cfg, 'uncertainty_pool', None) in ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg'))
+                     and (getattr(m.test_cfg, 'uncertainty_pool', None) in ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg') or self.posterior))
         self.pipe = two_phase and (os.environ.get('AOD_SCORE_PIPELINE', '1') != '0' if pipeline is None else bool(pipeline))
         self.s_conv = self.s_tail = None
 
@@ -413,7 +416,10 @@ class GraphedScore:
     def _run_a(self, sl):
         m = self.module
         with torch.no_grad():
-            sl['preds'] = m.bbox_head.test_heads(m.extract_feat(sl['img']))
+            feats = m.extract_feat(sl['img'])
+            # (a posterior pool reads no lambda: an evidence head leaves its lambda tower out, as its simple_test does when run eagerly)
+            no_L = self.posterior and hasattr(m.bbox_head, 'L_convs')
+            sl['preds'] = m.bbox_head.test_heads(feats, with_L=False) if no_L else m.bbox_head.test_heads(feats)
 
     def _run_b(self, sl):
         """the selection half as SSL_L_SingleStageDetector.simple_test / forward_test run it for isEval=False"""

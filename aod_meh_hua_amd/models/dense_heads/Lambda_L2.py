@@ -200,9 +200,12 @@ class Lambda_L2Net(L_AnchorHead):
         outs = (self.retina_cls(c, out_f32=True), self.retina_reg(r, out_f32=True))
         return outs, self.retina_L(l, relu=True, out_f32=True)
 
-    def test_heads(self, feats):
-        """the conv half of simple_test (Lambda_L2.py:398-403): ((cls_scores, bbox_preds), L_scores) of a scoring batch"""
+    def test_heads(self, feats, with_L=True):
+        """the conv half of simple_test (Lambda_L2.py:398-403): ((cls_scores, bbox_preds), L_scores) of a scoring batch.
+        with_L=False (the posterior pools): the lambda tower is not run, L_scores is None."""
         import os
+        if not with_L:
+            return self.forward(feats), None
         x3_ok = AF.get_precision() == 'bf16' or all(m.conv.weight.shape[0] % 256 == 0 and m.conv.weight.shape[1] % 32 == 0 for m in self.cls_convs)
         if (not torch.is_grad_enabled() and x3_ok and os.environ.get('AOD_GROUP_TOWERS', '1') != '0'
                 and len(self.cls_convs) == len(self.reg_convs) == len(self.L_convs) > 0 and all(m.with_activation for m in self.cls_convs)):
@@ -213,6 +216,12 @@ class Lambda_L2Net(L_AnchorHead):
     def simple_test(self, feats, img_metas, rescale=False, _preds=None, **kwargs):
         """Lambda_L2.py:398-420.  `_preds` = the result of test_heads() computed earlier (graphs.GraphedScore runs the conv half and the
         selection / HUA half as two graphs on two streams: the half below keeps at most 16 workgroups busy)."""
+        from ...scoring import POSTERIOR_POOLS
+        if not kwargs['isEval'] and kwargs.get('isUnc') and kwargs.get('uPool') in POSTERIOR_POOLS:
+            # posterior uncertainty pools (DESIGN 3l): the class posterior alone -- the lambda tower is neither run nor passed on
+            outs = _preds[0] if _preds is not None else self.test_heads(feats, with_L=False)[0]
+            results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=True, **kwargs)
+            return (results_list[0], *results_list[1:])
         outs, L_scores = _preds if _preds is not None else self.test_heads(feats)
         if not kwargs['isEval'] and kwargs['uPool'] == 'Entropy_NoNMS':
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=False, **kwargs)

@@ -104,13 +104,17 @@ class MyRetinaHead(L_AnchorHead):
 
     def simple_test(self, feats, img_metas, rescale=False, _preds=None, **kwargs):
         """anchor_head.py simple_test -> get_bboxes: detections only.  isEval (with or without _padded) and the with_nms=False candidates
-        of uPool='Entropy_NoNMS'; the HUA pools and detUnc need lambda and raise."""
+        of uPool='Entropy_NoNMS'; the HUA pools and detUnc need lambda and raise.  The posterior pools (uPool in scoring.POSTERIOR_POOLS)
+        read the sigmoid scores alone: (det_results, unc) like the evidence heads' Entropy_NMS."""
         from ...scoring import refuse_hua
         refuse_hua(self, **kwargs)
         outs, _ = _preds if _preds is not None else self.test_heads(feats)
         with_nms = not (not kwargs['isEval'] and kwargs.get('uPool') == 'Entropy_NoNMS')
         results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=with_nms, **kwargs)
         if not kwargs['isEval']:
+            from ...scoring import POSTERIOR_POOLS
+            if kwargs.get('isUnc') and kwargs.get('uPool') in POSTERIOR_POOLS:      # (det_results, unc): DESIGN 3l, no lambda needed
+                return (results_list[0], *results_list[1:])
             return (results_list,)
         return results_list
 

@@ -112,7 +112,12 @@ class MyLSSDHead(L_AnchorHead):
 
     # ------------------------------------------------------------------ scoring
     def simple_test(self, feats, img_metas, rescale=False, **kwargs):
+        from ...scoring import POSTERIOR_POOLS
         outs = self.forward(feats)
+        if not kwargs['isEval'] and kwargs.get('isUnc') and kwargs.get('uPool') in POSTERIOR_POOLS:
+            # posterior uncertainty pools: the softmax posterior (background included) alone -- no lambda map is computed
+            results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=True, **kwargs)
+            return (results_list[0], *results_list[1:])
         L_scores = self.forward_L(feats, head_out=None)
         if not kwargs['isEval'] and kwargs['uPool'] in ('Entropy_ALL', 'Entropy_NMS'):
             results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=kwargs['uPool'] == 'Entropy_NMS', L_scores=L_scores, **kwargs)

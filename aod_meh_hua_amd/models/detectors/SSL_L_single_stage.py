@@ -74,6 +74,9 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
         results_list, *uncertainties = self.bbox_head.simple_test(feat, img_metas, rescale=rescale, **kwargs)
         if self.test_cfg.uncertainty_pool in ('Entropy_NoNMS', 'Entropy_ALL', 'Entropy_NMS', 'Entropy_Avg'):
             return (results_list, *uncertainties)
+        from ...scoring import POSTERIOR_POOLS
+        if kwargs.get('isUnc') and kwargs.get('uPool') in POSTERIOR_POOLS:      # the posterior pools: (results_list, unc) as above
+            return (results_list, *uncertainties)
         bbox_results = [bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes) for det_bboxes, det_labels in results_list]
         return bbox_results, uncertainties
 

@@ -477,6 +477,73 @@ def cdal_descriptor(maps, n_cls, score_thr=0.3, out=None):
     return out
 
 
+POSTERIOR_POOLS = ('Entropy', 'Margin', 'LeastConf')
+UNC_LAYOUTS = {'cat': 0, 'cat_bg': 1, 'sigmoid': 2}
+UNC_MEASURES = {'entropy': 0, 'margin': 1, 'leastconf': 2}
+UNC_AGGREGATES = {'max': 0, 'mean': 1, 'sum': 2}
+POOL_MEASURE = {'Entropy': 'entropy', 'Margin': 'margin', 'LeastConf': 'leastconf'}
+ACTIVATION_LAYOUT = {'relu': 'cat', 'softmax': 'cat_bg', 'sigmoid': 'sigmoid'}      # head.last_activation -> the posterior's row layout
+UNC_MAX_DET = 1024
+
+
+def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregate='max', score_thr=0.3, want_objects=False):
+    """Posterior uncertainty of every image of a batch (aod_det_uncertainty): entropy, 1-vs-2 margin or least confidence of the
+    class posterior of every detection, aggregated over the image's detections by max, mean or sum; an image without an object scores 0.
+
+    cand: the Candidates of pre_nms (boxes [B, n, 4], scores [B, n, W]); dets [B, max_num, 5], labels [B, max_num] int64, num [B] int32: the
+    outputs of multiclass_nms_batch on them.  layout: 'cat' (the first W - 1 columns are one categorical distribution: the Lambda_L2Net
+    family), 'cat_bg' (all W columns, background last: MyLSSDHead) or 'sigmoid' (the first W - 1 columns are independent Bernoulli
+    posteriors: MyRetinaHead).  A detection row j < num[b] with a score > score_thr (strict) is an object; its score row is looked up among
+    the candidates by its box and score bits.  Returns unc [B] fp32 on the device (no host sync), or with want_objects
+    (unc, obj_out [B, max_num] fp32 -- NaN where the row is no object --, missing [B] int32 -- objects without a candidate row: always 0)."""
+    if layout not in UNC_LAYOUTS:
+        raise ValueError(f"det_uncertainty: unknown layout {layout!r} (expected 'cat', 'cat_bg' or 'sigmoid')")
+    if measure not in UNC_MEASURES:
+        raise ValueError(f"det_uncertainty: unknown measure {measure!r} (expected 'entropy', 'margin' or 'leastconf')")
+    if aggregate not in UNC_AGGREGATES:
+        raise ValueError(f"det_uncertainty: unknown aggregate {aggregate!r} (expected 'max', 'mean' or 'sum')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('det_uncertainty: score_thr is NaN')
+    boxes, scores = getattr(cand, 'boxes', None), getattr(cand, 'scores', None)
+    for name, t, dt, nd in (('cand.boxes', boxes, torch.float32, 3), ('cand.scores', scores, torch.float32, 3), ('dets', dets, torch.float32, 3),
+                            ('labels', labels, torch.int64, 2), ('num', num, torch.int32, 1)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"det_uncertainty: {name} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'det_uncertainty: {name} is not contiguous; no copy is made here')
+    B, n, W = (int(v) for v in scores.shape)
+    if B < 1 or n < 1:
+        raise ValueError(f'det_uncertainty: cand.scores has shape {tuple(scores.shape)}; a positive batch size and candidate count are needed')
+    if tuple(boxes.shape) != (B, n, 4):
+        raise ValueError(f'det_uncertainty: cand.boxes has shape {tuple(boxes.shape)}, cand.scores {tuple(scores.shape)}: expected ({B}, {n}, 4)')
+    if W < 2:
+        raise ValueError(f'det_uncertainty: cand.scores rows of at least 2 columns are needed, got {W}')
+    used = W if layout == 'cat_bg' else W - 1
+    if measure == 'margin' and used < 2:
+        raise ValueError(f"det_uncertainty: measure 'margin' needs two used columns; layout {layout!r} reads {used} of the {W} of cand.scores")
+    if dets.shape[0] != B or dets.shape[2] != 5 or not 1 <= dets.shape[1] <= UNC_MAX_DET:
+        raise ValueError(f'det_uncertainty: dets has shape {tuple(dets.shape)}: expected ({B}, max_num, 5) with 1 <= max_num <= {UNC_MAX_DET}')
+    max_num = int(dets.shape[1])
+    if tuple(labels.shape) != (B, max_num):
+        raise ValueError(f'det_uncertainty: labels has shape {tuple(labels.shape)}, expected ({B}, {max_num})')
+    if tuple(num.shape) != (B,):
+        raise ValueError(f'det_uncertainty: num has shape {tuple(num.shape)}, expected ({B},)')
+    ts = (boxes, scores, dets, labels, num)
+    for t in ts:
+        if not t.is_cuda:
+            raise _C.AodHipError('det_uncertainty needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    dev = scores.device
+    if any(t.device != dev for t in ts):
+        raise ValueError(f'det_uncertainty: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    unc = torch.empty(B, dtype=torch.float32, device=dev)
+    obj_out = torch.empty(B, max_num, dtype=torch.float32, device=dev) if want_objects else None
+    missing = torch.empty(B, dtype=torch.int32, device=dev) if want_objects else None
+    call('aod_det_uncertainty', ptr(boxes), ptr(scores), ptr(dets), ptr(labels), ptr(num), B, n, W, max_num, UNC_LAYOUTS[layout],
+         UNC_MEASURES[measure], UNC_AGGREGATES[aggregate], score_thr, ptr(unc), ptr(obj_out), ptr(missing), stream())
+    return (unc, obj_out, missing) if want_objects else unc
+
+
 HUA_POOLS = ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg')
 
 
@@ -499,6 +566,9 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
     hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / Entropy_Avg / detUnc paths.
     isUnc with uPool == 'Entropy_NMS' -> (det_results, unc [B] device tensor).
+    isUnc with uPool in POSTERIOR_POOLS ('Entropy' | 'Margin' | 'LeastConf') -> the same pair from det_uncertainty: the measure of
+                 the head's own class posterior per detection, aggregated by `unc_aggregate` ('max' | 'mean' | 'sum', default 'max') over the
+                 detections whose score exceeds `score_thr` (default 0.3).  No lambda is read: every head offers these pools.
     Two class attributes of the head select the reference's ablations: `_hua_lam` ('scaled' | 'none': whether lambda scales alpha) and
     `_hua_thr_kwargs` (whether the `score_thr` / `iou_thr` kwargs replace the 0.3 / 0.5 of GetObjectIdx, the level gate and the candidate
     filter, Lambda_L2_ablation.py:261-265,355,496-518; a falsy or missing value falls back to 0.3 / 0.5).
@@ -566,6 +636,16 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
         if kwargs.get('detUnc'):
             raise ValueError('detUnc is not offered with the padded evaluation outputs')
         return dets, labels, num
+    if isUnc and not kwargs.get('isEval') and uPool in POSTERIOR_POOLS:
+        # posterior uncertainty pools: one launch behind the NMS kernel on what it and pre_nms left on the device; no lambda is
+        # read (L_scores may be None: every head has these pools, the plain RetinaNet and the SSD heads included), no host sync
+        thr = kwargs.get('score_thr')
+        unc = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation], POOL_MEASURE[uPool],
+                              kwargs.get('unc_aggregate') or 'max', 0.3 if thr is None else thr)
+        det_results = [(dets[b], labels[b]) for b in range(B)]   # zero-padded to max_per_img rows (num rows are valid)
+        if kwargs.get('_return_internals'):
+            return det_results, unc, dict(cand=cand, dets=dets, labels=labels, keep=keep, num=num)
+        return det_results, unc
     if (not isUnc or kwargs.get('isEval')) and not (kwargs.get('isEval') and kwargs.get('detUnc')):
         nh = num.cpu().tolist()           # evaluation path: variable-length results are part of the interface
         return [(dets[b, :nh[b]], labels[b, :nh[b]]) for b in range(B)]

@@ -10,7 +10,7 @@ load_from = None
 resume_from = None
 workflow = [('train', 1)]
 
-uncertainty_pool = 'Random'                 # 'Random' | 'Coreset' | 'CDAL'
+uncertainty_pool = 'Random'                 # 'Random' | 'Coreset' | 'CDAL' | 'Entropy' | 'Margin' | 'LeastConf'
 uncertainty_type = 'Epistemic'
 uncertainty_pool2 = 'objectSum_scaleMax_classSum'
 

@@ -718,6 +718,29 @@ int aod_cdal_descriptor(const void* const* maps, int L, const int64_t* rows_per_
 int aod_kcenter_greedy_ex(const float* desc, int64_t N, int D, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
                           float* radius, float* mind, void* ws, aod_stream_t stream, int metric);
 
+/* ------------------------------------------------------------------ Posterior uncertainty pools: entropy, margin, least confidence of the
+ * detector's own class posterior per detection, aggregated per image (csrc/det_unc.hip).  No reference call site ("Entropy" in the paper's
+ * tables; margin / least confidence and the max / mean / sum aggregates: Brust et al., VISAPP 2019; Roy et al., BMVC 2018); the semantics are
+ * fixed in DESIGN 3l.
+ *   aod_det_uncertainty: boxes [B][n][4], scores [B][n][W] = the candidates of aod_pre_nms_levels / aod_gather_decode; dets [B][max_num][5],
+ *     labels [B][max_num] int64, num [B] = the outputs of aod_multiclass_nms.  1 <= max_num <= 1024, n >= 1, W >= 2.
+ *     layout: the columns of a score row that form the posterior -- 0 (cat) the first W - 1 as one categorical distribution (the EDL-normalised
+ *     scores; the last column is the zero pad), 1 (cat_bg) all W (SSD's softmax, background last), 2 (sigmoid) the first W - 1 as independent
+ *     Bernoulli posteriors.  Row j of image b is an object iff j < num[b] and dets[b][j][4] > score_thr (strict; rows >= num[b] are never
+ *     read).  Its score row is the candidate of lowest index whose four box words equal dets[b][j][0..3] and whose score at labels[b][j]
+ *     equals dets[b][j][4], bit for bit (the NMS kernel copies both); an object without one (or with a label outside [0, W)) is skipped and
+ *     counted in missing[b].
+ *     measure: 0 entropy (-sum s ln s; layout 2: sum_c -s ln s - (1 - s) log1pf(-s); 0 ln 0 = 0), 1 margin 1 - (s_(1) - s_(2)) (two used
+ *     columns at least, else refused), 2 least confidence 1 - s_(1).  aggregate over the image's objects: 0 max, 1 mean, 2 sum; an image
+ *     without an object scores 0.  unc [B]; obj_out [B][max_num] (nullable): the measure per detection row, NaN where the row is no object
+ *     (or is missing); missing [B] int32 (nullable).
+ *     One launch, one workgroup per image, no atomics, no workspace, no host sync; logf / log1pf.  The classes of a row are added in column
+ *     order and the objects in a pairwise tree over the next power of two >= max_num: a function of j and max_num alone, so an image has the
+ *     same score bits alone, at any position of any batch, eager or replayed. */
+int aod_det_uncertainty(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B, int n,
+                        int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc, float* obj_out,
+                        int32_t* missing, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

@@ -51,10 +51,14 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--uncertainty-pool', default=None,
                    help="pool scoring rule (default: the config's uncertainty_pool): Random | Entropy_NMS | Entropy_ALL | Entropy_Avg | Coreset "
                         '| CDAL (Entropy_Avg: Lambda_L2Net_NoL only; Coreset: k-center greedy on pooled pyramid descriptors, zeroRate off; '
-                        'CDAL: k-center greedy on class-mixture descriptors under the symmetrised KL divergence, zeroRate off)')
+                        'CDAL: k-center greedy on class-mixture descriptors under the symmetrised KL divergence, zeroRate off) '
+                        '| Entropy | Margin | LeastConf (uncertainty sampling on the class posterior of every detection, aggregated per '
+                        'image by --unc-aggregate; every head has them, the plain RetinaNet and SSD included)')
+    p.add_argument('--unc-aggregate', choices=['max', 'mean', 'sum'], default='max',
+                   help="how the Entropy / Margin / LeastConf pools aggregate an image's per-detection values (default: max)")
     p.add_argument('--hua-score-thr', type=float, default=score_thr,
-                   help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL and, as the region '
-                        'threshold, by the CDAL pool')
+                   help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL, as the region '
+                        'threshold by the CDAL pool, and as the object gate by the Entropy / Margin / LeastConf pools')
     p.add_argument('--hua-iou-thr', type=float, default=iou_thr,
                    help='iou_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL only')
     p.add_argument('--uncertainty', help='uncertainty type (accepted like the reference accepts it, tools/train_RetinaNet.py:56: never read there either)')
@@ -250,6 +254,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
             coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL')
             pool_kw = dict(X_L=X_L) if coreset else {}
+            if cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf'):    # the posterior pools: ordinary scores, zeroRate stays on
+                pool_kw = dict(unc_aggregate=args.unc_aggregate)
             if coreset and zeroRate and cycle == cfg.cycles[0]:
                 logger.info(f'uncertainty_pool={cfg.uncertainty_pool}: zeroRate {zeroRate} -> 0 (the picks are the selection)')
             with torch.no_grad():
