@@ -174,6 +174,9 @@ _SIGS = {
     'aod_cdal_ws_len': (SZ, [I32, P, I32, I32]),
     'aod_cdal_descriptor': (C.c_int, [P, I32, P, I32, I32, F32, P, I64, P, I64, P]),
     'aod_det_uncertainty': (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P, P, P, P]),
+    'aod_loc_stability_max_levels': (C.c_int, []),
+    'aod_pixel_noise': (C.c_int, [P, P, I32, I32, I32, I32, P, P, F32, I32, U64, P, P]),
+    'aod_loc_stability': (C.c_int, [P, P, P, I32, I32, I32, F32, I32, I32, P, P, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

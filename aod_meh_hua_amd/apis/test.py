@@ -84,6 +84,23 @@ class Uncertainty_fns:
         return CDAL_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr)
 
     @staticmethod
+    def _loc_stability(combine, cfg, *args, **kwargs):
+        # localization stability (Kao et al., ACCV 2018): reads score_thr (the object gate, default 0.3), sigmas, seed and
+        # same_class; the HUA options that calculate_uncertainty's callers pass for the Entropy_* pools have no meaning for it
+        model, dataloader = args
+        own = {k: kwargs[k] for k in ('sigmas', 'seed', 'same_class') if kwargs.get(k) is not None}
+        thr = kwargs.get('score_thr')
+        return LocStability_uncertainty(cfg, model, dataloader, score_thr=0.3 if thr is None else thr, combine=combine, **own)
+
+    @staticmethod
+    def LocStability(cfg, *args, **kwargs):
+        return Uncertainty_fns._loc_stability('ls', cfg, *args, **kwargs)
+
+    @staticmethod
+    def LocStability_C(cfg, *args, **kwargs):
+        return Uncertainty_fns._loc_stability('ls+c', cfg, *args, **kwargs)
+
+    @staticmethod
     def Entropy_NoNMS(cfg, *args, **kwargs):
         # the reference's own Entropy_NoNMS path calls ComputeScaleUnc with L_scores=None (Lambda_L2.py:404-405,364) and raises a
         # TypeError on the first batch: there is no behaviour to reproduce
@@ -546,6 +563,133 @@ def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate=
         raise ValueError('Posterior_uncertainty: score_thr is NaN')
     pool = {'entropy': 'Entropy', 'margin': 'Margin', 'leastconf': 'LeastConf'}[measure]
     return getattr(Uncertainty_fns, pool)(cfg, model, data_loader, unc_aggregate=aggregate, score_thr=score_thr, **kwargs)
+
+
+def _noise_inv_std(img_metas, channels):
+    """1 / std_c of a batch's normalisation in the tensor's channel order (img_metas[...]['img_norm_cfg']['std']; a meta without one was
+    not normalised by the pipeline: std 1, Collect's own default).  One value for the whole batch, else ValueError."""
+    stds = []
+    for m in img_metas:
+        cfg = m.get('img_norm_cfg') if hasattr(m, 'get') else None
+        std = np.ones(channels, np.float64) if cfg is None else np.asarray(cfg['std'], np.float64).reshape(-1)
+        if std.size != channels or not np.all(np.isfinite(std)) or not np.all(std > 0):
+            raise ValueError(f'single_gpu_loc_stability: img_norm_cfg std {std.tolist()} does not hold {channels} finite positive values')
+        stds.append(std)
+    if any(not np.array_equal(s, stds[0]) for s in stds[1:]):
+        raise ValueError('single_gpu_loc_stability: the images of one batch were normalised with different std '
+                         f'({sorted({tuple(s.tolist()) for s in stds})}); the noise is scaled by one std per channel')
+    return [float(1.0 / v) for v in stds[0]]
+
+
+def _check_sigmas(sigmas):
+    from ..scoring import LOCSTAB_MAX_LEVELS
+    try:
+        sigmas = tuple(float(s) for s in sigmas)
+    except TypeError:
+        raise ValueError(f'single_gpu_loc_stability: sigmas must be a sequence of noise levels, got {sigmas!r}') from None
+    if not 1 <= len(sigmas) <= LOCSTAB_MAX_LEVELS:
+        raise ValueError(f'single_gpu_loc_stability: 1..{LOCSTAB_MAX_LEVELS} noise levels are supported, got {len(sigmas)}')
+    if not all(s >= 0.0 and s != float('inf') for s in sigmas):
+        raise ValueError(f'single_gpu_loc_stability: every noise level must be finite and >= 0, got {sigmas}')
+    return sigmas
+
+
+@torch.no_grad()
+def single_gpu_loc_stability(model, data_loader, sigmas=(8, 16, 24, 32, 40, 48), seed=0, score_thr=0.3, same_class=False, combine='ls',
+                             **kwargs):
+    """Localization stability (C.-C. Kao, T.-Y. Lee, P. Sen, M.-Y. Liu, "Localization-Aware Active Learning for Object Detection", ACCV
+    2018; the reference has none) on _PoolPass's loop: the pool is sharded over the ranks, batches come from the prefetch workers
+    through pinned memory (one H2D copy per batch), the scores stay on the device and are gathered once.  Returns a [N] fp32 tensor
+    identical on every rank.
+
+    Per batch: the clean detection forward (isEval=True, padded outputs), then per noise level k one aod_pixel_noise launch into a reused
+    scratch batch (keyed by seed, k and the GLOBAL image ids; sigmas in 0..255 pixel units, scaled by the batch's img_norm_cfg std) and one
+    forward; (dets, labels, num) are copied into slot k of a preallocated stack after every forward, then ONE scoring.loc_stability launch.
+    While the batch shape repeats (and AOD_HIP_GRAPH != 0) the K + 1 forwards are K + 1 replays of the ONE captured detection graph
+    single_gpu_map uses (the same key: an evaluation and a stability pass of one model share the capture): a shape is captured when a
+    batch repeats the previous batch's shape, as in single_gpu_map.  A batch whose shape is seen for the first time (a ragged last batch,
+    every batch of a variable-shape pool) makes all its K + 1 forwards eagerly, and so does a batch that is a list of several image
+    tensors, every one of which gets its own noise launch (the detectors here refuse such test-time augmentation lists themselves).  It
+    needs nothing but detections, so every detector has it.  An image's score is a function of (weights, image, seed, image id, sigmas) only: the same bits
+    alone, in any batch, on any rank count, eager or replayed."""
+    from .. import functional as AF
+    from .. import hipops as ho
+    from ..scoring import LOCSTAB_COMBINES, loc_stability
+    sigmas = _check_sigmas(sigmas)
+    if combine not in LOCSTAB_COMBINES:
+        raise ValueError(f"single_gpu_loc_stability: unknown combine {combine!r} (expected 'ls' or 'ls+c')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('single_gpu_loc_stability: score_thr is NaN')
+    seed = int(seed)
+    kwargs.setdefault('isUnc', False)              # (single_gpu_map's option set: the two passes share one graph key)
+    model.eval()
+    dev = next(model.parameters()).device
+    pool = _PoolPass(data_loader, dev)
+    gscore = _graphed(model, dev, ('eval_padded',), kwargs, isEval=True, _padded=True)
+    K = len(sigmas)
+    chunks, stacks, scratch, hw_cache = [], {}, {}, {}
+
+    def sizes(metas):
+        """int32 [B, 2] (h, w) of a batch on the device, kept by value (a pool re-uses a handful of them)"""
+        key = tuple((int(m['img_shape'][0]), int(m['img_shape'][1])) for m in metas)
+        hw = hw_cache.get(key)
+        if hw is None:
+            if len(hw_cache) > 256:
+                hw_cache.clear()
+            hw = hw_cache[key] = torch.tensor(key, dtype=torch.int32).to(dev)
+        return hw
+
+    for idxs, image_ids, data in pool.batches(to_device=True):          # the K + 1 forwards read the one device tensor
+        # the batch as the model takes it: a list of image tensors (one entry; test-time augmentation lists have more) and their metas
+        listed = isinstance(data['img'], (list, tuple))
+        imgs = list(data['img']) if listed else [data['img']]
+        metas = list(data['img_metas']) if listed else [data['img_metas']]
+        if len(imgs) != len(metas) or not all(torch.is_tensor(t) and t.dim() == 4 for t in imgs):
+            raise ValueError('single_gpu_loc_stability: a batch must hold [B, C, H, W] image tensors, one list of metas for each')
+        imgs = [t.to(dev, non_blocking=True).float().contiguous() for t in imgs]      # (a one-tensor batch is on the device already)
+        prep = [(_noise_inv_std(m, int(t.shape[1])), sizes(m)) for t, m in zip(imgs, metas)]
+        # the graph serves a batch whose shape it has captured, or captures one that repeats the previous batch's shape (as single_gpu_map
+        # does); a shape seen for the first time -- a ragged last batch, every batch of a variable-shape pool -- runs its K + 1 forwards
+        # eagerly, and so does a list batch
+        g = None
+        if gscore is not None and _single(data):
+            gkey = (tuple(imgs[0].shape), AF.mode_key())
+            if gkey in gscore.cache or gkey == gscore.pending:
+                g = gscore
+            else:
+                gscore.pending = gkey
+        stack = None
+        for k in range(-1, K):
+            xs = imgs
+            if k >= 0:
+                xs = []
+                for a, (t, (inv_std, hw)) in enumerate(zip(imgs, prep)):
+                    noisy = scratch.get((a, tuple(t.shape)))
+                    if noisy is None:
+                        noisy = scratch[(a, tuple(t.shape))] = torch.empty_like(t)
+                    xs.append(ho.pixel_noise(t, noisy, hw, inv_std, sigmas[k], k, seed, image_ids))
+            d = dict(data, img=xs if listed else xs[0])
+            dets, labels, num = _replay_or_eager(g, d, image_ids,
+                                                 lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **d, **kwargs))
+            if stack is None:
+                key = (int(dets.shape[0]), int(dets.shape[1]))
+                stack = stacks.get(key)
+                if stack is None:
+                    stack = stacks[key] = (torch.empty((K + 1,) + tuple(dets.shape), dtype=torch.float32, device=dev),
+                                           torch.empty((K + 1,) + tuple(labels.shape), dtype=torch.int64, device=dev),
+                                           torch.empty((K + 1,) + tuple(num.shape), dtype=torch.int32, device=dev))
+            # (a replay overwrites the graph's static outputs: every forward is copied out)
+            stack[0][k + 1].copy_(dets), stack[1][k + 1].copy_(labels), stack[2][k + 1].copy_(num)
+        chunks.append(loc_stability(*stack, score_thr=score_thr, same_class=same_class, combine=combine))
+    return pool.gather(pool.cat(chunks))
+
+
+def LocStability_uncertainty(cfg, model, data_loader, **kwargs):
+    """Localization-stability acquisition in the form update_X_L takes (single_gpu_loc_stability; kwargs: sigmas, seed, score_thr,
+    same_class, combine 'ls' | 'ls+c').  Larger scores are selected first; these are ordinary scores, zeroRate stays on.  The config is not
+    read.  Returns the CPU [N] fp32 vector."""
+    return single_gpu_loc_stability(model, data_loader, **kwargs).cpu()
 
 
 @torch.no_grad()

@@ -102,4 +102,14 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
   r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
 }
 __device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 1.0f) * 5.9604644775390625e-08f; }
+// one Philox block -> two Box-Muller pairs -> four N(0, 1) values (ra cos, ra sin, rb cos, rb sin): the synthetic pool images and the
+// pixel noise of the localization-stability pool share this quad bit for bit
+__device__ __forceinline__ f32x4 philox_normal4(const unsigned* r) {
+  const float ra = __builtin_amdgcn_sqrtf(-2.f * 0.693147180559945309f * __builtin_amdgcn_logf(u01(r[0])));
+  const float rb = __builtin_amdgcn_sqrtf(-2.f * 0.693147180559945309f * __builtin_amdgcn_logf(u01(r[2])));
+  f32x4 v;
+  v[0] = ra * __builtin_amdgcn_cosf(u01(r[1])); v[1] = ra * __builtin_amdgcn_sinf(u01(r[1]));
+  v[2] = rb * __builtin_amdgcn_cosf(u01(r[3])); v[3] = rb * __builtin_amdgcn_sinf(u01(r[3]));
+  return v;
+}
 

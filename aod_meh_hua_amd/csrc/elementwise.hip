@@ -583,12 +583,7 @@ __global__ __launch_bounds__(256) void synth_normal_kernel(float* __restrict__ d
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_img4; i += (long long)gridDim.x * 256) {
     unsigned r[4];
     philox4x32_10((unsigned)i, (unsigned)(i >> 32), id_lo, id_hi, k0, k1, r);
-    const float ra = __builtin_amdgcn_sqrtf(-2.f * 0.693147180559945309f * __builtin_amdgcn_logf(u01(r[0])));
-    const float rb = __builtin_amdgcn_sqrtf(-2.f * 0.693147180559945309f * __builtin_amdgcn_logf(u01(r[2])));
-    f32x4 v;
-    v[0] = ra * __builtin_amdgcn_cosf(u01(r[1])); v[1] = ra * __builtin_amdgcn_sinf(u01(r[1]));
-    v[2] = rb * __builtin_amdgcn_cosf(u01(r[3])); v[3] = rb * __builtin_amdgcn_sinf(u01(r[3]));
-    *reinterpret_cast<f32x4*>(dst + ((long long)b * per_img4 + i) * 4) = v;
+    *reinterpret_cast<f32x4*>(dst + ((long long)b * per_img4 + i) * 4) = philox_normal4(r);
   }
 }
 

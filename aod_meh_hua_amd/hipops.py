@@ -964,3 +964,39 @@ def image_xform(src_pack, items, B, Hp, Wp, out):
         raise ValueError(f'image_xform: out must be a contiguous float32 [{B}, 3, {Hp}, {Wp}] tensor, got {out.dtype} {tuple(out.shape)}')
     call('aod_image_xform', ptr(src_pack), ptr(items), B, Hp, Wp, ptr(out), stream())
     return out
+
+
+def pixel_noise(src, dst, hw, inv_std, sigma, level, seed, image_ids):
+    """dst = src + (sigma / std_c) z inside every image's img_shape, src's bits in the pad (aod_pixel_noise): the noisy copies
+    of the localization-stability pool.  src, dst: contiguous fp32 [B, C, Hp, Wp] on the device, out of place, C <= 4, Wp % 4 == 0;
+    hw: device int32 [B, 2] (h, w) per image; inv_std: C host floats 1 / std_c in the tensor's channel order; sigma >= 0 in 0..255 pixel
+    units; level 0..15; image_ids: device int64 [B], the GLOBAL ids.  z is a pure function of (seed, level, id, c, y, x)."""
+    for name, t in (('src', src), ('dst', dst)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+            raise ValueError(f'pixel_noise: {name} must be a contiguous fp32 [B, C, Hp, Wp] tensor')
+    if tuple(dst.shape) != tuple(src.shape):
+        raise ValueError(f'pixel_noise: dst has shape {tuple(dst.shape)}, src {tuple(src.shape)}')
+    B, Cc, Hp, Wp = (int(v) for v in src.shape)
+    if B < 1 or not 1 <= Cc <= 4:
+        raise ValueError(f'pixel_noise: a positive batch and 1..4 channels are needed, got {tuple(src.shape)}')
+    if not (1 <= Hp <= 65536 and 1 <= Wp <= 262144 and Wp % 4 == 0):
+        raise ValueError(f'pixel_noise: padded size {Hp} x {Wp}: Hp <= 65536, Wp <= 262144 and Wp % 4 == 0 are needed')
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and sigma != float('inf')):
+        raise ValueError(f'pixel_noise: sigma must be finite and >= 0, got {sigma}')
+    max_levels = int(lib.aod_loc_stability_max_levels())
+    if not 0 <= int(level) < max_levels:
+        raise ValueError(f'pixel_noise: level must be in 0..{max_levels - 1}, got {level}')
+    inv_std = [float(v) for v in inv_std]
+    if len(inv_std) != Cc or not all(0.0 < v < float('inf') for v in inv_std):
+        raise ValueError(f'pixel_noise: inv_std must hold {Cc} finite positive values, got {inv_std}')
+    if not (torch.is_tensor(hw) and hw.dtype == torch.int32 and tuple(hw.shape) == (B, 2) and hw.is_contiguous()):
+        raise ValueError(f'pixel_noise: hw must be a contiguous int32 [{B}, 2] tensor')
+    if not (torch.is_tensor(image_ids) and image_ids.dtype == torch.int64 and tuple(image_ids.shape) == (B,) and image_ids.is_contiguous()):
+        raise ValueError(f'pixel_noise: image_ids must be a contiguous int64 [{B}] tensor')
+    a, b, n = src.data_ptr(), dst.data_ptr(), 4 * src.numel()
+    if a == b or (a < b + n and b < a + n):
+        raise ValueError('pixel_noise: dst == src (or overlaps it): the kernel is out of place')
+    call('aod_pixel_noise', ptr(src), ptr(dst), B, Cc, Hp, Wp, ptr(hw), (C.c_float * Cc)(*inv_std), sigma, int(level),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(image_ids), stream())
+    return dst

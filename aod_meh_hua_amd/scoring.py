@@ -544,6 +544,55 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     return (unc, obj_out, missing) if want_objects else unc
 
 
+LOCSTAB_COMBINES = {'ls': 0, 'ls+c': 1}
+LOCSTAB_MAX_LEVELS = int(_C.lib.aod_loc_stability_max_levels())      # (written once, in csrc/loc_stability.hip)
+LOCSTAB_SIGMAS = (8, 16, 24, 32, 40, 48)      # Kao et al.'s noise levels, 0..255 pixel units
+
+
+def loc_stability(dets, labels, num, score_thr=0.3, same_class=False, combine='ls', want_objects=False):
+    """Localization stability of every image of a batch (aod_loc_stability; Kao et al., ACCV 2018): how far the boxes of the
+    clean detections move under pixel noise.
+
+    dets [K+1, B, max_num, 5] fp32, labels [K+1, B, max_num] int64, num [K+1, B] int32: the stacked padded detections, slot 0 of the clean
+    batch, slot k + 1 of noise level k; 1 <= K <= 16, 1 <= max_num <= 1024.  A row j < num[0][b] of slot 0 with a score > score_thr (strict)
+    is an object of weight w_j = its score; m_jk is its largest IoU over the rows < num[k+1][b] of slot k + 1 (same_class: rows of its label
+    only), S_j the mean of m_jk over the levels, S_I the w-weighted mean of S_j.  combine 'ls': 1 - S_I; 'ls+c': (1 - S_I) + (1 - max_j w_j);
+    an image without an object scores 0.  Returns unc [B] fp32 on the device (no host sync), or with want_objects (unc, stab [B, max_num]
+    fp32: S_j, NaN where the row is no object)."""
+    if combine not in LOCSTAB_COMBINES:
+        raise ValueError(f"loc_stability: unknown combine {combine!r} (expected 'ls' or 'ls+c')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('loc_stability: score_thr is NaN')
+    for name, t, dt, nd in (('dets', dets, torch.float32, 4), ('labels', labels, torch.int64, 3), ('num', num, torch.int32, 2)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"loc_stability: {name} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'loc_stability: {name} is not contiguous; no copy is made here')
+    K1, B, max_num, five = (int(v) for v in dets.shape)
+    if not 1 <= K1 - 1 <= LOCSTAB_MAX_LEVELS:
+        raise ValueError(f'loc_stability: dets holds {K1} slots: the clean one and 1..{LOCSTAB_MAX_LEVELS} noise levels are needed')
+    if B < 1 or five != 5 or not 1 <= max_num <= UNC_MAX_DET:
+        raise ValueError(f'loc_stability: dets has shape {tuple(dets.shape)}: expected (K + 1, B, max_num, 5) with B >= 1 and '
+                         f'1 <= max_num <= {UNC_MAX_DET}')
+    if tuple(labels.shape) != (K1, B, max_num):
+        raise ValueError(f'loc_stability: labels has shape {tuple(labels.shape)}, expected ({K1}, {B}, {max_num})')
+    if tuple(num.shape) != (K1, B):
+        raise ValueError(f'loc_stability: num has shape {tuple(num.shape)}, expected ({K1}, {B})')
+    ts = (dets, labels, num)
+    for t in ts:
+        if not t.is_cuda:
+            raise _C.AodHipError('loc_stability needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    dev = dets.device
+    if any(t.device != dev for t in ts):
+        raise ValueError(f'loc_stability: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    unc = torch.empty(B, dtype=torch.float32, device=dev)
+    stab = torch.empty(B, max_num, dtype=torch.float32, device=dev) if want_objects else None
+    call('aod_loc_stability', ptr(dets), ptr(labels), ptr(num), K1 - 1, B, max_num, score_thr, 1 if same_class else 0,
+         LOCSTAB_COMBINES[combine], ptr(unc), ptr(stab), stream())
+    return (unc, stab) if want_objects else unc
+
+
 HUA_POOLS = ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg')
 
 

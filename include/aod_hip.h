@@ -741,6 +741,37 @@ int aod_det_uncertainty(const float* boxes, const float* scores, const float* de
                         int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc, float* obj_out,
                         int32_t* missing, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ Localization-stability acquisition (csrc/loc_stability.hip): detect on
+ * the clean image and on copies with Gaussian pixel noise of growing strength, score the image by how far its boxes move (Kao, Lee, Sen,
+ * Liu, "Localization-Aware Active Learning for Object Detection", ACCV 2018: LS and LS+C).  No reference call site; the semantics are fixed
+ * in DESIGN 3m.
+ *   aod_pixel_noise: src, dst fp32 [B][C][Hp][Wp] (normalised, padded model input), out of place (dst == src or overlapping: refused),
+ *     16-B aligned; C <= 4, Hp <= 65536, Wp <= 262144, Wp % 4 == 0.  hw [B][2] int32 (device): img_shape (h, w) per image; inv_std: C HOST
+ *     floats, 1 / std_c of the normalisation in the tensor's channel order; sigma >= 0, finite, in 0..255 pixel units; 0 <= level < 16.
+ *     dst[b][c][y][x] = src + (sigma * inv_std[c]) * z for y < h and x < w, src's bits elsewhere (and everywhere for sigma == 0); no
+ *     clipping.  z = element x & 3 of the four normals (u01, two Box-Muller pairs: ra cos, ra sin, rb cos, rb sin -- the quad of
+ *     aod_synth_normal_images) of the Philox4x32-10 block with counter (c0, c1, c2, c3) = ((y << 16) | (x >> 2), 0x80000000 | (level << 8) | c,
+ *     id & 0xffffffff, id >> 32), id = image_ids[b] (device int64), key (seed & 0xffffffff, seed >> 32).  Bit 31 of c1 keeps the stream
+ *     disjoint from the synthetic pool's.  z is a function of (seed, level, id, c, y, x) alone -- not of B, the batch position or Wp.
+ *     One thread per 4 consecutive x (a 16-B load and a 16-B store).
+ *   aod_loc_stability: the stacked slots dets [K+1][B][max_num][5], labels [K+1][B][max_num] int64,
+ *     num [K+1][B]: slot 0 the clean detections, slot k + 1 those of noise level k; 1 <= K <= 16, 1 <= max_num <= 1024.  Reference row j of
+ *     slot 0 is an object iff j < num[0][b] and dets[0][b][j][4] > score_thr (strict); w_j is that score.  m_jk = the largest IoU of box j
+ *     over the rows < num[k+1][b] of slot k + 1 (same_class = 1: rows with j's label only), 0 for an empty slot;
+ *       iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih likewise, ov = iw * ih, un = area_a + area_b - ov, IoU = ov / max(un, 1e-6)
+ *     in fp32 with an IEEE division (aod_eval_match's form, no +1).  S_j = (m_j0 + ... + m_j,K-1) / K, added in level order;
+ *     S_I = sum_j w_j S_j / sum_j w_j over the objects.  combine 0 (ls): unc[b] = 1 - S_I; 1 (ls+c): (1 - S_I) + (1 - max_j w_j); an image
+ *     without an object scores 0.  stab_out [B][max_num] (nullable): S_j, NaN where the row is no object.  Rows >= num of any slot are never
+ *     read.
+ *     One launch, one workgroup per image, no atomics, no workspace, no host sync.  The sums over j run in a pairwise tree over the next
+ *     power of two >= max_num: a function of j and max_num alone, so an image has the same score bits alone, at any position of any batch,
+ *     eager or replayed. */
+int aod_loc_stability_max_levels(void); /* 16: the largest K of aod_loc_stability, levels 0 .. 15 of aod_pixel_noise */
+int aod_pixel_noise(const float* src, float* dst, int B, int C, int Hp, int Wp, const int32_t* hw, const float* inv_std, float sigma, int level,
+                    uint64_t seed, const int64_t* image_ids, aod_stream_t stream);
+int aod_loc_stability(const float* dets, const int64_t* labels, const int32_t* num, int K, int B, int max_num, float score_thr, int same_class,
+                      int combine, float* unc, float* stab_out, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

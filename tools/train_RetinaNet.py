@@ -53,7 +53,14 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         '| CDAL (Entropy_Avg: Lambda_L2Net_NoL only; Coreset: k-center greedy on pooled pyramid descriptors, zeroRate off; '
                         'CDAL: k-center greedy on class-mixture descriptors under the symmetrised KL divergence, zeroRate off) '
                         '| Entropy | Margin | LeastConf (uncertainty sampling on the class posterior of every detection, aggregated per '
-                        'image by --unc-aggregate; every head has them, the plain RetinaNet and SSD included)')
+                        'image by --unc-aggregate; every head has them, the plain RetinaNet and SSD included) '
+                        '| LocStability | LocStability_C (localization stability, Kao et al., ACCV 2018: how far the boxes of the clean '
+                        'detections move under Gaussian pixel noise of the strengths --noise-levels; LocStability_C adds 1 - the largest '
+                        'detection score; reads detections only, so every detector has them)')
+    p.add_argument('--noise-levels', default='8,16,24,32,40,48',
+                   help='noise strengths of the LocStability pools: up to 16 comma-separated standard deviations in 0..255 pixel units '
+                        '(default: 8,16,24,32,40,48)')
+    p.add_argument('--noise-seed', type=int, default=0, help='seed of the pixel noise of the LocStability pools (default: 0)')
     p.add_argument('--unc-aggregate', choices=['max', 'mean', 'sum'], default='max',
                    help="how the Entropy / Margin / LeastConf pools aggregate an image's per-detection values (default: max)")
     p.add_argument('--hua-score-thr', type=float, default=score_thr,
@@ -88,6 +95,13 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                    help='EvalHook computes mAP on the device: padded detections -> aod_eval_match -> one D2H copy, the test set sharded over '
                         'the ranks (config key evaluation.device_metric); same numbers as the host metric')
     args = p.parse_args()
+    try:            # (at start-up: a malformed value must not surface after a whole training cycle)
+        args.noise_sigmas = tuple(float(s) for s in args.noise_levels.split(',') if s.strip())
+    except ValueError:
+        p.error(f'--noise-levels: {args.noise_levels!r} is not a comma-separated list of numbers')
+    from aod_meh_hua_amd.scoring import LOCSTAB_MAX_LEVELS
+    if not 1 <= len(args.noise_sigmas) <= LOCSTAB_MAX_LEVELS or not all(0.0 <= s < float('inf') for s in args.noise_sigmas):
+        p.error(f'--noise-levels: 1..{LOCSTAB_MAX_LEVELS} finite values >= 0 are needed, got {args.noise_levels!r}')
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
 
@@ -256,6 +270,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             pool_kw = dict(X_L=X_L) if coreset else {}
             if cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf'):    # the posterior pools: ordinary scores, zeroRate stays on
                 pool_kw = dict(unc_aggregate=args.unc_aggregate)
+            if cfg.uncertainty_pool in ('LocStability', 'LocStability_C'):    # localization stability: ordinary scores too
+                pool_kw = dict(sigmas=args.noise_sigmas, seed=args.noise_seed)
             if coreset and zeroRate and cycle == cfg.cycles[0]:
                 logger.info(f'uncertainty_pool={cfg.uncertainty_pool}: zeroRate {zeroRate} -> 0 (the picks are the selection)')
             with torch.no_grad():
