@@ -70,10 +70,30 @@ __device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d) {
   return q;
 }
 
-__device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
+__host__ __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
   // bijective remap: blocks that share an XCD (bid % 8) get a contiguous range of tiles
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
+// block -> (tile, member) of a grouped launch of `ngroups` members of `nwg` tiles each; a bijection of [0, nwg * ngroups).
+// mapped = 0 (no member carries a row-activity map): member-major over xcd_swizzle -- every XCD a contiguous range of tiles.
+// mapped = 1: a member's LIVE tiles cluster (the positives sit on the coarse levels, the last quarter of the tile range), and a contiguous
+// range per XCD hands them all to two of the eight XCDs, which then run as many rounds as the dense launch while the other six idle.  So the
+// blocks are dealt (tile, member) with the member fastest and NO swizzle: consecutive tiles of one member then sit `ngroups` blocks apart,
+// which walks all eight bid % 8 classes when ngroups is odd; when it is even they would stay on every other class (with two members: the dense
+// member on the even classes only), so the member order turns by one with every eight blocks.  Any 64 consecutive tiles of a member put 8 +- 1
+// on each class.  Placement only (which XCD runs a block is a speed heuristic): nothing depends on it for correctness.  (Measured, docs/LAB_NOTES.md
+// section 22: the mapped forward runs in two thirds of the dense time; the paired dgrad stays within 4 % of its dense time under either order.)
+__host__ __device__ __forceinline__ void conv_grouped_deal(int bid, int nwg, int ngroups, int mapped, int& tile, int& group) {
+  if (!mapped) {
+    const int wg = xcd_swizzle(bid, nwg * ngroups);
+    tile = wg % nwg; group = wg / nwg;
+    return;
+  }
+  tile = bid / ngroups;
+  const int turn = (ngroups & 1) ? 0 : (tile * ngroups) >> 3;
+  group = (bid - tile * ngroups + turn) % ngroups;
 }
 
 // OPS: which optional epilogue operands the instance supports -- 0 none, 1 ReLU mask only, 2 residual and mask (their prefetch registers
@@ -123,10 +143,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
     const int x = blockIdx.x & 7, j = blockIdx.x >> 3, q = j & 3, k = j >> 2, tq = nwg >> 2;
     wg = q * tq + x * (tq >> 3) + k;
   } else wg = blockIdx.x;
-  // (grouped launches with a row-activity map: tiles dealt (tile, group)-interleaved.  xcd_swizzle hands every XCD a contiguous range of `wg`;
-  // group-major, the mapped member's mostly dead tiles would all fall to half of the XCDs, which then idle beside the dense member's half)
-  const bool il = GROUPED && p.interleave;
-  const int tile = il ? wg / p.ngroups : wg % nwg, zz = il ? wg % p.ngroups : wg / nwg;
+  // (grouped launches with a row-activity map, forward or dgrad: the even deal of conv_grouped_deal instead)
+  int tile = wg % nwg, zz = wg / nwg;
+  if (GROUPED && p.interleave) conv_grouped_deal(blockIdx.x, nwg, p.ngroups, 1, tile, zz);
   const int kz = GROUPED ? 0 : zz;           // kz: which slice of the K-steps (split-K launches)
   // grouped launch: `ngroups` convolutions of identical geometry (the cls / reg / evidence towers at one depth) share one grid, so
   // that their tiles fill whole rounds of the CUs together; group = which operand set this workgroup uses
@@ -146,6 +165,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
     // sparse backward: a tile that nothing but zero dZ rows can reach (the launcher: dense stride-1 dgrad, destination row = GEMM row, no bias /
     // residual, atomic column sums -- a zero tile adds nothing to them) loads no operand and runs no K-step: it stores its zero rows, heads and
     // tails, which the next dgrad reads as halo, and returns.  Workgroup-uniform: scalar loads of at most BM / 64 map bytes, one branch.
+    // sparse forward (conv_fwd_map_setup): the same block with a map of where the OUTPUT is needed.  A dead tile stores ZERO rows, not
+    // relu(bias): the wgrad and the next layer's halo read them against exact-zero gradients, and those rows must be finite.
     const unsigned char* const om = AOD_GSEL(omap, p.omap);
     if (om) {
       const int mend = m0 + BM < p.M ? m0 + BM : p.M;
@@ -1090,13 +1111,13 @@ struct ConvKnobs {
   static const Once& once() { static const Once k{}; return k; }
 
   enum Call { X3P_OVER_256, X3_TILE_192, X3P_GROUPED, X3P, X3P_PRE, X3P_BN, X3P_DGRAD, X3P_LATTICE, X3P_MIN_STEPS, X3P_PRE_MIN_STEPS, X3P_MIN_TILES,
-              X3P_ROT, SPARSE_BWD, NCALL };
+              X3P_ROT, SPARSE_BWD, SPARSE_FWD, NCALL };
   const char* val[NCALL];
   unsigned seen = 0;
   const char* call(Call k) {
     static const char* const names[NCALL] = {"AOD_X3P_OVER_256", "AOD_X3_TILE_192", "AOD_X3P_GROUPED", "AOD_X3P", "AOD_X3P_PRE", "AOD_X3P_BN",
                                              "AOD_X3P_DGRAD", "AOD_X3P_LATTICE", "AOD_X3P_MIN_STEPS", "AOD_X3P_PRE_MIN_STEPS", "AOD_X3P_MIN_TILES",
-                                             "AOD_X3P_ROT", "AOD_SPARSE_BWD"};
+                                             "AOD_X3P_ROT", "AOD_SPARSE_BWD", "AOD_SPARSE_FWD"};
     if (!((seen >> k) & 1u)) { val[k] = getenv(names[k]); seen |= 1u << k; }
     return val[k];
   }
@@ -1216,9 +1237,7 @@ static int conv_params_grouped(const aod_conv_desc_t* desc, int ngroups, const v
 // out[b] = OR of in[] over the dZ rows that the destination rows of block b can reach through the filter taps of a dense stride-1 dgrad: the
 // linear range [first - up W - left, last + down W + right] of the segment, cut to the whole image rows and to the images the block touches.
 struct MapGeo { int nseg, M, R, S, pad, dil; int segH[8], segW[8], seg_mend[8]; };
-__global__ __launch_bounds__(256) void row_map_dilate_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, const MapGeo g) {
-  const int b = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (b >= (g.M + 63) >> 6) return;
+__device__ __forceinline__ unsigned char row_map_dilate_at(const unsigned char* in, int b, const MapGeo& g) {
   const int r0 = b << 6, r1 = r0 + 63 < g.M ? r0 + 63 : g.M - 1;
   const int up = (g.R - 1) * g.dil - g.pad, dn = g.pad, lf = (g.S - 1) * g.dil - g.pad, rt = g.pad;
   int any = 0;
@@ -1234,7 +1253,60 @@ __global__ __launch_bounds__(256) void row_map_dilate_kernel(const unsigned char
     a = a > ia ? a : ia; z = z < iz ? z : iz;
     for (int k = (s0 + a) >> 6; k <= (s0 + z) >> 6; ++k) any |= in[k];
   }
-  out[b] = any ? 1 : 0;
+  return any ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void row_map_dilate_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, const MapGeo g) {
+  const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (b >= (g.M + 63) >> 6) return;
+  out[b] = row_map_dilate_at(in, b, g);
+}
+
+// ---- sparse forward: the same maps, read the other way -- byte b = 1: some row of block b of a tower activation is NEEDED.  The box-regression
+// and the MEH loss multiply by bbox_weights, which the assigner writes before the head runs and which is exactly 0 at every anchor that is not
+// positive: level 0 of the chain marks the pixel blocks that hold a weighted anchor (pixel row p owns the A anchors A p .. A p + A - 1 of the
+// level-major target rows), and every further level is the dilation above of the one before -- the MapGeo of a 3 x 3 / pad 1 conv is
+// symmetric, so "the rows a dgrad reaches from block b" is also "the rows whose forward reads block b".  maps[k] = D^k(maps[0]).
+struct FwdMapChain { unsigned char* m[8]; int n; };
+__global__ __launch_bounds__(256) void fwd_row_map_kernel(const float* __restrict__ bw, unsigned char* __restrict__ out, long long rows, int fpr) {
+  // one workgroup per block of 64 pixel rows: 64 * fpr contiguous floats (fpr = floats per pixel row, 4 * anchors: whole 16-B vectors)
+  const long long r0 = (long long)blockIdx.x * 64, r1 = r0 + 64 < rows ? r0 + 64 : rows;
+  const float4* const src = reinterpret_cast<const float4*>(bw + r0 * fpr);
+  const int n4 = (int)((r1 - r0) * (fpr >> 2));
+  int any = 0;
+  for (int i = (int)threadIdx.x; i < n4; i += 256) {
+    const float4 v = src[i];
+    any |= (v.x != 0.f || v.y != 0.f || v.z != 0.f || v.w != 0.f) ? 1 : 0;
+  }
+  any = __syncthreads_or(any);
+  if (threadIdx.x == 0) out[blockIdx.x] = any ? 1 : 0;
+}
+// ONE workgroup walks the whole chain: level k reads level k - 1 behind a barrier.  LDS_BLOCKS > 0: the two levels in flight live in the LDS
+// (a pyramid has ~1 400 blocks; a dependent global load per neighbour block and level made this launch 70 us), and every level is copied out
+// as it completes; 0: maps of more than LDS_BLOCKS bytes, level by level through global memory.
+template <int LDS_BLOCKS>
+__global__ __launch_bounds__(1024) void fwd_map_chain_kernel(const FwdMapChain c, const MapGeo g) {
+  const int nblk = (g.M + 63) >> 6;
+  if constexpr (LDS_BLOCKS > 0) {
+    __shared__ unsigned char buf[2][LDS_BLOCKS];
+    for (int b = (int)threadIdx.x; b < nblk; b += 1024) buf[0][b] = c.m[0][b];
+    __syncthreads();
+    for (int k = 1; k < c.n; ++k) {
+      const unsigned char* const in = buf[(k - 1) & 1];
+      unsigned char* const out = buf[k & 1];
+      for (int b = (int)threadIdx.x; b < nblk; b += 1024) {
+        const unsigned char v = row_map_dilate_at(in, b, g);
+        out[b] = v;
+        c.m[k][b] = v;
+      }
+      __syncthreads();
+    }
+  } else {
+    for (int k = 1; k < c.n; ++k) {
+      for (int b = (int)threadIdx.x; b < nblk; b += 1024) c.m[k][b] = row_map_dilate_at(c.m[k - 1], b, g);
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
 }
 
 // in_map[g] / out_map[g] of a (grouped) dgrad launch: writes every out_map from its in_map (a small launch of its own, ahead of the conv) and
@@ -1274,6 +1346,43 @@ static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map
     if (ngroups) { p.grp[g].omap = (const unsigned char*)out_map[g]; p.interleave = 1; }
     else p.omap = (const unsigned char*)out_map[g];
   }
+  return 0;
+}
+
+// the geometry the maps are defined on: x3, stride 1, same-size segments whose destination rows ARE the GEMM rows (a forward launch may
+// gather its source levels from anywhere: only the rows it stores are skipped by map)
+static int conv_map_geo(const ConvKParams& p, MapGeo& mg, bool dense_src) {
+  AOD_CHECK_ARG(p.x3 && p.stride == 1 && !p.out_f32 && !p.perm && !p.up_w, "conv (map): row-activity maps exist for x3 stride-1 launches with X-layout rows only");
+  AOD_CHECK_ARG((p.R - 1) * p.dil >= p.pad && (p.S - 1) * p.dil >= p.pad, "conv (map): padding beyond the filter");
+  memset(&mg, 0, sizeof(mg));
+  mg.nseg = p.nseg; mg.M = p.M; mg.R = p.R; mg.S = p.S; mg.pad = p.pad; mg.dil = p.dil;
+  for (int i = 0; i < p.nseg; ++i) {
+    const long long m0 = i ? p.seg_mend[i - 1] : 0;
+    AOD_CHECK_ARG(p.segH[i] == p.segOH[i] && p.segW[i] == p.segOW[i] && (!dense_src || p.seg_src0[i] == m0) && p.seg_dst0[i] == m0,
+                  "conv (map): segment %d is not a dense same-size map (the destination rows must be the GEMM rows)", i);
+    mg.segH[i] = p.segH[i]; mg.segW[i] = p.segW[i]; mg.seg_mend[i] = p.seg_mend[i];
+  }
+  return 0;
+}
+
+// omap[g] of a grouped FORWARD launch (sparse forward): the READY-MADE map of where member g's output is needed (aod_fwd_row_maps; null = a
+// dense member).  A dead tile stores zero rows whatever its bias.  The grouped forward has no residual, raw-sum (zraw) or fp32 destination,
+// and a mapped launch may carry neither a mask nor column sums (both belong to dgrad epilogues): those stay forbidden here.
+static int conv_fwd_map_setup(ConvKParams& p, int ngroups, const void* const* omap) {
+  bool any = false;
+  for (int g = 0; g < ngroups; ++g) any = any || omap[g];
+  if (!any || p.M == 0) return 0;
+  AOD_CHECK_ARG(!p.transposed, "conv_grouped (forward map): a dgrad descriptor -- its maps go through aod_conv2d_grouped_map");
+  AOD_CHECK_ARG(!p.pre_scale && !p.res && !p.post_scale && !p.zraw, "conv_grouped (forward map): scale / residual / raw-sum operands are not supported");
+  for (int g = 0; g < ngroups; ++g)
+    AOD_CHECK_ARG(!p.grp[g].mask && !p.grp[g].colsum, "conv_grouped (forward map): member %d carries a mask or column sums", g);
+  MapGeo mg;
+  const int rc = conv_map_geo(p, mg, false);
+  if (rc) return rc;
+  ConvKnobs kn;
+  if (kn.is(ConvKnobs::SPARSE_FWD, '0')) return 0;      // AOD_SPARSE_FWD=0: the maps exist, no tile is skipped (and the launch keeps the unmapped deal)
+  for (int g = 0; g < ngroups; ++g) p.grp[g].omap = (const unsigned char*)omap[g];
+  p.interleave = 1;
   return 0;
 }
 
@@ -1610,6 +1719,68 @@ extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, cons
                                   void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
                                   aod_stream_t stream) {
   return aod_conv2d_grouped_map(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, nullptr, nullptr, stream);
+}
+
+// aod_conv2d_grouped, forward, with a ready-made row-activity map per member (omap: ngroups pointers, null entries = dense members)
+extern "C" int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                          void* const* dst, const float* const* pre_shift, const void* const* omap, aod_stream_t stream) {
+  ConvKParams p;
+  ConvPlan pl;
+  int rc = conv_params_grouped(desc, ngroups, src, w_packed, dst, pre_shift, nullptr, nullptr, p);
+  if (rc) return rc;
+  if (p.M == 0) return 0;
+  rc = conv_plan(p, ngroups, false, pl);
+  if (rc) return rc;
+  if (omap && pl.kind == AOD_CONV_PLAN_IGEMM && pl.x3) {      // (the persistent kernel, AOD_X3P_GROUPED=1, skips bias-free dgrad tiles only: dense there)
+    rc = conv_fwd_map_setup(p, ngroups, omap);
+    if (rc) return rc;
+  }
+  return conv_launch(pl, p, nullptr, 0, (hipStream_t)stream);
+}
+
+// The row-activity maps of the sparse forward: maps[0] from the assigner's bbox_weights (fp32 [rows * anchors][4], level-major like the rows
+// of `desc`), maps[k] = the dilation of maps[k - 1] by the filter of `desc`, k < nmaps <= 8.  (rows + 63) / 64 bytes each.
+extern "C" int aod_fwd_row_maps(const aod_conv_desc_t* desc, const float* bbox_weights, int anchors, int nmaps, void* const* maps,
+                                aod_stream_t stream) {
+  AOD_CHECK_ARG(desc && bbox_weights && maps && anchors >= 1 && nmaps >= 1 && nmaps <= 8, "fwd_row_maps: null argument, or nmaps %d outside 1 .. 8", nmaps);
+  ConvKParams p;
+  memset(&p, 0, sizeof(p));
+  int rc = fill_params(desc, p);
+  if (rc) return rc;
+  AOD_CHECK_ARG(!p.transposed, "fwd_row_maps: a forward descriptor is expected");
+  MapGeo mg;
+  rc = conv_map_geo(p, mg, true);
+  if (rc) return rc;
+  if (p.M == 0) return 0;
+  FwdMapChain c;
+  memset(&c, 0, sizeof(c));
+  c.n = nmaps;
+  for (int k = 0; k < nmaps; ++k) {
+    AOD_CHECK_ARG(maps[k], "fwd_row_maps: map %d is null", k);
+    c.m[k] = (unsigned char*)maps[k];
+  }
+  AOD_CHECK_ARG(((uintptr_t)bbox_weights & 15) == 0, "fwd_row_maps: bbox_weights must be 16-byte aligned");
+  hipLaunchKernelGGL(fwd_row_map_kernel, dim3((p.M + 63) >> 6), dim3(256), 0, (hipStream_t)stream, bbox_weights, c.m[0], (long long)p.M, 4 * anchors);
+  AOD_LAUNCH_CHECK();
+  if (nmaps > 1) {
+    constexpr int LB = 16384;      // 2 x 16 KB of LDS: pyramids of up to 2^20 rows
+    if (((p.M + 63) >> 6) <= LB) hipLaunchKernelGGL(fwd_map_chain_kernel<LB>, dim3(1), dim3(1024), 0, (hipStream_t)stream, c, mg);
+    else hipLaunchKernelGGL(fwd_map_chain_kernel<0>, dim3(1), dim3(1024), 0, (hipStream_t)stream, c, mg);
+    AOD_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// conv_grouped_deal as data (host logic only): tile[b] / group[b] of block b of a grouped launch of `ngroups` members of `nwg` tiles each,
+// b < nwg * ngroups; mapped: whether a member carries a row-activity map.
+extern "C" int aod_conv2d_grouped_deal(int nwg, int ngroups, int mapped, int32_t* tile, int32_t* group) {
+  AOD_CHECK_ARG(nwg >= 1 && ngroups >= 1 && ngroups <= 4 && tile && group, "conv_grouped_deal: nwg %d, ngroups %d", nwg, ngroups);
+  for (int b = 0; b < nwg * ngroups; ++b) {
+    int t, g;
+    conv_grouped_deal(b, nwg, ngroups, mapped ? 1 : 0, t, g);
+    tile[b] = t; group[b] = g;
+  }
+  return 0;
 }
 
 extern "C" int aod_conv2d(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,

@@ -451,6 +451,7 @@ _S1_OF = {}      # data_ptr of a masked gradient handed to a residual branch -> 
 # (pad_cast_colsum), every tower dgrad hands the map of its dX on to the layer below, whose dgrad skips the tiles that only zero rows reach.
 _ROW_MAPS = {}
 MAP_LOG = None       # tests: a list that receives every (gradient rows shape, map) pair in the order the backward pass produced them
+FWD_MAP_LOG = None   # tests: a list that receives (members, output rows shape, per-member forward maps or None) of every paired tower launch
 
 
 def _map_of(dz):
@@ -848,8 +849,13 @@ class ConvPairFn(Function):
             rows.append(xL)
             wfs.append(PREP.get(convL.weight, None, cin, 0.0).wf)
             shifts.append(convL.bias.detach())
+        # sparse forward (hipops.sparse_fwd): fwd_map = where the outputs of the reg member and of the rider are needed; the cls member is dense
+        fmap = meta.get('fwd_map')
+        omaps = [None, fmap] + ([fmap] if rider is not None else []) if fmap is not None else None
+        if FWD_MAP_LOG is not None:
+            FWD_MAP_LOG.append((len(rows), (sum(s.rows for s in segs[0]), ho.width(O)), omaps))
         outs, y_segs = ho.conv2d_rows_grouped(rows, list(segs[0]), wfs, O, R, S, 1, meta['pad'], meta['dil'], pre_shifts=shifts, relu=True,
-                                              alg=(I, O))
+                                              alg=(I, O), omaps=omaps)
         if rider is not None:
             meta['rider_out'] = outs[2]
         ctx.meta, ctx.x_segs, ctx.y_segs, ctx.nl = meta, list(segs[0]), y_segs, nl
@@ -904,10 +910,12 @@ class ConvPairFn(Function):
         return (None, gws[0], gbs[0], gws[1], gbs[1]) + tuple(gxs)
 
 
-def conv_pair_act(xsA, xsB, convA, convB, sole_consumer=False, rider=None):
+def conv_pair_act(xsA, xsB, convA, convB, sole_consumer=False, rider=None, fwd_map=None):
     """cls / reg tower convs of one depth (ConvModule.conv holders: weight, bias, padding, dilation) on their own level lists; falls back to
     two conv_bn_act calls whenever the grouped form does not apply.  rider = (conv holder, input rows [M, C]): a third conv of the same shape
-    whose forward (no autograd) is computed in the same launch; then returns (ya, yb, rider output rows or None)."""
+    whose forward (no autograd) is computed in the same launch; then returns (ya, yb, rider output rows or None).
+    fwd_map (sparse forward, hipops.fwd_row_maps): row-activity map of where the outputs of convB and of the rider are NEEDED -- their other
+    256-row tiles come back as zero rows; convA stays dense.  Ignored (dense) where the grouped form or the rider does not apply."""
     import os
     wA, wB = convA.weight, convB.weight
     # (reference-precision mode: the grouped launch exists for the 256 x 256 tile only -- N % 256 == 0 and a deep filter)
@@ -926,6 +934,8 @@ def conv_pair_act(xsA, xsB, convA, convB, sole_consumer=False, rider=None):
         if (cl.weight.shape == wA.shape and cl.bias is not None and cl.padding == convA.padding and cl.dilation == convA.dilation
                 and cl.stride[0] == 1 and rider[1].dtype == torch.bfloat16):
             meta['rider'] = rider
+    if fwd_map is not None and ho.sparse_fwd() and 'rider' in meta and convA.stride[0] == 1 and torch.is_grad_enabled():
+        meta['fwd_map'] = fwd_map
     grad = torch.is_grad_enabled()
     if grad:
         meta['slot'] = [ActSlot(), ActSlot()]

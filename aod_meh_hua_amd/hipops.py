@@ -221,9 +221,11 @@ def conv2d_rows(x_rows, src_segs, w_packed, N, R, S, stride=1, pad=0, dil=1, *, 
     return (out, dst_segs, z) if save_z else (out, dst_segs)
 
 
-def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pre_shifts=None, relu=False, outs=None, alg=None):
+def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pre_shifts=None, relu=False, outs=None, alg=None, omaps=None):
     """G forward convs of identical geometry in ONE launch (aod_conv2d_grouped): xs / ws / pre_shifts / outs are lists of G row tensors
-    (inputs may be the same tensor), `src_segs` the shared segment list.  Returns (list of outputs, dst_segs)."""
+    (inputs may be the same tensor), `src_segs` the shared segment list.  Returns (list of outputs, dst_segs).
+    omaps (sparse forward): list of G row-activity maps of where each member's OUTPUT is needed (fwd_row_maps), None entries = dense members;
+    the tiles outside a member's map come back as zero rows (aod_conv2d_grouped_fwd_map)."""
     G = len(xs)
     Cin = xs[0].shape[1]
     dst_segs = out_segs(src_segs, R, S, stride, pad, dil)
@@ -235,13 +237,41 @@ def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pr
     for t in list(xs) + list(ws) + list(outs):
         ptr(t)                                   # (refuses CPU tensors)
     keep = [arr(xs), arr(ws), arr(outs), arr(pre_shifts) if pre_shifts is not None else None]
+    if omaps is not None and any(m is not None for m in omaps):
+        assert (len(omaps) == G and X3 and stride == 1 and all((a.B, a.H, a.W) == (b.B, b.H, b.W) for a, b in zip(src_segs, dst_segs))), \
+            'forward maps: x3 stride-1 launches between same-size maps'
+        for m in omaps:
+            assert m is None or (m.dtype == torch.uint8 and m.is_cuda and m.numel() == (rows + 63) // 64)
+        keep.append(arr(omaps))
+        fn = lambda: call('aod_conv2d_grouped_fwd_map', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], keep[4], stream())
+    else:
+        fn = lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], None, None, stream())
     if PROFILE is None:
-        call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], None, None, stream())
+        fn()
     else:                                       # (profiling: the G groups count as G launches' worth of FLOPs in one record)
-        for _ in range(1):
-            _prof('fwd', d, lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], None, None, stream()),
-                  (alg[0] * G, alg[1]) if alg is not None else (Cin * G, N))
+        _prof('fwd', d, fn, (alg[0] * G, alg[1]) if alg is not None else (Cin * G, N))
     return outs, dst_segs
+
+
+def sparse_fwd():
+    """Sparse forward of the reg / MEH towers in training (reference-precision mode): the positives are known before the head runs, and the
+    towers' grouped launches skip the tiles outside their receptive field (fwd_row_maps).  AOD_SPARSE_FWD=0: the maps are still built and
+    passed, the library skips no tile.  Deterministic mode may use it (the forward has no column sums)."""
+    return X3
+
+
+def fwd_row_maps(bbox_weights, segs, anchors, Cin, N, R, S, pad, dil, nmaps):
+    """The map chain of the sparse forward (aod_fwd_row_maps): [m0, D(m0), D(D(m0)), ...], `nmaps` uint8 maps of one byte per 64 pyramid rows.
+    m0 marks the blocks that own an anchor with a non-zero bbox weight (bbox_weights: fp32 [rows * anchors, 4], level-major like `segs`);
+    D is the dilation of a (R x S, pad, dil) stride-1 conv, the rule of the sparse backward's maps."""
+    rows = sum(s.rows for s in segs)
+    assert bbox_weights.dtype == torch.float32 and bbox_weights.is_contiguous() and bbox_weights.numel() == rows * anchors * 4
+    d = make_desc(Cin, N, R, S, 1, pad, dil, segs, segs, False, True, False)
+    buf = torch.empty(nmaps, (rows + 63) // 64, dtype=torch.uint8, device=bbox_weights.device)
+    maps = list(buf.unbind(0))
+    keep = (C.c_void_p * nmaps)(*[m.data_ptr() for m in maps])
+    call('aod_fwd_row_maps', C.byref(d), ptr(bbox_weights), anchors, nmaps, keep, stream())
+    return maps
 
 
 def sparse_bwd():

@@ -175,8 +175,10 @@ class L_AnchorHead(BaseModule):
         if self._can_defer_avg:
             from ... import functional as AF
             want_fused = AF.LOSS_LEVELS
-        labels_list, lw_list, bt_list, bw_list, num_pos, nla = self.get_targets_batch(featmap_sizes, img_metas, gt_bboxes, gt_labels, device,
-                                                                                      raw_num_pos=True)
+        targets = kwargs.pop('targets', None)          # (a head that assigned before its forward -- the sparse forward -- hands the result in)
+        if targets is None:
+            targets = self.get_targets_batch(featmap_sizes, img_metas, gt_bboxes, gt_labels, device, raw_num_pos=True)
+        labels_list, lw_list, bt_list, bw_list, num_pos, nla = targets
         assert not self.sampling
         fused = None
         if want_fused:                      # (heads on the HIP loss kernels)

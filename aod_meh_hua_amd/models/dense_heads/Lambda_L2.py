@@ -48,32 +48,71 @@ class Lambda_L2Net(L_AnchorHead):
 
     # ------------------------------------------------------------------ forward
     def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        outs = self.forward(x, **kwargs)
+        # sparse forward: the assigner reads anchors and ground truth only, so the targets -- and with them the rows whose box / MEH loss
+        # weights are not zero -- are known BEFORE the head runs: assign once here, hand the map chain to forward() and the targets to loss()
+        prepare = getattr(self, '_sparse_fwd_prepare', None)
+        targets, fwd_maps = prepare(x, img_metas, gt_bboxes, gt_labels, **kwargs) if prepare is not None else (None, None)
+        outs = self.forward(x, **kwargs) if fwd_maps is None else self.forward(x, fwd_maps=fwd_maps, **kwargs)
         loss_inputs = outs + (None, gt_bboxes, gt_labels, img_metas)
+        if targets is not None:
+            kwargs = dict(kwargs, targets=targets)
         return self.loss(*loss_inputs, gt_bboxes_ignore=gt_bboxes_ignore, **kwargs)
+
+    def _sparse_fwd_prepare(self, x, img_metas, gt_bboxes, gt_labels, **kwargs):
+        """-> (the assigner's targets, [m0, F_n, ..., F_1]) or (None, None): the dense path.  F_k = where the output of tower layer k is needed
+        (hipops.fwd_row_maps).  Taken only in the live training branch whose readers of bbox_preds / L_scores all multiply by bbox_weights
+        (DESIGN 3a): L1 box loss, an MEH form of hipops.MEH_FORMS, the MEH tower riding in the paired launches."""
+        from ... import hipops as ho
+        x = list(x)
+        n = len(self.reg_convs)
+        ok = (ho.sparse_fwd() and torch.is_grad_enabled() and self.training and kwargs.get('Labeled', True) and not kwargs.get('Pseudo', False)
+              and type(self.loss_bbox).__name__ == 'L1Loss' and self._meh_form in ('l2', 'l1', 'msle') and self._rides(x)
+              and 1 <= n == len(self.cls_convs) <= 7 and all(m.with_activation for m in list(self.cls_convs) + list(self.reg_convs))
+              and all(m.conv.weight.shape[2:] == (3, 3) and m.conv.padding == (1, 1) and m.conv.dilation == (1, 1) and m.conv.stride == (1, 1)
+                      for m in list(self.reg_convs) + list(self.L_convs))
+              and self.retina_reg.weight.shape[2:] == (3, 3) and self.retina_L.weight.shape[2:] == (3, 3))
+        if not ok:
+            return None, None
+        featmap_sizes = [tuple(f.shape[-2:]) for f in x]
+        targets = self.get_targets_batch(featmap_sizes, img_metas, gt_bboxes, gt_labels, x[0].device, raw_num_pos=True)
+        bw = AF.dense_concat([t.reshape(-1, 4) for t in targets[3]])
+        if bw is None or bw.dtype != torch.float32:
+            return targets, None
+        B = x[0].shape[0]
+        segs = AF.dense_segs([ho.Seg(B, h, w, 0) for h, w in featmap_sizes])
+        c = self.feat_channels
+        return targets, ho.fwd_row_maps(bw, segs, self.num_anchors, ho.width(c), c, 3, 3, 1, 1, n + 1)
+
+    def _rides(self, feats):
+        """whether the MEH tower's forward rides in the paired tower launches of forward()"""
+        import os
+        return (torch.is_grad_enabled() and self.training and os.environ.get('AOD_MEH_RIDER', '1') != '0'
+                and len(self.L_convs) == len(self.cls_convs) and all(m.with_activation for m in self.L_convs)
+                and feats[0].dtype == torch.bfloat16)
 
     def forward_train_L(self, prev_loss, head_out, x, **kwargs):
         L_scores = self.forward_L(x, head_out, **kwargs)
         return self.loss_L(L_scores, head_out, prev_loss, **kwargs)
 
-    def forward(self, feats, **kwargs):
-        """Lambda_L2.py:79-94, all levels per launch.  Returns (cls_scores[L], bbox_preds[L]) fp32 [B, A*C, h, w]."""
+    def forward(self, feats, fwd_maps=None, **kwargs):
+        """Lambda_L2.py:79-94, all levels per launch.  Returns (cls_scores[L], bbox_preds[L]) fp32 [B, A*C, h, w].
+        fwd_maps (_sparse_fwd_prepare): the reg tower and the MEH rider compute only the tiles their losses read; their other rows -- and the
+        bbox_preds / L_scores above them -- hold finite values that every reader weights by zero."""
         feats = list(feats)
         cls_feat, reg_feat = (list(t) for t in zip(*[AF.fork(f, 2) for f in feats]))      # (every level feeds both towers)
         if len(self.cls_convs) == len(self.reg_convs) and all(m.with_activation for m in list(self.cls_convs) + list(self.reg_convs)):
             # the two towers advance together: one grouped launch per depth (functional.ConvPairFn)
             # training: the MEH tower's forward (forward_L below, on the same -- detached -- pyramid, run by train_step_L right after this pass)
             # rides in the same grouped launches; forward_L then only records its autograd nodes around the stored outputs
-            import os
-            ride = (torch.is_grad_enabled() and self.training and os.environ.get('AOD_MEH_RIDER', '1') != '0'
-                    and len(self.L_convs) == len(self.cls_convs) and all(m.with_activation for m in self.L_convs)
-                    and feats[0].dtype == torch.bfloat16)
+            ride = self._rides(feats)
+            nl = len(self.cls_convs)
             self._L_pre = None
             L_rows, L_outs = (AF.multi_rows([f.detach() for f in feats])[0] if ride else None), []
             for i, (cc, rc) in enumerate(zip(self.cls_convs, self.reg_convs)):          # every tower activation has exactly one consumer
                 if L_rows is not None:
                     cls_feat, reg_feat, L_rows = AF.conv_pair_act(cls_feat, reg_feat, cc.conv, rc.conv, sole_consumer=i > 0,
-                                                                  rider=(self.L_convs[i].conv, L_rows))
+                                                                  rider=(self.L_convs[i].conv, L_rows),
+                                                                  fwd_map=fwd_maps[nl - i] if fwd_maps is not None else None)
                     L_outs.append(L_rows)
                 else:
                     cls_feat, reg_feat = AF.conv_pair_act(cls_feat, reg_feat, cc.conv, rc.conv, sole_consumer=i > 0)

@@ -214,6 +214,21 @@ int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void*
                            const float* const* pre_shift, const void* const* mask, float* const* colsum, const void* const* in_map,
                            void* const* out_map, aod_stream_t stream);
 
+/* Sparse forward (reference-precision mode, the reg and MEH towers in training).  The box-regression and the MEH loss multiply by the assigner's
+ * bbox_weights, 0 at every anchor that is not positive, so those towers' activations are read only inside the receptive field of the positives.
+ * aod_fwd_row_maps writes the chain: maps[0] byte b = 1 when a pixel row of 64 b .. 64 b + 63 owns an anchor with a non-zero weight (pixel row p
+ * owns rows anchors * p .. anchors * p + anchors - 1 of bbox_weights, fp32 [.][4], level-major like the rows of `desc`), maps[k] = the dilation
+ * of maps[k - 1] by the rule of aod_conv2d_ws_map (desc: a forward x3 stride-1 descriptor between dense same-size maps; nmaps <= 8).
+ * aod_conv2d_grouped_fwd_map is aod_conv2d_grouped (forward) with a READY-MADE map per member (NULL entries: dense members): a 256-row tile
+ * whose blocks are all 0 loads nothing, multiplies nothing and stores ZERO rows -- not relu(bias) --; live tiles run the dense code on the
+ * same operands: same bits.  AOD_SPARSE_FWD=0: no tile is skipped.  Launches on the persistent kernel (AOD_X3P_GROUPED=1) stay dense.
+ * aod_conv2d_grouped_deal gives the block -> (tile, member) assignment of a grouped launch as data: mapped = 0 the member-major XCD-contiguous
+ * order, mapped = 1 (some member carries a map, forward or dgrad) the even deal over the eight blockIdx % 8 classes. */
+int aod_fwd_row_maps(const aod_conv_desc_t* desc, const float* bbox_weights, int anchors, int nmaps, void* const* maps, aod_stream_t stream);
+int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
+                               const float* const* pre_shift, const void* const* omap, aod_stream_t stream);
+int aod_conv2d_grouped_deal(int nwg, int ngroups, int mapped, int32_t* tile, int32_t* group);
+
 /* replaces: the weight-gradient half of autograd's conv backward (cuDNN wgrad) for the same
  * call sites.  dw_f32 is [N][R][S][C] fp32 and is ACCUMULATED into (caller zeroes it);
  * x: forward input [rows, C] bf16; dz: [rows_out, N] bf16. */
