@@ -38,6 +38,16 @@ class ConvPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('kind', 'bm', 'bn', 'nt', 'ops', 'stages', 'x3', 'grouped', 'ksplit', 'taps', 'wide', 'pre', 'lat', 'grid')]
 
 
+class WgradPlan(C.Structure):
+    """aod_wgrad_plan_t: the kernel and the splits a weight-gradient launch runs on (aod_conv2d_wgrad_plan_ex)"""
+    _fields_ = ([(n, C.c_int32) for n in ('form', 'wide', 'waves', 'tile', 'x3', 'sparse', 'grouped', 'threads', 'lds_bytes', 'grid')]
+                + [(n, C.c_int32 * 4) for n in ('tiles_n', 'tiles_k', 'splits', 'rows_per_split')])
+
+
+WGRAD_ATOMIC, WGRAD_GROUPED = 1, 2
+WGRAD_HAS_MAP = lambda g: 16 << g      # flag of aod_conv2d_wgrad_plan_ex: member g carries a row-activity map
+
+
 P, I32, I64, F32, U64, SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     'aod_version': (C.c_int, []),
@@ -78,6 +88,7 @@ _SIGS = {
     'aod_conv2d_wgrad_group_plan': (C.c_int, [P, I32, P]),
     'aod_conv2d_wgrad_grouped': (C.c_int, [P, I32, P, P, P, P, P, P, P]),
     'aod_conv2d_wgrad_plan': (C.c_int, [P, I32, P, P, P]),
+    'aod_conv2d_wgrad_plan_ex': (C.c_int, [P, I32, C.c_uint, C.POINTER(WgradPlan)]),
     'aod_conv2d_wgrad_grouped_map': (C.c_int, [P, I32, P, P, P, P, P, P, P, P]),
     'aod_unpack_wgrad_slabs_grouped': (C.c_int, [I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_unpack_wgrad_slabs': (C.c_int, [P, I32, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P]),

@@ -258,9 +258,29 @@ int aod_conv2d_wgrad_grouped(const aod_conv_desc_t* const* descs, int n, const v
 int aod_conv2d_wgrad_grouped_map(const aod_conv_desc_t* const* descs, int n, const void* const* x, const void* const* dz, float* const* slabs,
                                  const int32_t* nslabs, const int64_t* slab_stride, const void* const* row_table, const void* const* dz_map,
                                  aod_stream_t stream);
-/* The split plan of a weight-gradient launch as data (host logic only): n = 1 -- aod_conv2d_wgrad_slabs(_map); n = 2 .. 4 -- the grouped launch.
- * form: 0 = 128 x 128 tile, 1 = 256 x 256, 2 / 3 = the wide x3 forms of 8 / 4 waves; split s of member g covers GEMM rows
- * [s * rows_per_split[g], (s + 1) * rows_per_split[g]).  Returns 1 when the members cannot share a grid. */
+/* The plan of a weight-gradient launch as data -- the decision the launch itself follows.  Host logic only: nothing is enqueued and no device
+ * is needed.  flags: AOD_WGRAD_ATOMIC -- aod_conv2d_wgrad (one member, fp32 atomics) instead of the slab form; AOD_WGRAD_GROUPED -- the
+ * grouped launch and its planner (implied for n > 1; one member goes through it as well, with other splits than aod_conv2d_wgrad_slabs);
+ * AOD_WGRAD_HAS_MAP(g) -- member g carries a row-activity map of its dZ (the plan drops it where the launch would: not x3, non-dense dZ
+ * segments, AOD_SPARSE_BWD=0).
+ * form: 0 = 128 x 128 tile, 1 = 256 x 256, 2 / 3 = the wide x3 forms of 8 / 4 waves.  The kernel instance: wide 0 conv_wgrad(_grouped)_kernel
+ * <waves, tile, tile, x3, sparse>, wide 1 conv_wgrad(_grouped)_x3w_kernel<waves, tile, sparse> (tile in units of 128 columns), on `grid`
+ * workgroups of `threads` threads with lds_bytes of dynamic LDS.  Member g: tiles_n[g] x tiles_k[g] tiles, each over splits[g] splits;
+ * split s covers GEMM rows [s * rows_per_split[g], (s + 1) * rows_per_split[g]).
+ * Returns 1 (plan not valid) when the members cannot share a grid, -1 on argument errors.
+ * aod_conv2d_wgrad_splits, aod_conv2d_wgrad_group_plan and aod_conv2d_wgrad_plan report parts of this plan; aod_conv2d_wgrad_splits still
+ * returns 0 for a descriptor without rows and now leaves "empty member" in aod_last_error when it does. */
+enum { AOD_WGRAD_ATOMIC = 1, AOD_WGRAD_GROUPED = 2 };
+#define AOD_WGRAD_HAS_MAP(g) (16u << (g))
+typedef struct {
+  int32_t form;
+  int32_t wide, waves, tile, x3, sparse, grouped;
+  int32_t threads, lds_bytes, grid;
+  int32_t tiles_n[4], tiles_k[4], splits[4], rows_per_split[4];
+} aod_wgrad_plan_t;
+int aod_conv2d_wgrad_plan_ex(const aod_conv_desc_t* const* descs, int n, unsigned flags, aod_wgrad_plan_t* out);
+/* The earlier, shorter report of the same plan (flags 0), kept with its signature for its callers: form, and per member splits and
+ * rows_per_split.  n = 1 -- aod_conv2d_wgrad_slabs(_map); n = 2 .. 4 -- the grouped launch.  Same return values. */
 int aod_conv2d_wgrad_plan(const aod_conv_desc_t* const* descs, int n, int32_t* form, int32_t* splits, int32_t* rows_per_split);
 int aod_conv2d_wgrad_slabs_map(const aod_conv_desc_t* desc, const void* x, const void* dz, float* slabs, int nslabs, int64_t slab_stride,
                                const void* row_table, const void* dz_map, aod_stream_t stream);

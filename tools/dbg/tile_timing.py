@@ -1,6 +1,9 @@
 """Per-tile phase timing of conv_igemm_kernel (debug build with -DAOD_TILE_TIMING).
   build here:   python tools/dbg/tile_timing.py build
-  run on GPU:   AOD_HIP_LIB=tools/dbg/_build/libaodhip_dbg.so python tools/dbg/tile_timing.py run B H W C N RS [res]"""
+  run on GPU:   AOD_HIP_LIB=tools/dbg/_build/libaodhip_dbg.so python tools/dbg/tile_timing.py run B H W C N RS [res]
+`build noepi` adds the weight-gradient ablation -DAOD_WGRAD_NO_EPI, which csrc/conv_wgrad.hip reads (every source of csrc/ is compiled with
+the flags; the stamps themselves live in csrc/conv.hip).  `build notload` defines AOD_WGRAD_NO_TLOAD, which no source tests any more: that
+build equals the plain one."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, 'tools', 'dbg', '_build')
