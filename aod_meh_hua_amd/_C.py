@@ -79,6 +79,9 @@ _SIGS = {
     'aod_fwd_row_maps': (C.c_int, [C.POINTER(ConvDesc), P, I32, I32, P, P]),
     'aod_conv2d_grouped_fwd_map': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P]),
     'aod_conv2d_grouped_deal': (C.c_int, [I32, I32, I32, P, P]),
+    'aod_conv2d_grouped_map_order': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P, P, P, P]),
+    'aod_conv2d_grouped_fwd_map_order': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P]),
+    'aod_conv2d_tile_order': (C.c_int, [I32, I32, I32, P, P, P]),
     'aod_halo_conv3x3_applies': (C.c_int, [C.POINTER(ConvDesc)]),
     'aod_halo_conv3x3': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P]),
     'aod_conv2d_wgrad': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P]),

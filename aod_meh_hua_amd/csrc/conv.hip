@@ -39,6 +39,8 @@ __device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d) {
 // member on the even classes only), so the member order turns by one with every eight blocks.  Any 64 consecutive tiles of a member put 8 +- 1
 // on each class.  Placement only (which XCD runs a block is a speed heuristic): nothing depends on it for correctness.  (Measured, docs/LAB_NOTES.md
 // section 22: the mapped forward runs in two thirds of the dense time; the paired dgrad stays within 4 % of its dense time under either order.)
+// Since the list below this is the FALLBACK of mapped launches (AOD_TILE_ORDER=0, callers without a list): it levels the live blocks per XCD,
+// not per CU -- a dead block takes a CU in dispatch order and leaves it empty behind it (section 23).
 __host__ __device__ __forceinline__ void conv_grouped_deal(int bid, int nwg, int ngroups, int mapped, int& tile, int& group) {
   if (!mapped) {
     const int wg = xcd_swizzle(bid, nwg * ngroups);
@@ -48,6 +50,29 @@ __host__ __device__ __forceinline__ void conv_grouped_deal(int bid, int nwg, int
   tile = bid / ngroups;
   const int turn = (ngroups & 1) ? 0 : (tile * ngroups) >> 3;
   group = (bid - tile * ngroups + turn) % ngroups;
+}
+
+// ---- the block order of a mapped grouped launch as a LIST (ConvKParams.order): which tiles are live is device data, so a small launch that
+// reads the maps (tile_order_kernel, next to where they are written) builds, per launch, a permutation of the ngroups * nwg entries
+// member * nwg + tile.  The entries are ranked member-major (member, then tile), the live ones (a member without a map: all of them) and
+// the dead ones apart; conv_tile_order_slot is the rule that places them:
+//   live entry of rank k  -> the block b with xcd_swizzle(b, nlive) = k: the live entries fill the blocks [0, nlive), every blockIdx % 8 class
+//                            (XCD) takes a CONTIGUOUS range of the member-major ranking, nlive / 8 of them +- 1 -- one member's tiles follow
+//                            each other inside a class, so an XCD is through with one packed filter before it touches the next
+//   dead entry of rank k  -> block nlive + k: behind every live one, where its zero stores no longer stand in the dispatch order between them
+__host__ __device__ __forceinline__ int conv_tile_live(const unsigned char* map, int tile_m, int bm, int M) {
+  if (!map) return 1;
+  const int m0 = tile_m * bm, mend = m0 + bm < M ? m0 + bm : M;
+  int any = 0;
+  for (int b = m0 >> 6; b <= (mend - 1) >> 6; ++b) any |= map[b];
+  return any ? 1 : 0;
+}
+__host__ __device__ __forceinline__ int conv_tile_order_slot(int live, int rank, int nlive) {
+  if (!live) return nlive + rank;
+  const int q = nlive >> 3, r = nlive & 7, head = r * (q + 1);      // (the inverse of xcd_swizzle(., nlive))
+  if (rank < head) { const int c = rank / (q + 1); return c + 8 * (rank - c * (q + 1)); }
+  const int c = (rank - head) / q;                                   // (rank >= head with rank < nlive: q >= 1)
+  return r + c + 8 * (rank - head - c * q);
 }
 
 // OPS: which optional epilogue operands the instance supports -- 0 none, 1 ReLU mask only, 2 residual and mask (their prefetch registers
@@ -90,7 +115,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
   // class-major launches keep the round-robin block -> XCD assignment: the classes differ in work (1 / 2 / 2 / 4 taps of a 3x3, 1 / 0 / 0 / 0
   // of a 1x1) and contiguous per-XCD tile ranges would hand whole classes to single XCDs
   int wg;
-  if (!p.perm) wg = xcd_swizzle(blockIdx.x, nwg * (GROUPED ? p.ngroups : p.ksplit));
+  if (GROUPED && p.order) {
+    // mapped grouped launch with a device-built order (conv_tile_order_slot): one scalar load; the entry decodes like a swizzled index below
+    // (clamped: a list the builder has not written must not send a block outside the tensors)
+    const unsigned e = (unsigned)p.order[blockIdx.x], last = (unsigned)(nwg * p.ngroups - 1);
+    wg = (int)(e < last ? e : last);
+  }
+  else if (!p.perm) wg = xcd_swizzle(blockIdx.x, nwg * (GROUPED ? p.ngroups : p.ksplit));
   else if ((nwg & 31) == 0) {
     // ... but inside each quarter of the tile range (~ one class) every XCD still takes a contiguous chunk (neighbouring column tiles
     // share their A rows in that XCD's L2), and the quarters are interleaved in launch order
@@ -99,7 +130,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
   } else wg = blockIdx.x;
   // (grouped launches with a row-activity map, forward or dgrad: the even deal of conv_grouped_deal instead)
   int tile = wg % nwg, zz = wg / nwg;
-  if (GROUPED && p.interleave) conv_grouped_deal(blockIdx.x, nwg, p.ngroups, 1, tile, zz);
+  if (GROUPED && p.interleave && !p.order) conv_grouped_deal(blockIdx.x, nwg, p.ngroups, 1, tile, zz);
   const int kz = GROUPED ? 0 : zz;           // kz: which slice of the K-steps (split-K launches)
   // grouped launch: `ngroups` convolutions of identical geometry (the cls / reg / evidence towers at one depth) share one grid, so
   // that their tiles fill whole rounds of the CUs together; group = which operand set this workgroup uses
@@ -138,6 +169,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
           const int r = i / cpr, c = i - r * cpr;
           *reinterpret_cast<bf16x8*>(yz + (long long)r * NPz + c * 8) = z;
         }
+#ifdef AOD_TILE_TIMING
+        // a dead block: end stamp behind its acknowledged stores, where it ran, what it was (11: dead flag, 14: tile | member << 32)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        TSTAMP(6);
+        if (g_tile_stamps && threadIdx.x == 0) {
+          g_tile_stamps[(size_t)blockIdx.x * 16 + 7] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
+          g_tile_stamps[(size_t)blockIdx.x * 16 + 11] = 1ull;
+          g_tile_stamps[(size_t)blockIdx.x * 16 + 14] = ((unsigned long long)gi << 32) | (unsigned)tile;
+          g_tile_stamps[(size_t)blockIdx.x * 16 + 15] = wall_clock64();
+        }
+#endif
         return;
       }
     }
@@ -874,6 +917,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
       else atomicAdd(g_colsum + n0 + t, s);
     }
   }
+#ifdef AOD_TILE_TIMING
+  // the block's last stamp, behind the column sums (15), and what it was (14: tile | member << 32)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (g_tile_stamps && threadIdx.x == 0) g_tile_stamps[(size_t)blockIdx.x * 16 + 14] = ((unsigned long long)gi << 32) | (unsigned)tile;
+  TSTAMP(15);
+#endif
 }
 
 #undef g_y
@@ -1191,9 +1241,96 @@ __global__ __launch_bounds__(1024) void fwd_map_chain_kernel(const FwdMapChain c
   }
 }
 
+// ---- the list of a mapped grouped launch (ConvKParams.order, conv_tile_order_slot).  ONE workgroup: (dgrad launches) first the dilation of
+// every member's incoming map, in place of the row_map_dilate_kernel launches; then, over the entries e = member * tiles + tile in
+// member-major order, the live count, and a block-wide scan that gives every entry its rank among the live or the dead ones.
+struct TileOrderArgs {
+  const unsigned char* omap[4];      // per member: the map that decides its tiles (null: every tile is live)
+  const unsigned char* dil_in[4];    // per member, optional: dil_out = dilation of dil_in, written before the list
+  unsigned char* dil_out[4];
+  int* order;
+  int ngroups, tiles_m, tiles_n, bm, M;
+};
+__host__ __device__ __forceinline__ int tile_order_live(const TileOrderArgs& a, int e) {
+  const int nwg = a.tiles_m * a.tiles_n, g = e / nwg, tile_m = (e - g * nwg) / a.tiles_n;
+  const unsigned char* const m = g == 0 ? a.omap[0] : (g == 1 ? a.omap[1] : (g == 2 ? a.omap[2] : a.omap[3]));
+  return conv_tile_live(m, tile_m, a.bm, a.M);
+}
+__global__ __launch_bounds__(1024) void tile_order_kernel(const TileOrderArgs a, const MapGeo g) {
+  __shared__ int wcnt[16];
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int nblk = (g.M + 63) >> 6;
+  bool dilated = false;
+  for (int m = 0; m < a.ngroups; ++m) {
+    const unsigned char* const in = m == 0 ? a.dil_in[0] : (m == 1 ? a.dil_in[1] : (m == 2 ? a.dil_in[2] : a.dil_in[3]));
+    unsigned char* const out = m == 0 ? a.dil_out[0] : (m == 1 ? a.dil_out[1] : (m == 2 ? a.dil_out[2] : a.dil_out[3]));
+    if (!in) continue;
+    dilated = true;
+    for (int b = t; b < nblk; b += 1024) out[b] = row_map_dilate_at(in, b, g);
+  }
+  if (dilated) { __threadfence_block(); __syncthreads(); }
+  const int total = a.ngroups * a.tiles_m * a.tiles_n;
+  int nlive = 0;
+  for (int base = 0; base < total; base += 1024) {
+    const int e = base + t;
+    nlive += __syncthreads_count(e < total && tile_order_live(a, e));
+  }
+  int live_before = 0;            // live entries in the chunks behind us
+  for (int base = 0; base < total; base += 1024) {
+    const int e = base + t;
+    const int live = (e < total && tile_order_live(a, e)) ? 1 : 0;
+    const unsigned long long bal = __ballot(live);
+    if (lane == 0) wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = __popcll(bal & ((1ull << lane) - 1ull)), chunk = 0;
+    for (int w = 0; w < 16; ++w) { before += w < wave ? wcnt[w] : 0; chunk += wcnt[w]; }
+    if (e < total) {
+      const int rank = live ? live_before + before : (base - live_before) + (t - before);
+      a.order[conv_tile_order_slot(live, rank, nlive)] = e;
+    }
+    live_before += chunk;
+    __syncthreads();
+  }
+}
+// the same list on the host (maps in host memory): aod_conv2d_tile_order
+static void tile_order_host(const TileOrderArgs& a, int* order) {
+  const int total = a.ngroups * a.tiles_m * a.tiles_n;
+  int nlive = 0;
+  for (int e = 0; e < total; ++e) nlive += tile_order_live(a, e);
+  int nl = 0, nd = 0;
+  for (int e = 0; e < total; ++e) {
+    const int live = tile_order_live(a, e);
+    order[conv_tile_order_slot(live, live ? nl : nd, nlive)] = e;
+    (live ? nl : nd) += 1;
+  }
+}
+// whether the launch takes a list: a caller's buffer, a map on some member, the 256 x 256 grouped tile, and not AOD_TILE_ORDER=0
+static bool tile_order_applies(const ConvKParams& p, const ConvPlan& pl, const void* order) {
+  if (!order || !p.interleave || pl.kind != AOD_CONV_PLAN_IGEMM || !pl.grouped || !pl.x3 || pl.bm != 256 || pl.bn != 256) return false;
+  ConvKnobs kn;
+  return !kn.is(ConvKnobs::TILE_ORDER, '0');
+}
+static int tile_order_launch(ConvKParams& p, const MapGeo& mg, int ngroups, const void* const* dil_in, void* const* dil_out, int* order, hipStream_t st) {
+  TileOrderArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int g = 0; g < ngroups; ++g) {
+    a.omap[g] = p.grp[g].omap;
+    if (dil_in && dil_in[g]) { a.dil_in[g] = (const unsigned char*)dil_in[g]; a.dil_out[g] = (unsigned char*)dil_out[g]; }
+  }
+  a.order = order; a.ngroups = ngroups; a.bm = 256; a.M = p.M;
+  a.tiles_m = (p.M + 255) / 256; a.tiles_n = (p.N + 255) / 256;
+  AOD_CHECK_ARG(((uintptr_t)order & 3) == 0, "conv (tile order): the list must be 4-byte aligned");
+  hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, st, a, mg);
+  AOD_LAUNCH_CHECK();
+  p.order = order;
+  return 0;
+}
+
 // in_map[g] / out_map[g] of a (grouped) dgrad launch: writes every out_map from its in_map (a small launch of its own, ahead of the conv) and
 // hands the conv kernel the OUT map of each member whose zero tiles are safe to skip.  ngroups = 0: the plain launch (p.omap).
-static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map, void* const* out_map, hipStream_t st) {
+// order (grouped launches of the 256 x 256 tile, optional): the list of the launch is built by the same small launch (tile_order_kernel).
+static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map, void* const* out_map, hipStream_t st,
+                          const ConvPlan* pl = nullptr, int* order = nullptr) {
   const int ng = ngroups ? ngroups : 1;
   bool any = false;
   for (int g = 0; g < ng; ++g) {
@@ -1217,8 +1354,6 @@ static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map
   const bool dense = kn.is(ConvKnobs::SPARSE_BWD, '0');      // AOD_SPARSE_BWD=0: the maps are still written, no tile is skipped
   for (int g = 0; g < ng; ++g) {
     if (!in_map[g]) continue;
-    hipLaunchKernelGGL(row_map_dilate_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, (const unsigned char*)in_map[g], (unsigned char*)out_map[g], mg);
-    AOD_LAUNCH_CHECK();
     // a skipped tile stores zeros and sends no column sums: only where the epilogue of a zero accumulator IS zero (no bias / scale / residual)
     // and the column sums are atomics (deterministic mode expects a partial row from every tile: it stays dense)
     const float* const shift = ngroups ? p.grp[g].pre_shift : p.pre_shift;
@@ -1227,6 +1362,13 @@ static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map
     if (!skip_ok) continue;
     if (ngroups) { p.grp[g].omap = (const unsigned char*)out_map[g]; p.interleave = 1; }
     else p.omap = (const unsigned char*)out_map[g];
+  }
+  // the maps themselves: one launch with the list of the conv launch behind them, or a launch per mapped member
+  if (ngroups && pl && tile_order_applies(p, *pl, order)) return tile_order_launch(p, mg, ngroups, in_map, out_map, order, st);
+  for (int g = 0; g < ng; ++g) {
+    if (!in_map[g]) continue;
+    hipLaunchKernelGGL(row_map_dilate_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, (const unsigned char*)in_map[g], (unsigned char*)out_map[g], mg);
+    AOD_LAUNCH_CHECK();
   }
   return 0;
 }
@@ -1250,7 +1392,7 @@ static int conv_map_geo(const ConvKParams& p, MapGeo& mg, bool dense_src) {
 // omap[g] of a grouped FORWARD launch (sparse forward): the READY-MADE map of where member g's output is needed (aod_fwd_row_maps; null = a
 // dense member).  A dead tile stores zero rows whatever its bias.  The grouped forward has no residual, raw-sum (zraw) or fp32 destination,
 // and a mapped launch may carry neither a mask nor column sums (both belong to dgrad epilogues): those stay forbidden here.
-static int conv_fwd_map_setup(ConvKParams& p, int ngroups, const void* const* omap) {
+static int conv_fwd_map_setup(ConvKParams& p, int ngroups, const void* const* omap, hipStream_t st, const ConvPlan& pl, int* order) {
   bool any = false;
   for (int g = 0; g < ngroups; ++g) any = any || omap[g];
   if (!any || p.M == 0) return 0;
@@ -1265,6 +1407,7 @@ static int conv_fwd_map_setup(ConvKParams& p, int ngroups, const void* const* om
   if (kn.is(ConvKnobs::SPARSE_FWD, '0')) return 0;      // AOD_SPARSE_FWD=0: the maps exist, no tile is skipped (and the launch keeps the unmapped deal)
   for (int g = 0; g < ngroups; ++g) p.grp[g].omap = (const unsigned char*)omap[g];
   p.interleave = 1;
+  if (tile_order_applies(p, pl, order)) return tile_order_launch(p, mg, ngroups, nullptr, nullptr, order, st);
   return 0;
 }
 
@@ -1579,9 +1722,12 @@ extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const
 
 // aod_conv2d_grouped with per-member row-activity maps (in_map / out_map: arrays of ngroups pointers, null entries = dense members; both
 // arrays null: the plain launch)
-extern "C" int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
-                                      void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
-                                      const void* const* in_map, void* const* out_map, aod_stream_t stream) {
+// order (optional): int32 [ngroups * tiles of 256 rows * tiles of 256 columns], device memory -- where the launch carries a map and runs the
+// 256 x 256 tile, the small launch that writes the maps also writes the block order of the launch there (conv_tile_order_slot) and the
+// kernel follows it; null, or AOD_TILE_ORDER=0: the fixed deal (conv_grouped_deal)
+extern "C" int aod_conv2d_grouped_map_order(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                            void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
+                                            const void* const* in_map, void* const* out_map, void* order, aod_stream_t stream) {
   ConvKParams p;
   ConvPlan pl;
   int rc = conv_params_grouped(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, p);
@@ -1591,10 +1737,16 @@ extern "C" int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, 
   if (rc) return rc;
   AOD_CHECK_ARG(!in_map == !out_map, "conv_grouped (map): incoming and outgoing maps come together");
   if (in_map) {
-    rc = conv_map_setup(p, ngroups, in_map, out_map, (hipStream_t)stream);
+    rc = conv_map_setup(p, ngroups, in_map, out_map, (hipStream_t)stream, &pl, (int*)order);
     if (rc) return rc;
   }
   return conv_launch(pl, p, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                      void* const* dst, const float* const* pre_shift, const void* const* mask, float* const* colsum,
+                                      const void* const* in_map, void* const* out_map, aod_stream_t stream) {
+  return aod_conv2d_grouped_map_order(desc, ngroups, src, w_packed, dst, pre_shift, mask, colsum, in_map, out_map, nullptr, stream);
 }
 
 extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
@@ -1604,8 +1756,10 @@ extern "C" int aod_conv2d_grouped(const aod_conv_desc_t* desc, int ngroups, cons
 }
 
 // aod_conv2d_grouped, forward, with a ready-made row-activity map per member (omap: ngroups pointers, null entries = dense members)
-extern "C" int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
-                                          void* const* dst, const float* const* pre_shift, const void* const* omap, aod_stream_t stream) {
+// (order: as in aod_conv2d_grouped_map_order; the list is built by a small launch ahead of the conv)
+extern "C" int aod_conv2d_grouped_fwd_map_order(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                                void* const* dst, const float* const* pre_shift, const void* const* omap, void* order,
+                                                aod_stream_t stream) {
   ConvKParams p;
   ConvPlan pl;
   int rc = conv_params_grouped(desc, ngroups, src, w_packed, dst, pre_shift, nullptr, nullptr, p);
@@ -1614,10 +1768,15 @@ extern "C" int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngrou
   rc = conv_plan(p, ngroups, false, pl);
   if (rc) return rc;
   if (omap && pl.kind == AOD_CONV_PLAN_IGEMM && pl.x3) {      // (the persistent kernel, AOD_X3P_GROUPED=1, skips bias-free dgrad tiles only: dense there)
-    rc = conv_fwd_map_setup(p, ngroups, omap);
+    rc = conv_fwd_map_setup(p, ngroups, omap, (hipStream_t)stream, pl, (int*)order);
     if (rc) return rc;
   }
   return conv_launch(pl, p, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                          void* const* dst, const float* const* pre_shift, const void* const* omap, aod_stream_t stream) {
+  return aod_conv2d_grouped_fwd_map_order(desc, ngroups, src, w_packed, dst, pre_shift, omap, nullptr, stream);
 }
 
 // The row-activity maps of the sparse forward: maps[0] from the assigner's bbox_weights (fp32 [rows * anchors][4], level-major like the rows
@@ -1662,6 +1821,21 @@ extern "C" int aod_conv2d_grouped_deal(int nwg, int ngroups, int mapped, int32_t
     conv_grouped_deal(b, nwg, ngroups, mapped ? 1 : 0, t, g);
     tile[b] = t; group[b] = g;
   }
+  return 0;
+}
+
+// The list of a mapped grouped launch as data (host logic only; the rule and the walk are the ones tile_order_kernel runs): `ngroups` members
+// of `rows` GEMM rows and `tiles_n` column tiles each, maps[g] = a HOST copy of member g's row-activity map ((rows + 63) / 64 bytes) or null
+// for a member without one.  tile[b] / group[b] of block b, b < ngroups * ceil(rows / 256) * tiles_n.
+extern "C" int aod_conv2d_tile_order(int rows, int tiles_n, int ngroups, const void* const* maps, int32_t* tile, int32_t* group) {
+  AOD_CHECK_ARG(rows >= 1 && tiles_n >= 1 && ngroups >= 1 && ngroups <= 4 && maps && tile && group, "conv_tile_order: rows %d, tiles_n %d, ngroups %d", rows, tiles_n, ngroups);
+  TileOrderArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int g = 0; g < ngroups; ++g) a.omap[g] = (const unsigned char*)maps[g];
+  a.ngroups = ngroups; a.bm = 256; a.M = rows; a.tiles_m = (rows + 255) / 256; a.tiles_n = tiles_n;
+  const int nwg = a.tiles_m * tiles_n;
+  tile_order_host(a, tile);
+  for (int b = 0; b < nwg * ngroups; ++b) { const int e = tile[b]; tile[b] = e % nwg; group[b] = e / nwg; }
   return 0;
 }
 

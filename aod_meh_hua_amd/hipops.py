@@ -221,11 +221,19 @@ def conv2d_rows(x_rows, src_segs, w_packed, N, R, S, stride=1, pad=0, dil=1, *, 
     return (out, dst_segs, z) if save_z else (out, dst_segs)
 
 
-def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pre_shifts=None, relu=False, outs=None, alg=None, omaps=None):
+def tile_order_list(G, rows, N, device):
+    """the (unwritten) block-order list of a mapped grouped launch of G members: one int32 per 256 x 256 tile and member, written on the
+    device from the maps ahead of the launch (aod_conv2d_grouped_map_order / _fwd_map_order; AOD_TILE_ORDER=0: left unwritten)"""
+    return torch.empty(G * ((rows + 255) // 256) * ((N + 255) // 256), dtype=torch.int32, device=device)
+
+
+def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pre_shifts=None, relu=False, outs=None, alg=None, omaps=None,
+                        order=None):
     """G forward convs of identical geometry in ONE launch (aod_conv2d_grouped): xs / ws / pre_shifts / outs are lists of G row tensors
     (inputs may be the same tensor), `src_segs` the shared segment list.  Returns (list of outputs, dst_segs).
     omaps (sparse forward): list of G row-activity maps of where each member's OUTPUT is needed (fwd_row_maps), None entries = dense members;
-    the tiles outside a member's map come back as zero rows (aod_conv2d_grouped_fwd_map)."""
+    the tiles outside a member's map come back as zero rows (aod_conv2d_grouped_fwd_map_order; order: a caller's tile_order_list, else a
+    fresh one)."""
     G = len(xs)
     Cin = xs[0].shape[1]
     dst_segs = out_segs(src_segs, R, S, stride, pad, dil)
@@ -243,7 +251,8 @@ def conv2d_rows_grouped(xs, src_segs, ws, N, R, S, stride=1, pad=0, dil=1, *, pr
         for m in omaps:
             assert m is None or (m.dtype == torch.uint8 and m.is_cuda and m.numel() == (rows + 63) // 64)
         keep.append(arr(omaps))
-        fn = lambda: call('aod_conv2d_grouped_fwd_map', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], keep[4], stream())
+        order = tile_order_list(G, rows, N, xs[0].device) if order is None else order
+        fn = lambda: call('aod_conv2d_grouped_fwd_map_order', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], keep[4], ptr(order), stream())
     else:
         fn = lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], keep[3], None, None, stream())
     if PROFILE is None:
@@ -296,9 +305,10 @@ def _maps_apply(dz_segs, x_segs, stride, out_f32):
 
 
 def conv2d_dgrad_rows_grouped(dzs, dz_segs, x_segs, wds, Cin, R, S, stride=1, pad=0, dil=1, *, masks=None, colsums=None, alg=None,
-                              in_maps=None, outs=None):
+                              in_maps=None, outs=None, order=None):
     """G dgrads of identical geometry in one launch: dX_g = conv_T(dZ_g, W_g) (* [mask_g > 0], column sums into colsums[g]).
-    in_maps (list of G row-activity maps of the dZ_g, None entries = dense members): returns (outs, out_maps) -- the maps of the dX_g."""
+    in_maps (list of G row-activity maps of the dZ_g, None entries = dense members): returns (outs, out_maps) -- the maps of the dX_g.
+    order: a caller's tile_order_list for the mapped launch, else a fresh one."""
     G = len(dzs)
     Npad = dzs[0].shape[1]
     rows = sum(s.rows for s in x_segs)
@@ -315,7 +325,9 @@ def conv2d_dgrad_rows_grouped(dzs, dz_segs, x_segs, wds, Cin, R, S, stride=1, pa
         for m in in_maps:
             assert m is None or (m.dtype == torch.uint8 and m.numel() == (rows + 63) // 64)
         keep += [arr(in_maps), arr(out_maps)]
-        fn = lambda: call('aod_conv2d_grouped_map', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], keep[5], keep[6], stream())
+        order = tile_order_list(G, rows, Cin, outs[0].device) if order is None else order
+        fn = lambda: call('aod_conv2d_grouped_map_order', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], keep[5], keep[6],
+                          ptr(order), stream())
     else:
         fn = lambda: call('aod_conv2d_grouped', C.byref(d), G, keep[0], keep[1], keep[2], None, keep[3], keep[4], stream())
     if PROFILE is None:

@@ -229,6 +229,20 @@ int aod_conv2d_grouped_fwd_map(const aod_conv_desc_t* desc, int ngroups, const v
                                const float* const* pre_shift, const void* const* omap, aod_stream_t stream);
 int aod_conv2d_grouped_deal(int nwg, int ngroups, int mapped, int32_t* tile, int32_t* group);
 
+/* The block order of a mapped grouped launch as a device-built LIST.  `order`: int32 [ngroups * tiles], device memory, tiles = ceil(rows / 256)
+ * * ceil(N / 256).  Where the launch carries a map and runs the 256 x 256 tile, the small launch that writes the maps (dgrad) or one ahead of
+ * the conv (forward) writes a permutation of the entries member * tiles + tile there, and block b of the conv runs entry order[b]: every live
+ * entry (a member without a map: all its tiles) before every dead one; the live ones, ranked member-major, dealt so that each blockIdx % 8
+ * class takes a contiguous range of the ranking, the same number +- 1.  Which block runs a tile is placement only: same bits per row.
+ * order = NULL, AOD_TILE_ORDER=0, or a launch the list does not apply to: aod_conv2d_grouped_map / aod_conv2d_grouped_fwd_map unchanged.
+ * aod_conv2d_tile_order applies the same rule to HOST copies of the maps (NULL entries: members without a map; tiles_n = ceil(N / 256)). */
+int aod_conv2d_grouped_map_order(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
+                                 const float* const* pre_shift, const void* const* mask, float* const* colsum, const void* const* in_map,
+                                 void* const* out_map, void* order, aod_stream_t stream);
+int aod_conv2d_grouped_fwd_map_order(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed,
+                                     void* const* dst, const float* const* pre_shift, const void* const* omap, void* order, aod_stream_t stream);
+int aod_conv2d_tile_order(int rows, int tiles_n, int ngroups, const void* const* maps, int32_t* tile, int32_t* group);
+
 /* replaces: the weight-gradient half of autograd's conv backward (cuDNN wgrad) for the same
  * call sites.  dw_f32 is [N][R][S][C] fp32 and is ACCUMULATED into (caller zeroes it);
  * x: forward input [rows, C] bf16; dz: [rows_out, N] bf16. */
