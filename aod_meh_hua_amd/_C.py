@@ -145,6 +145,7 @@ _SIGS = {
     'aod_nms_ws_bytes': (SZ, [I32, I32, I32]),
     'aod_multiclass_nms': (C.c_int, [P, P, I32, I32, I32, F32, F32, I32, P, P, P, P, P, P]),
     'aod_eval_match': (C.c_int, [P, P, P, P, P, P, P, I32, I32, I32, P, I32, P, P]),
+    'aod_coco_match': (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, P, I32, P, I32, P, P]),
     'aod_hua_ws_bytes': (SZ, [I32, I32]),
     'aod_hua_score': (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, F32, I32, U64, P, I32, I32, I32, P, P, I32, P, P, P]),
     'aod_hua_score_ex': (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, F32, I32, U64, P, I32, I32, I32, P, P, I32, P,

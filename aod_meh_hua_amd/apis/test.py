@@ -121,6 +121,8 @@ def calculate_uncertainty(cfg, *args, **kwargs):
 
 
 def _unwrap(x):
+    if isinstance(x, (list, tuple)):          # test-mode pipelines (MultiScaleFlipAug): one entry per augmentation, the metas in containers
+        return [v.data[0] if isinstance(v, DataContainer) else v for v in x]
     return x.data if isinstance(x, DataContainer) else x
 
 
@@ -768,3 +770,58 @@ def single_gpu_map(model, data_loader, iou_thr=0.5, dataset=None, show=False, ou
     for mean_ap, eval_results in res:
         print_map_summary(mean_ap, eval_results, dataset, None, logger=logger)
     return res[0] if single else res
+
+
+def coco_eval_infos(dataset):
+    """[dataset.get_eval_info(i)] read once per dataset object (CocoDataset.eval_infos keeps them)"""
+    if hasattr(dataset, 'eval_infos'):
+        return dataset.eval_infos()
+    if not hasattr(dataset, 'get_eval_info'):
+        raise TypeError(f'{type(dataset).__name__} has no get_eval_info: the COCO bbox metric needs a CocoDataset, or eval_infos=')
+    return [dataset.get_eval_info(i) for i in range(len(dataset))]
+
+
+@torch.no_grad()
+def single_gpu_coco_map(model, data_loader, iou_thrs=None, proposal_nums=(100, 300, 1000), classwise=False, metric_items=None,
+                        logger='silent', eval_infos=None, _timing=None, **kwargs):
+    """COCO bbox evaluation on the device: detect (isEval=True, padded outputs) -> aod_coco_match -> core.coco_eval_device
+    .DeviceCocoAccumulator, one D2H copy per evaluation.  Returns the dict of
+    dataset.evaluate(single_gpu_test(model, data_loader), metric='bbox', iou_thrs=..., classwise=..., metric_items=...), value for value.
+
+    The loop is single_gpu_map's: the test set is sharded over the ranks (_PoolPass), batches come from the prefetch workers through
+    pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the detection pass replays the captured ('eval_padded',)
+    graph; the match kernel runs eagerly behind the replay on the same stream, so it has read the graph's static outputs before the next
+    replay overwrites them.  `eval_infos`: the dataset's get_eval_info list, when the caller already holds it.  `_timing` (a dict;
+    tools/eval_throughput.py): the loop is followed by a device sync and its wall time lands in _timing['pass_s'], the gathered
+    DeviceCocoAccumulator in _timing['accumulator']."""
+    t_start = time.perf_counter()
+    from ..core.coco_eval import check_metric
+    from ..core.coco_eval_device import DeviceCocoAccumulator
+    if kwargs.get('detUnc'):
+        raise ValueError('single_gpu_coco_map: detUnc is not offered on the device metric; use single_gpu_test(detUnc=True)')
+    check_metric(kwargs.pop('metric', 'bbox'))
+    for k in ('device_metric', 'interval', 'show', 'out_dir', 'show_score_thr'):          # EvalHook forwards the whole `evaluation` dict
+        kwargs.pop(k, None)
+    kwargs.setdefault('isUnc', False)
+    model.eval()
+    ds = data_loader.dataset
+    N = len(ds)
+    module = getattr(model, 'module', model)
+    dev = next(model.parameters()).device
+    acc = DeviceCocoAccumulator(module.bbox_head.num_classes, iou_thrs, module.bbox_head.test_cfg.max_per_img, N, dev,
+                                proposal_nums=proposal_nums)
+    infos = eval_infos if eval_infos is not None else coco_eval_infos(ds)
+    assert len(infos) == N
+    pool = _PoolPass(data_loader, dev, device_batch=False)
+    gscore = _graphed(model, dev, ('eval_padded',), kwargs, isEval=True, _padded=True)
+    for idxs, image_ids, data in pool.batches():
+        dets, labels, num = _replay_or_eager(gscore, data, image_ids,
+                                             lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **kwargs))
+        acc.update(idxs, dets, labels, num, [infos[i] for i in idxs])
+    if _timing is not None:
+        torch.cuda.synchronize()
+        _timing['pass_s'] = time.perf_counter() - t_start
+    acc.gather()
+    if _timing is not None:
+        _timing['accumulator'] = acc          # (the tests read its unrounded precision array)
+    return acc.finalize(getattr(ds, 'CLASSES', None), classwise=classwise, metric_items=metric_items, logger=logger)

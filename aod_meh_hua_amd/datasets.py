@@ -295,6 +295,136 @@ class VOCDataset(XMLDataset):
                             logger=logger, iou_thr=iou_thr)
 
 
+COCO_CLASSES = ('person', 'bicycle', 'car', 'motorcycle', 'airplane', 'bus', 'train', 'truck', 'boat', 'traffic light', 'fire hydrant',
+                'stop sign', 'parking meter', 'bench', 'bird', 'cat', 'dog', 'horse', 'sheep', 'cow', 'elephant', 'bear', 'zebra', 'giraffe',
+                'backpack', 'umbrella', 'handbag', 'tie', 'suitcase', 'frisbee', 'skis', 'snowboard', 'sports ball', 'kite', 'baseball bat',
+                'baseball glove', 'skateboard', 'surfboard', 'tennis racket', 'bottle', 'wine glass', 'cup', 'fork', 'knife', 'spoon', 'bowl',
+                'banana', 'apple', 'sandwich', 'orange', 'broccoli', 'carrot', 'hot dog', 'pizza', 'donut', 'cake', 'chair', 'couch',
+                'potted plant', 'bed', 'dining table', 'toilet', 'tv', 'laptop', 'mouse', 'remote', 'keyboard', 'cell phone', 'microwave',
+                'oven', 'toaster', 'sink', 'refrigerator', 'book', 'clock', 'vase', 'scissors', 'teddy bear', 'hair drier', 'toothbrush')
+_COCO_JSON = {}           # absolute path -> parsed annotation file (per process: the splits of one pool share it)
+
+
+def load_coco_json(path):
+    """A COCO annotation file parsed once per path and process: dict(images = the image records in file order, by_id = image id -> record,
+    anns = image id -> its annotations in file order, categories)."""
+    import json
+    key = osp.abspath(path)
+    parsed = _COCO_JSON.get(key)
+    if parsed is None:
+        with open(key) as f:
+            raw = json.load(f)
+        images = list(raw.get('images', []))
+        anns = {im['id']: [] for im in images}
+        for ann in raw.get('annotations', []):
+            anns.setdefault(ann['image_id'], []).append(ann)
+        parsed = _COCO_JSON[key] = dict(images=images, by_id={im['id']: im for im in images}, anns=anns,
+                                        categories=list(raw.get('categories', [])))
+    return parsed
+
+
+@DATASETS.register_module()
+class CocoDataset(CustomDataset):
+    """COCO detection annotations read with plain json (mmdet/datasets/coco.py's behaviour, restated; no pycocotools).  `ann_file` is the
+    annotation json itself (all of its images) or, with `coco_json=` naming the json, a text list of image ids, one per line: the form
+    the active-learning bookkeeping reads and rewrites (utils/active_datasets.py).  Category ids need not be contiguous: cat_ids lists the
+    ids of the categories named in CLASSES, in CLASSES order, and cat2label enumerates them."""
+    CLASSES = COCO_CLASSES
+
+    def __init__(self, coco_json=None, **kwargs):
+        self.coco_json = coco_json
+        super().__init__(**kwargs)
+
+    def load_annotations(self, ann_file):
+        path = ann_file if str(ann_file).endswith('.json') else self.coco_json
+        if path is None:
+            raise ValueError(f'CocoDataset: ann_file {ann_file!r} is an image-id list; coco_json= must name the annotation file')
+        if self.data_root is not None and not osp.isabs(path):
+            path = osp.join(self.data_root, path)
+        self.coco = load_coco_json(path)
+        by_name = {c['name']: c['id'] for c in self.coco['categories']}
+        self.cat_ids = [by_name[n] for n in self.CLASSES if n in by_name]
+        self.cat2label = {cid: i for i, cid in enumerate(self.cat_ids)}
+        if str(ann_file).endswith('.json'):
+            records = self.coco['images']
+        else:
+            by_str = {str(k): v for k, v in self.coco['by_id'].items()}
+            records = []
+            for img_id in [ln.strip() for ln in open(ann_file) if ln.strip()]:
+                if img_id not in by_str:
+                    raise KeyError(f'CocoDataset: image id {img_id} of {ann_file} is not in {path}')
+                records.append(by_str[img_id])
+        self.img_ids = [im['id'] for im in records]
+        return [dict(id=im['id'], filename=im['file_name'], width=im['width'], height=im['height']) for im in records]
+
+    def _anns(self, idx):
+        return self.coco['anns'].get(self.data_infos[idx]['id'], [])
+
+    def _filter_imgs(self, min_size=32):
+        valid = []
+        for i, info in enumerate(self.data_infos):
+            if min(info['width'], info['height']) < min_size:
+                continue
+            if self.filter_empty_gt and not any(a['category_id'] in self.cat2label for a in self._anns(i)):
+                continue
+            valid.append(i)
+        self.img_ids = [self.img_ids[i] for i in valid]
+        return valid
+
+    def get_cat_ids(self, idx):
+        return [a['category_id'] for a in self._anns(idx)]
+
+    def get_ann_info(self, idx):
+        """The training view: an annotation is dropped when it is marked `ignore`, lies outside the image, has area <= 0 or a side below
+        one pixel, or belongs to no kept category; xywh -> [x, y, x + w, y + h]; `iscrowd` boxes go to the ignore set."""
+        info = self.data_infos[idx]
+        bboxes, labels, bboxes_ignore, labels_ignore = [], [], [], []
+        for ann in self._anns(idx):
+            if ann.get('ignore', False):
+                continue
+            x1, y1, w, h = ann['bbox']
+            inter_w = max(0, min(x1 + w, info['width']) - max(x1, 0))
+            inter_h = max(0, min(y1 + h, info['height']) - max(y1, 0))
+            if inter_w * inter_h == 0:
+                continue
+            if ann['area'] <= 0 or w < 1 or h < 1:
+                continue
+            if ann['category_id'] not in self.cat2label:
+                continue
+            bbox = [x1, y1, x1 + w, y1 + h]
+            if ann.get('iscrowd', False):
+                bboxes_ignore.append(bbox), labels_ignore.append(self.cat2label[ann['category_id']])
+            else:
+                bboxes.append(bbox), labels.append(self.cat2label[ann['category_id']])
+        return dict(bboxes=np.array(bboxes, dtype=np.float32).reshape(-1, 4), labels=np.array(labels, dtype=np.int64),
+                    bboxes_ignore=np.array(bboxes_ignore, dtype=np.float32).reshape(-1, 4), labels_ignore=np.array(labels_ignore, dtype=np.int64))
+
+    def get_eval_info(self, idx):
+        """The evaluation view, untouched by the training filters: every annotation of a kept category in file order --
+        boxes [G, 4] float64 xywh as written, area [G] float64 (the file's), iscrowd [G] uint8, labels [G] int64."""
+        anns = [a for a in self._anns(idx) if a['category_id'] in self.cat2label]
+        return dict(boxes=np.array([a['bbox'] for a in anns], dtype=np.float64).reshape(-1, 4),
+                    area=np.array([a['area'] for a in anns], dtype=np.float64),
+                    iscrowd=np.array([1 if a.get('iscrowd', 0) else 0 for a in anns], dtype=np.uint8),
+                    labels=np.array([self.cat2label[a['category_id']] for a in anns], dtype=np.int64))
+
+    def eval_infos(self):
+        """[get_eval_info(i)] built once per dataset object"""
+        infos = getattr(self, '_eval_infos', None)
+        if infos is None or len(infos) != len(self):
+            infos = self._eval_infos = [self.get_eval_info(i) for i in range(len(self))]
+        return infos
+
+    def evaluate(self, results, metric='bbox', logger=None, proposal_nums=(100, 300, 1000), iou_thrs=None, classwise=False,
+                 metric_items=None, **kwargs):
+        """COCO bbox AP (core/coco_eval.py) with mmdet's keys: bbox_mAP, _50, _75, _s, _m, _l and bbox_mAP_copypaste.  The arrays
+        go straight to the evaluator; extra EvalHook kwargs (show, isUnc, out_dir) are ignored like the reference's signature swallows them."""
+        from .core.coco_eval import check_metric, evaluate_bbox
+        check_metric(metric)
+        return evaluate_bbox(results, self.eval_infos(), self.CLASSES, iou_thrs=iou_thrs, proposal_nums=proposal_nums, classwise=classwise,
+                             metric_items=metric_items, logger=logger)
+
+
 class ConcatDataset(torch.utils.data.ConcatDataset):
     """dataset_wrappers.py:12-125 (VOC07+12 trainval): concatenated flags; evaluation is per-dataset in the reference and unused here."""
 

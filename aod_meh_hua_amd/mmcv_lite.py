@@ -681,6 +681,8 @@ class EvalHook(Hook):
         kw = dict(self.eval_kwargs)
         metric = kw.pop('metric', 'mAP')
         metric = metric[0] if not isinstance(metric, str) and len(metric) == 1 else metric
+        if metric == 'bbox':
+            return self._device_coco_metric(runner, kw)
         if metric != 'mAP':
             raise KeyError(f'metric {metric} is not supported')
         dataset = self.dataloader.dataset
@@ -697,6 +699,19 @@ class EvalHook(Hook):
             mean_aps.append(mean_ap)
             eval_res[f'AP{int(thr * 100):02d}'] = round(mean_ap, 3)
         eval_res['mAP'] = sum(mean_aps) / len(mean_aps)
+        for name, val in eval_res.items():
+            runner.log_buffer.output[name] = val
+        runner.log_buffer.ready = True
+        return eval_res
+
+    def _device_coco_metric(self, runner, kw):
+        """evaluation = dict(metric='bbox', device_metric=True): apis.test.single_gpu_coco_map (detect -> aod_coco_match -> accumulate on
+        the device) instead of single_gpu_test + CocoDataset.evaluate; the dict is that evaluate's, value for value."""
+        from .apis.test import coco_eval_infos, single_gpu_coco_map
+        if getattr(self, '_eval_infos', None) is None:          # read once per hook, not once per evaluation
+            self._eval_infos = coco_eval_infos(self.dataloader.dataset)
+        eval_res = single_gpu_coco_map(runner.model, self.dataloader, logger=runner.logger, eval_infos=self._eval_infos, **kw)
+        runner.log_buffer.output['eval_iter_num'] = len(self.dataloader)
         for name, val in eval_res.items():
             runner.log_buffer.output[name] = val
         runner.log_buffer.ready = True

@@ -564,6 +564,18 @@ int aod_multiclass_nms(const float* boxes, const float* scores, int B, int n, in
 int aod_eval_match(const float* dets, const int64_t* labels, const int32_t* num, const float* gt_boxes, const int32_t* gt_labels,
                    const uint8_t* gt_ignore, const int32_t* gt_num, int B, int M, int G, const float* iou_thr_host, int T,
                    uint8_t* flags, aod_stream_t stream);
+/* COCO bbox matching (replaces the per-image loop of core/coco_eval.py evaluate_bbox: coco_eval.match_image once per image and
+ * class) for a whole batch, all classes, A (1..4) area ranges and T (1..16) IoU thresholds in one launch.  dets / labels / num as for
+ * aod_eval_match (M <= 1024).  gt_boxes [B,G,4] fp64 xywh, gt_area [B,G] fp64 (the annotation's area, which the range test reads),
+ * gt_label [B,G] int32, gt_crowd [B,G] uint8, gt_num [B] int32: the image's gts in file order (G <= 512).  area_rng_host: HOST array of
+ * A (lo, hi) pairs, inclusive; iou_thr_host: HOST array of T thresholds; both fp64.  states [A,T,B,M] uint8: 1 matched to a counted gt,
+ * 0 unmatched and counted, 2 ignored (matched to an ignored gt, or unmatched with its own area outside the range); rows >= num[b] are 0.
+ * Detections rank by descending score, ties by lower row; IoU is coco_eval.iou_matrix bit for bit in fp64.  No workspace, no host sync.
+ * Scores must not be NaN: such rows have no rank, and some rows below num[b] are then left unwritten (the caller zeroes `states` first if
+ * it cannot rule NaN out; core/coco_eval_device.py does). */
+int aod_coco_match(const float* dets, const int64_t* labels, const int32_t* num, const double* gt_boxes, const double* gt_area,
+                   const int32_t* gt_label, const uint8_t* gt_crowd, const int32_t* gt_num, int B, int M, int G,
+                   const double* area_rng_host, int A, const double* iou_thr_host, int T, uint8_t* states, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ HUA (K13-K15)
  * replaces GetObjectIdx + ComputeObjUnc + AggregateObjScaleUnc (Lambda_L2.py:343-349,489-537,597-619;

@@ -93,7 +93,8 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                    help='run Resize / RandomFlip / Normalize / Pad of the VOC pipelines as one HIP kernel per batch (config key data.device_transforms)')
     p.add_argument('--device-metric', action='store_true',
                    help='EvalHook computes mAP on the device: padded detections -> aod_eval_match -> one D2H copy, the test set sharded over '
-                        'the ranks (config key evaluation.device_metric); same numbers as the host metric')
+                        'the ranks (config key evaluation.device_metric); same numbers as the host metric.  With metric=\'bbox\' (COCO '
+                        'configs): padded detections -> aod_coco_match, the dict of CocoDataset.evaluate')
     args = p.parse_args()
     try:            # (at start-up: a malformed value must not surface after a whole training cycle)
         args.noise_sigmas = tuple(float(s) for s in args.noise_levels.split(',') if s.strip())
