@@ -63,10 +63,6 @@ _SIGS = {
     'aod_bottleneck128x3_bwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_bottleneck128x3_fwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_bottleneck128_fwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    'aod_frag_pack': (C.c_int, [P, I32, I32, P]),
-    'aod_frag_pack_item_bytes': (C.c_int, []),
-    'aod_bottleneck256f_fwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    'aod_bottleneck256f_bwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_bottleneck_bwd': (C.c_int, [I32, P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_bottleneck256_fwd': (C.c_int, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     'aod_conv2d': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P]),

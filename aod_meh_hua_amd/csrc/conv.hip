@@ -90,7 +90,7 @@ template <int BM, int BN, int NT, int OPS, bool GROUPED, int ST, bool X3>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 2 : (NT == 512 ? 4 : 1), BM >= 192 ? 2 : (NT == 512 ? 4 : 8)))) void conv_igemm_kernel(const ConvKParams p) {
   static_assert(NT == 256 || NT == 512, "4 or 8 waves");
   static_assert(ST == 2 || (ST == 3 && NT == 256), "LDS stages: 2, or 3 for the 4-wave forms");
-  static_assert(!X3 || NT == 256 || (NT == 512 && (BM == 256 || BM == 192 || BM == 128)), "X3: the 4-wave forms, the 8-wave 256 x 256 / 192 x 192 tiles and (A/B) the 8-wave 128 x 128 tile");
+  static_assert(!X3 || NT == 256 || (NT == 512 && (BM == 256 || BM == 192)), "X3: the 4-wave forms and the 8-wave 256 x 256 / 192 x 192 tiles");
   constexpr int BK = 64;
   constexpr int CPR = BK / 8;        // 16-B chunks per tile row
   constexpr int RPP = NT / CPR;      // tile rows covered per pass of the NT threads
@@ -1578,11 +1578,6 @@ static int conv_plan(const ConvKParams& p, int ngroups, bool has_workspace, Conv
     // forms), same K order -> same bits.  AOD_X3_TILE_192=0: the 128 x 64 tile.
     if (p.N > 128 && p.N <= 192 && !p.res && !p.mask && !p.zraw && p.K >= 2048 && ntiles(192, 192) >= 240 && !kn.is(ConvKnobs::X3_TILE_192, '0'))
       return igemm(192, 192, 512, 0, 2);
-    // A/B knob (AOD_X3_128_W8=1): the 128 x 128 x3 tile on EIGHT waves for launches without a residual operand.  Back to back on warm operands
-    // it beats the 64 x 128 three-stage tile on the 16 384-row layers (80.0 -> 73.2 us for the stage-3 3 x 3, tools/dbg/x3_w8_ab.sh); INSIDE the
-    // step, on operands that come from HBM / the Infinity Cache, it loses 8 % (80.2 -> 86.3 us forward, 77.9 -> 89.3 us dgrad in the instrumented
-    // step, profiles/r05_conv_shapes_one_step.txt against the run before it): not taken.
-    if (knob_is(k1.x3_128_w8, '1') && !p.res && !p.out_f32 && p.N % 128 == 0 && ntiles(128, 128) >= 256) return w8(128, 128);
   } else {
     if (!knob_is(k1.tile_256, '0') && shape256 && ((knob_is(k1.tile_256, '1') && t256 >= 128) || fits256)) return w8(256, 256);
     // deep convs without a residual operand (forward and dgrad of the head towers, the 3x3 of the backbone): the 128 x 128 tile on 8
@@ -1596,10 +1591,9 @@ static int conv_plan(const ConvKParams& p, int ngroups, bool has_workspace, Conv
   const bool ragged = p.N > 128 && (pad128 - pad64) * 5 >= pad128;
   // (three LDS stages for the 64-row tiles -- x3: always; plain: when the K loop is long enough to matter, AOD_RING3=0 disables; the 128 x 64
   // tile keeps two -- three stages cost it its third workgroup per CU: 61 -> 69 us on the narrow prediction convs; the 128 x 128 tile too --
-  // three stages = 96 KB = one workgroup per CU: measured +0.55 ms per step; 64 x 128 x 3 stages instead: +0.3 ms -- but for AOD_X3_128_ST3=1)
+  // three stages = 96 KB = one workgroup per CU: measured +0.55 ms per step; 64 x 128 x 3 stages instead: +0.3 ms)
   const int st64 = (p.x3 || (!knob_is(k1.ring3, '0') && p.K >= 256)) ? 3 : 2;
   if (ragged && ntiles(128, 64) >= want) return igemm(128, 64, 256, 2, 2);
-  if (p.N > 64 && p.x3 && knob_is(k1.x3_128_st3, '1') && ntiles(128, 128) >= 256) return igemm(128, 128, 256, 2, 3);
   if (p.N > 64 && ntiles(128, 128) >= want) return igemm(128, 128, 256, 2, 2);
   if (p.N > 64 && ntiles(64, 128) >= want) return igemm(64, 128, 256, 2, st64);
   if (p.N <= 64 && ntiles(128, 64) >= want) return igemm(128, 64, 256, 2, 2);
@@ -1639,8 +1633,7 @@ static void x3p_args(const ConvKParams& p, const ConvPlan& plan, X3PArgs& a) {
   X(64, 64, 256, 2, false, 2, false) X(64, 64, 256, 2, false, 3, false)                                                               \
   X(256, 256, 512, 0, true, 2, false) X(256, 256, 512, 1, true, 2, false) X(128, 128, 512, 0, true, 2, false) X(128, 128, 512, 1, true, 2, false)    \
   X(256, 256, 512, 0, false, 2, true) X(256, 256, 512, 1, false, 2, true) X(192, 192, 512, 0, false, 2, true)                          \
-  X(128, 128, 512, 0, false, 2, true) X(128, 128, 512, 1, false, 2, true) X(128, 128, 256, 2, false, 2, true) X(128, 128, 256, 2, false, 3, true)    \
-  X(128, 64, 256, 2, false, 2, true) X(64, 128, 256, 2, false, 3, true) X(64, 64, 256, 2, false, 3, true)                              \
+  X(128, 128, 256, 2, false, 2, true) X(128, 64, 256, 2, false, 2, true) X(64, 128, 256, 2, false, 3, true) X(64, 64, 256, 2, false, 3, true)      \
   X(256, 256, 512, 0, true, 2, true) X(256, 256, 512, 1, true, 2, true)
 
 static int launch_igemm(const ConvPlan& pl, const ConvKParams& p, hipStream_t st) {

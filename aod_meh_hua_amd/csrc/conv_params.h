@@ -104,8 +104,6 @@ struct ConvKnobs {
     const char* dgrad_classes = getenv("AOD_DGRAD_CLASSES");
     const char* tile_want = getenv("AOD_TILE_WANT");            // (debug: the tile count that counts as 'fills the device')
     const char* tile_256 = getenv("AOD_TILE_256");              // (1 forces the plain 256 x 256 tile, 0 disables it in every form)
-    const char* x3_128_w8 = getenv("AOD_X3_128_W8");
-    const char* x3_128_st3 = getenv("AOD_X3_128_ST3");          // (debug / A-B: the 128 x 128 x3 tile on a three-stage ring, one workgroup per CU)
     const char* tile_w8 = getenv("AOD_TILE_W8");
     const char* ring3 = getenv("AOD_RING3");
     // the weight-gradient plan (conv_wgrad.hip).  No test or tool sets an AOD_WGRAD_* variable in-process, so reading them here, at the first

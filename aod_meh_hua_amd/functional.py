@@ -67,12 +67,8 @@ class _PrepRec(_C.Structure):
                 ('eps', _C.c_float), ('pad_', _C.c_int32), ('pad2_', _C.c_int64 * 2)]
 
 
-class _FragRec(_C.Structure):
-    _fields_ = [('src', _C.c_void_p), ('dst', _C.c_void_p), ('rows', _C.c_int32), ('K', _C.c_int32), ('blk0', _C.c_int32), ('pad_', _C.c_int32)]
-
-
 class _PrepItem:
-    __slots__ = ('srcs', 'ver', 'wf', 'wd', 'scale', 'shift', 'invstd', 'eps', 'dims', 'nblk', 'fragf', 'fragd', 'x3')
+    __slots__ = ('srcs', 'ver', 'wf', 'wd', 'scale', 'shift', 'invstd', 'eps', 'dims', 'nblk', 'x3')
 
 
 class ParamPrep:
@@ -122,7 +118,6 @@ class ParamPrep:
         else:
             it.scale = it.shift = it.invstd = None
         it.eps, it.dims, it.ver = float(eps), (O, I, R * S, cin_pad, opad), None
-        it.fragf = it.fragd = None
         if R * S <= 9 and it.x3:
             it.nblk = (opad // 64) * (cin_pad // 64)                         # 32 x 32 LOGICAL channel tiles, each a head and a tail band
         elif R * S <= 9:
@@ -132,21 +127,6 @@ class ParamPrep:
         self.items[(id(w), it.x3)] = it
         self.dirty = True
         return it
-
-    def frag(self, it, which):
-        """fragment-major image (aod_frag_pack) of a layer's forward ('f') or dgrad ('d') pack for the register-streamed bottleneck kernels;
-        created on first request and from then on re-derived together with the packs, in the same batched step"""
-        name = 'fragf' if which == 'f' else 'fragd'
-        t = getattr(it, name)
-        if t is None:
-            src = it.wf if which == 'f' else it.wd
-            rows = src.shape[0]
-            assert rows % 256 == 0 and (src.numel() // rows) % 64 == 0, 'frag images need rows % 256 == 0 and K % 64 == 0'
-            t = torch.empty(src.numel(), dtype=torch.bfloat16, device=src.device)
-            setattr(it, name, t)
-            self.tables, it.ver = {}, None           # the device tables list the frag images: rebuild them, and pack this one now
-            self.refresh()
-        return t
 
     def refresh_if_stale(self):
         for r in self.stems:              # derived weights first: an in-place rewrite bumps the version the items below watch
@@ -194,21 +174,9 @@ class ParamPrep:
                 blk += it.nblk
             host = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
             dev = self.order[stale[0]].wf.device
-            # fragment-major images of the stale layers that have them: one more launch, after the packs they are made from
-            fl = [(src, dst) for i in stale for src, dst in ((self.order[i].wf, self.order[i].fragf), (self.order[i].wd, self.order[i].fragd))
-                  if dst is not None]
-            ftab, fblk = None, 0
-            if fl:
-                frecs = (_FragRec * len(fl))()
-                for r, (src, dst) in zip(frecs, fl):
-                    r.src, r.dst, r.rows, r.K, r.blk0 = src.data_ptr(), dst.data_ptr(), src.shape[0], src.numel() // src.shape[0], fblk
-                    fblk += (src.numel() + 2047) // 2048
-                ftab = torch.frombuffer(bytearray(bytes(frecs)), dtype=torch.uint8).to(dev)
-            ent = self.tables[stale] = (host.to(dev), blk, ftab, len(fl), fblk)
+            ent = self.tables[stale] = (host.to(dev), blk)
         self.table = ent[0]           # (kept alive for captured graphs by graphs._pin_caches)
         ho.call('aod_param_prep', ho.ptr(ent[0]), len(stale), ent[1], ho.stream())
-        if ent[2] is not None:
-            ho.call('aod_frag_pack', ho.ptr(ent[2]), ent[3], ent[4], ho.stream())
         for i in stale:
             self.order[i].ver = self._versions(self.order[i])
 
@@ -725,12 +693,7 @@ class ConvFn(Function):
                     for r in (2, 1):
                         w_, g_, m_, cin_, _ = ch.prep[r]
                         pis[r] = PREP.get(w_, (g_, None, m_, None) if g_ is not None else None, cin_, ch.meta[r]['eps'])
-                    # (the register-streamed form of the dgrad chain exists -- aod_bottleneck256f_bwd -- but is NOT taken: it fails the bit-equality
-                    # check against the three launches in its third product on this toolchain, tools/dbg/frag_check.py; AOD_BOTTLENECK_FRAG_BWD=1 for experiments)
-                    fr = O == 1024 and _os.environ.get('AOD_BOTTLENECK_FRAG_BWD', '0') == '1'
-                    wds = {r: (PREP.frag(pis[r], 'd') if fr else pis[r].wd) for r in (3, 2, 1)}
-                    gx, dx, gt1, cx, s1_in, c1 = ho.bottleneck_bwd(dz, s0.B, s0.H, s0.W, wds[3], wds[2], wds[1], x_rows, ch.x_rows[2], ch.x_rows[1],
-                                                                   frag=fr)
+                    gx, dx, gt1, cx, s1_in, c1 = ho.bottleneck_bwd(dz, s0.B, s0.H, s0.W, pis[3].wd, pis[2].wd, pis[1].wd, x_rows, ch.x_rows[2], ch.x_rows[1])
                     ch.out[2], ch.out[1] = (gt1, c1), (gx, cx)
                 elif role in ch.out:
                     dx, s1_in = ch.out.pop(role)
@@ -1148,54 +1111,6 @@ def _wide_stage(blk):
     return blk.planes == 128 or (blk.planes == 256 and _os.environ.get('AOD_FUSE_BOTTLENECK256', '1') != '0')
 
 
-_FRAG_OK = {}
-
-
-def _frag_selfcheck(dev):
-    """The register-streamed 256-plane kernel keeps 16-40 loads in flight per wave between hand-placed waits; while it was written, logically
-    equivalent variants of it came out of the compiler producing garbage in a few lanes.  The shipped build is bit-exact in the
-    test suite; on top of that every process compares it ONCE against the LDS-ring form on random operands of the bench shape (three
-    launches, identical bits required) before it takes it -- a mismatch switches the process to the ring form (another HIP kernel) loudly."""
-    import warnings
-    g = torch.Generator(device=dev).manual_seed(7)
-    rnd = lambda *sh: torch.randn(*sh, device=dev, generator=g)
-    P, C4, B, H, W = 256, 1024, 16, 32, 32
-    ws = [(rnd(P, C4) * 0.05).bfloat16(), (rnd(P, 9 * P) * 0.03).bfloat16(), (rnd(C4, P) * 0.05).bfloat16()]
-    sb = [(torch.rand(n, device=dev, generator=g) + 0.5, rnd(n) * 0.1) for n in (P, P, C4)]
-    frags = [torch.empty(t.numel(), dtype=torch.bfloat16, device=dev) for t in ws]
-    recs, blk = (_FragRec * 3)(), 0
-    for r, t, f in zip(recs, ws, frags):
-        r.src, r.dst, r.rows, r.K, r.blk0 = t.data_ptr(), f.data_ptr(), t.shape[0], t.shape[1], blk
-        blk += (t.numel() + 2047) // 2048
-    tab = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
-    ho.call('aod_frag_pack', ho.ptr(tab), 3, blk, ho.stream())
-    ok = True
-    # the bench shape three times, then ragged shapes (partial tiles in both directions, odd image counts: what keep-ratio VOC batches produce)
-    for B, H, W in ((B, H, W),) * 3 + ((2, 13, 37), (3, 7, 129), (1, 38, 50)):
-        x = rnd(B * H * W, C4).relu().bfloat16()
-        a = ho.bottleneck128_fwd(x, B, H, W, ws[0], *sb[0], ws[1], *sb[1], ws[2], *sb[2], keep=True)
-        b = ho.bottleneck128_fwd(x, B, H, W, frags[0], *sb[0], frags[1], *sb[1], frags[2], *sb[2], keep=True, frag=True)
-        ok = ok and all(torch.equal(u, v) for u, v in zip(a, b))
-    if not ok:
-        warnings.warn('aod_bottleneck256f_fwd failed its self-check against aod_bottleneck256_fwd on this device: using the LDS-ring form')
-    return ok
-
-
-def _frag_form(blk):
-    """AOD_BOTTLENECK_FRAG=1: the 256-plane block takes the register-streamed kernel with fragment-major filter images.  OFF by default
-    (round 4): logically equivalent variants of that kernel miscomputed a few lanes and the cause was never found, so
-    the LDS-ring form -- 0.15 ms per step slower, no such history -- is what ships; the opt-in still runs the self-check first."""
-    if blk.planes != 256 or _os.environ.get('AOD_BOTTLENECK_FRAG', '0') != '1':
-        return False
-    dev = blk.conv1.weight.device
-    ok = _FRAG_OK.get(dev)
-    if ok is None:
-        if torch.cuda.is_current_stream_capturing():
-            return False                     # (never decided inside a capture: the eager warm-up iterations come first)
-        ok = _FRAG_OK[dev] = _frag_selfcheck(dev)
-    return ok
-
-
 def bottleneck128_applies(blk, x):
     """an identity bottleneck of the 128-plane stage (resnet.py:262-301: 512 -> 128 -> 128 -> 512, stride 1, no downsample branch) whose
     forward keeps nothing for a backward pass (inference / frozen): one launch (aod_bottleneck128_fwd)"""
@@ -1232,11 +1147,9 @@ def bottleneck128_train_fwd(x, blk):
     p1 = PREP.get(blk.conv1.weight, bn(blk.norm1), Cin, blk.norm1.eps)                  # (Cin = the row width of x: the X-layout width in the x3 mode)
     p2 = PREP.get(blk.conv2.weight, bn(blk.norm2), ho.width(blk.planes), blk.norm2.eps)
     p3 = PREP.get(blk.conv3.weight, bn(blk.norm3), ho.width(blk.planes), blk.norm3.eps)
-    fr = _frag_form(blk)
-    w1, w2, w3 = ((PREP.frag(q, 'f') for q in (p1, p2, p3)) if fr else (p1.wf, p2.wf, p3.wf))
     with torch.no_grad():
-        y, t1, t2 = ho.bottleneck128_fwd(as_rows(x.detach()), B, H, W, w1, p1.scale, p1.shift, w2, p2.scale, p2.shift, w3, p3.scale,
-                                         p3.shift, keep=True, frag=fr)
+        y, t1, t2 = ho.bottleneck128_fwd(as_rows(x.detach()), B, H, W, p1.wf, p1.scale, p1.shift, p2.wf, p2.scale, p2.shift, p3.wf, p3.scale,
+                                         p3.shift, keep=True)
     return t1, t2, y
 
 
@@ -1246,9 +1159,7 @@ def bottleneck128_fwd(x, blk):
     p1 = PREP.get(blk.conv1.weight, bn(blk.norm1), Cin, blk.norm1.eps)
     p2 = PREP.get(blk.conv2.weight, bn(blk.norm2), ho.width(blk.planes), blk.norm2.eps)
     p3 = PREP.get(blk.conv3.weight, bn(blk.norm3), ho.width(blk.planes), blk.norm3.eps)
-    fr = _frag_form(blk)
-    w1, w2, w3 = ((PREP.frag(q, 'f') for q in (p1, p2, p3)) if fr else (p1.wf, p2.wf, p3.wf))
-    out = ho.bottleneck128_fwd(as_rows(x.detach()), B, H, W, w1, p1.scale, p1.shift, w2, p2.scale, p2.shift, w3, p3.scale, p3.shift, frag=fr)
+    out = ho.bottleneck128_fwd(as_rows(x.detach()), B, H, W, p1.wf, p1.scale, p1.shift, p2.wf, p2.scale, p2.shift, p3.wf, p3.scale, p3.shift)
     return as_nchw(out, B, H, W)
 
 
