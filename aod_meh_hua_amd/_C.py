@@ -188,6 +188,11 @@ _SIGS = {
     'aod_cdal_ws_len': (SZ, [I32, P, I32, I32]),
     'aod_cdal_descriptor': (C.c_int, [P, I32, P, I32, I32, F32, P, I64, P, I64, P]),
     'aod_det_uncertainty': (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P, P, P, P]),
+    'aod_det_uncertainty_ex': (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P, P, P, P, P]),
+    'aod_object_descriptors': (C.c_int, [P, I32, P, P, I32, I32, I32, P, I32, P, P, P, P, I32, I32, F32, P, P, P, P, P, P]),
+    'aod_ccms_max_images': (C.c_int, []),
+    'aod_ccms_distance': (C.c_int, [P, P, P, P, I32, I32, I32, P, P]),
+    'aod_kcenter_greedy_matrix': (C.c_int, [P, I64, P, I64, I64, P, P, P, P, P]),
     'aod_loc_stability_max_levels': (C.c_int, []),
     'aod_pixel_noise': (C.c_int, [P, P, I32, I32, I32, I32, P, P, F32, I32, U64, P, P]),
     'aod_loc_stability': (C.c_int, [P, P, P, I32, I32, I32, F32, I32, I32, P, P, P]),

@@ -84,6 +84,18 @@ class Uncertainty_fns:
         return CDAL_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr)
 
     @staticmethod
+    def CCMS(cfg, *args, **kwargs):
+        # uncertainty pre-selection + instance-level diversity (PPAL, Yang et al., CVPR 2024): needs the labelled set (it is
+        # excluded from the candidates) and selects by rank like Coreset.  Of the HUA options only score_thr is read (the object gate);
+        # candidate_factor, max_obj, measure and aggregate are its own
+        if kwargs.get('X_L') is None:
+            raise TypeError("Uncertainty_fns.CCMS needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
+        model, dataloader = args
+        own = {k: kwargs[k] for k in ('candidate_factor', 'max_obj', 'measure', 'aggregate') if kwargs.get(k) is not None}
+        thr = kwargs.get('score_thr')
+        return CCMS_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr, **own)
+
+    @staticmethod
     def _loc_stability(combine, cfg, *args, **kwargs):
         # localization stability (Kao et al., ACCV 2018): reads score_thr (the object gate, default 0.3), sigmas, seed and
         # same_class; the HUA options that calculate_uncertainty's callers pass for the Entropy_* pools have no meaning for it
@@ -544,6 +556,83 @@ def CDAL_uncertainty(cfg, model, data_loader, X_L=None, budget=None, score_thr=0
     picks, _ = kcenter_greedy(desc, X_L, budget, metric='symkl')
     scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
     scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
+    return scores.cpu()
+
+
+@torch.no_grad()
+def single_gpu_object_descriptors(model, data_loader, max_obj=32, score_thr=0.3, measure='entropy', aggregate='sum', **kwargs):
+    """CCMS object descriptors and the stage-1 score of the whole pool on _PoolPass's loop: the pool is sharded over the
+    ranks, batches come from the prefetch workers through pinned memory, and while the batch shape repeats (and AOD_HIP_GRAPH != 0) the
+    forward (isEval=True, _padded=True, objDesc=max_obj: backbone, neck, the two prediction towers, selection, NMS, the posterior score
+    and the gather -- one graph on one stream, the form single_gpu_map uses) replays one captured graph.  The rows of its static outputs
+    are copied into preallocated pool tensors behind each replay on the same stream, so they have been read before the next replay
+    overwrites them; parallel.gather_rows makes the pool tensors whole on every rank.
+
+    Returns a dict of device tensors: unc [N] fp32 (the posterior `measure` aggregated by `aggregate` over the detections whose score
+    exceeds score_thr: Posterior_uncertainty's bits), feat [N, max_obj, C] fp32, cls [N, max_obj] int32 (-1 pad), w [N, max_obj] fp32,
+    cnt [N] int32, missing [N] int32 (always 0).  The feature store is N * max_obj * C * 4 bytes: 542 MB for the 16 551 images of
+    VOC07+12 trainval at max_obj = 32, C = 256.  A row's bits depend on its image alone -- not on the batch size, the rank count, or
+    eager / replayed execution."""
+    from ..scoring import CCMS_MAX_OBJ, UNC_AGGREGATES, UNC_MEASURES
+    if measure not in UNC_MEASURES:
+        raise ValueError(f"single_gpu_object_descriptors: unknown measure {measure!r} (expected 'entropy', 'margin' or 'leastconf')")
+    if aggregate not in UNC_AGGREGATES:
+        raise ValueError(f"single_gpu_object_descriptors: unknown aggregate {aggregate!r} (expected 'max', 'mean' or 'sum')")
+    max_obj, score_thr = int(max_obj), float(score_thr)
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'single_gpu_object_descriptors: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    if score_thr != score_thr:
+        raise ValueError('single_gpu_object_descriptors: score_thr is NaN')
+    module = getattr(model, 'module', model)
+    neck = getattr(module, 'neck', None)
+    if not (hasattr(neck, 'num_outs') and isinstance(getattr(neck, 'out_channels', None), int)):
+        raise NotImplementedError(f'single_gpu_object_descriptors: CCMS object descriptors are built for the FPN pyramid of the RetinaNet '
+                                  f'detectors, not for {type(module).__name__} / {type(neck).__name__} (SSD: its source maps do not share a '
+                                  'channel count)')
+    model.eval()
+    dev = next(model.parameters()).device
+    pool = _PoolPass(data_loader, dev)
+    N, Cc = pool.N, int(neck.out_channels)
+    store = dict(unc=torch.zeros(N, dtype=torch.float32, device=dev), feat=torch.zeros(N, max_obj, Cc, dtype=torch.float32, device=dev),
+                 cls=torch.full((N, max_obj), -1, dtype=torch.int32, device=dev), w=torch.zeros(N, max_obj, dtype=torch.float32, device=dev),
+                 cnt=torch.zeros(N, dtype=torch.int32, device=dev), missing=torch.zeros(N, dtype=torch.int32, device=dev))
+    kwargs.setdefault('isUnc', False)
+    fkw = dict(kwargs, objDesc=max_obj, score_thr=score_thr, unc_measure=measure, unc_aggregate=aggregate)
+    gscore = _graphed(model, dev, ('obj_desc',), fkw, isEval=True, _padded=True)
+    names = ('unc', 'feat', 'cls', 'w', 'cnt', 'missing')
+    for idxs, image_ids, data in pool.batches():
+        out = _replay_or_eager(gscore, data, image_ids,
+                               lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **fkw))
+        for name, t in zip(names, out[3:]):                 # (a batch is a run of consecutive images)
+            store[name][idxs[0]:idxs[0] + len(idxs)].copy_(t)
+    owned = torch.zeros(N, dtype=torch.bool, device=dev)
+    owned[pool.all_ids] = True
+    return {name: gather_rows(t, owned)[0] for name, t in store.items()}
+
+
+def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_factor=4, max_obj=32, score_thr=0.3, measure='entropy',
+                     aggregate='sum', **kwargs):
+    """CCMS acquisition (the two-stage pick of PPAL: C. Yang, L. Huang, E. J. Crowley, "Plug and Play Active Learning for Object
+    Detection", CVPR 2024, without its training-side class-difficulty EMA; the reference has none) in the form update_X_L takes.
+    Stage 1: the posterior score of every image (single_gpu_object_descriptors) ranks the unlabelled images; the top
+    M = min(ceil(candidate_factor * budget), #unlabelled) are the candidates (scoring.ccms_candidates).  Stage 2: the [M, M]
+    category-conditioned matching distance between them (scoring.ccms_distance), then k-center greedy on it with no initial centers
+    (scoring.kcenter_greedy_matrix): the first pick is the most uncertain candidate, every later one the candidate farthest from the picks
+    so far.  Every rank runs stage 2 on the same tensors and gets the same picks.  budget: default cfg.X_S_size.  Returns a CPU [N] fp32
+    vector: the image picked at step t = 0 .. budget - 1 scores budget - t, every other image 0 -- with a falsy zeroRate update_X_L's
+    arg[-X_S_size:] selects exactly the picks."""
+    from ..scoring import ccms_candidates, ccms_distance, kcenter_greedy_matrix
+    if X_L is None:
+        raise TypeError('CCMS_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are excluded from the candidates')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    pool = single_gpu_object_descriptors(model, data_loader, max_obj=max_obj, score_thr=score_thr, measure=measure, aggregate=aggregate, **kwargs)
+    cand = ccms_candidates(pool['unc'], X_L, budget, candidate_factor)
+    dev = pool['unc'].device
+    ci = torch.from_numpy(cand).to(dev)
+    dist = ccms_distance(pool['feat'][ci].contiguous(), pool['cls'][ci].contiguous(), pool['w'][ci].contiguous(), pool['cnt'][ci].contiguous())
+    picks, _ = kcenter_greedy_matrix(dist, [], budget)
+    scores = torch.zeros(pool['unc'].shape[0], dtype=torch.float32, device=dev)
+    scores[ci[picks]] = torch.arange(budget, 0, -1, dtype=torch.float32, device=dev)
     return scores.cpu()
 
 

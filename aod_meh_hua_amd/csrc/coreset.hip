@@ -18,6 +18,7 @@
 //    j + 64m), four running sums per lane, ((s0 + s1) + (s2 + s3)), xor butterfly: a function of the two rows and D alone.
 //    aod_kcenter_greedy_ex(..., metric = 1): the same kernels instantiated for the symmetrised KL divergence of [P | ln P] rows (CDAL,
 //    DESIGN 3j; kc_dists); metric 0 keeps the arithmetic above.
+//    aod_kcenter_greedy_matrix (CCMS): the same scheme on a precomputed [N][N] distance matrix (kcenter_matrix_* below).
 //    Non-negative floats order like their bit patterns as unsigned integers (+inf included) and ~i makes the LOWEST index win a tie.
 #include <hip/hip_runtime.h>
 #include "../../include/aod_hip.h"
@@ -361,6 +362,87 @@ static int kc_greedy(const float* desc, int64_t N, int D, const int64_t* labelle
                        (const u64*)keys[(t - 1) & 1], nkeys, keys[t & 1], (long long*)picks, radius, (int)t);
     nkeys = grid;
   }
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ k-center on a matrix
+// aod_kcenter_greedy_matrix (CCMS): the same prepare / mark / keys / one-launch-per-pick scheme, tie rule and workspace on a
+// precomputed [N][N] distance matrix: the sweeps read dist[p][i] (a thread per row: coalesced along the center's matrix row) instead of
+// computing a distance.  A minimum is exact in any order, so nothing here depends on the grid.
+__global__ __launch_bounds__(256) void kcenter_matrix_centers_kernel(const float* __restrict__ dist, long long N, const long long* __restrict__ lab,
+                                                                     long long n_lab, float* __restrict__ mind) {
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < N; i += 256ll * gridDim.x) {
+    float m = mind[i];
+    for (long long c = 0; c < n_lab; ++c) {
+      const long long ci = lab[c];
+      if (ci >= 0 && ci < N) m = fminf(m, dist[ci * N + i]);      // (the caller validates; an index outside the matrix is never dereferenced)
+    }
+    mind[i] = m;
+  }
+}
+
+__global__ __launch_bounds__(256) void kcenter_matrix_step_kernel(const float* __restrict__ dist, long long N, float* __restrict__ mind,
+                                                                  unsigned char* __restrict__ sel, const u64* __restrict__ keys_in, int nkeys,
+                                                                  u64* __restrict__ keys_out, long long* __restrict__ picks,
+                                                                  float* __restrict__ radius, int t) {
+  __shared__ u64 red[KC_WAVES];
+  u64 best = 0;
+  for (int j = threadIdx.x; j < nkeys; j += 256) {
+    const u64 k = keys_in[j];
+    best = k > best ? k : best;
+  }
+  best = kc_block_max(best, red);
+  const unsigned p = ~(unsigned)(best & 0xffffffffull);
+  const bool valid = best != 0 && (long long)p < N;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    picks[t - 1] = valid ? (long long)p : -1ll;
+    radius[t - 1] = __uint_as_float((unsigned)(best >> 32));
+    if (valid) sel[p] = 1;
+  }
+  if (!valid) {                                                   // workgroup-uniform
+    if (threadIdx.x == 0) keys_out[blockIdx.x] = 0;
+    return;
+  }
+  const float* row = dist + (long long)p * N;
+  u64 key = 0;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < N; i += 256ll * gridDim.x) {
+    const float m = fminf(mind[i], row[i]);
+    mind[i] = m;
+    if (i != (long long)p && !sel[i]) {                            // (workgroup 0 may or may not have set sel[p] yet: p is excluded by name)
+      const u64 k = kc_key(m, (unsigned)i);
+      key = k > key ? k : key;
+    }
+  }
+  key = kc_block_max(key, red);
+  if (threadIdx.x == 0) keys_out[blockIdx.x] = key;
+}
+
+extern "C" int aod_kcenter_greedy_matrix(const float* dist, int64_t N, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
+                                         float* radius, float* mind, void* ws, aod_stream_t stream) {
+  AOD_CHECK_ARG(N >= 1 && N <= 0x7fffffffll, "kcenter_greedy_matrix: 1 .. 2^31 - 1 rows (got %lld)", (long long)N);
+  AOD_CHECK_ARG(n_labelled >= 0 && n_labelled <= N, "kcenter_greedy_matrix: labelled count %lld outside 0 .. N = %lld", (long long)n_labelled,
+                (long long)N);
+  AOD_CHECK_ARG(budget >= 1 && budget <= N - n_labelled, "kcenter_greedy_matrix: budget %lld outside 1 .. %lld unselected rows", (long long)budget,
+                (long long)(N - n_labelled));
+  AOD_CHECK_ARG(dist && picks && radius && mind && ws && (labelled || n_labelled == 0), "kcenter_greedy_matrix: null pointer");
+  AOD_CHECK_ARG((((size_t)dist) & 3) == 0 && (((size_t)ws) & 7) == 0, "kcenter_greedy_matrix: dist must be 4-B aligned, ws 8-B aligned");
+  hipStream_t st = (hipStream_t)stream;
+  u64* keys[2] = {(u64*)ws, (u64*)ws + KC_MAX_GRID};
+  unsigned char* sel = (unsigned char*)ws + (size_t)2 * KC_MAX_GRID * sizeof(u64);
+  const int egrid = (int)((N + 255) / 256 > KC_MAX_GRID ? KC_MAX_GRID : (N + 255) / 256);
+  hipLaunchKernelGGL(kcenter_prepare_kernel, dim3(egrid), dim3(256), 0, st, mind, sel, (long long)N);
+  if (n_labelled > 0) {
+    const long long mg = (n_labelled + 255) / 256;
+    hipLaunchKernelGGL(kcenter_mark_kernel, dim3((unsigned)(mg > KC_MAX_GRID ? KC_MAX_GRID : mg)), dim3(256), 0, st, (const long long*)labelled,
+                       (int)n_labelled, sel, (long long)N);
+    hipLaunchKernelGGL(kcenter_matrix_centers_kernel, dim3(egrid), dim3(256), 0, st, dist, (long long)N, (const long long*)labelled,
+                       (long long)n_labelled, mind);
+  }
+  hipLaunchKernelGGL(kcenter_keys_kernel, dim3(egrid), dim3(256), 0, st, (const float*)mind, (const unsigned char*)sel, (long long)N, keys[0]);
+  for (int64_t t = 1; t <= budget; ++t)
+    hipLaunchKernelGGL(kcenter_matrix_step_kernel, dim3(egrid), dim3(256), 0, st, dist, (long long)N, mind, sel, (const u64*)keys[(t - 1) & 1], egrid,
+                       keys[t & 1], (long long*)picks, radius, (int)t);
   AOD_LAUNCH_CHECK();
   return 0;
 }

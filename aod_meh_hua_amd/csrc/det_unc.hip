@@ -17,7 +17,8 @@
 //      hashes (every lane of a wave reads the same LDS words: broadcasts, 16 B per read) and compares the five words in global memory only
 //      on a hash hit.  With max_num <= 128 the idle waves take further parts of the tile: wave w scans part w / ndw for the detection rows
 //      of wave w % ndw; the lowest index over the parts is the minimum of the parts' own lowest.
-//   3. a thread per detection row: the measure of its row (the classes in column order), written to obj_out and to LDS
+//   3. a thread per detection row: the measure of its row (the classes in column order), written to obj_out and to LDS; the matched
+//      candidate row itself goes to obj_cand (aod_det_uncertainty_ex: what the CCMS object descriptors of DESIGN 3o are gathered by)
 //   4. the aggregate: a pairwise tree over the next power of two >= max_num in LDS -- rows that are no object hold 0 -- so the association of
 //      the sum depends on j and max_num alone: an image has the same score bits alone, at any place of any batch, eager or replayed.
 #include <hip/hip_runtime.h>
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
                                                         const float* __restrict__ dets, const long long* __restrict__ labels,
                                                         const int* __restrict__ num, int n, int W, int max_num, int layout, int measure,
                                                         int aggregate, float thr, float* __restrict__ unc, float* __restrict__ obj_out,
-                                                        int* __restrict__ missing) {
+                                                        int* __restrict__ missing, int* __restrict__ obj_cand) {
   __shared__ __align__(16) unsigned tile[DU_TILE];
   __shared__ unsigned dhash[DU_MAX_DET];
   __shared__ int lab[DU_MAX_DET];          // the label of an object row; -1: no object; -2: an object whose label names no column
@@ -149,6 +150,7 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
     if (j < max_num) {
       const int l = lab[j];
       float o = NAN;
+      int kc = -1;                                           // (obj_cand: the matched candidate row of an object, else -1)
       if (l != -1) {
         int k = INT_MAX;
         if (l >= 0)
@@ -158,9 +160,11 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
         } else {
           m = o = du_measure(sc + (long long)k * W, used, layout, measure);
           flag = 1;
+          kc = k;
         }
       }
       if (obj_out) obj_out[(long long)b * max_num + j] = o;
+      if (obj_cand) obj_cand[(long long)b * max_num + j] = kc;
     }
     val[j] = m;
     lab[j] = flag;            // (a row's lab[] and found[] words are read by the thread that owns the row alone)
@@ -186,9 +190,11 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
   }
 }
 
-extern "C" int aod_det_uncertainty(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
-                                   int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
-                                   float* obj_out, int32_t* missing, aod_stream_t stream) {
+// obj_cand [B][max_num] int32 (nullable): the candidate row the lookup matched to every object row, -1 for a row that is no object or has none
+// (aod_object_descriptors reads the neck row of that candidate's anchor: no second matching pass).  The other outputs are aod_det_uncertainty's.
+extern "C" int aod_det_uncertainty_ex(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
+                                      int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
+                                      float* obj_out, int32_t* missing, int32_t* obj_cand, aod_stream_t stream) {
   AOD_CHECK_ARG(layout >= 0 && layout <= 2, "det_uncertainty: layout %d is none of 0 (cat), 1 (cat_bg), 2 (sigmoid)", layout);
   AOD_CHECK_ARG(measure >= 0 && measure <= 2, "det_uncertainty: measure %d is none of 0 (entropy), 1 (margin), 2 (leastconf)", measure);
   AOD_CHECK_ARG(aggregate >= 0 && aggregate <= 2, "det_uncertainty: aggregate %d is none of 0 (max), 1 (mean), 2 (sum)", aggregate);
@@ -199,13 +205,21 @@ extern "C" int aod_det_uncertainty(const float* boxes, const float* scores, cons
   const int used = layout == 1 ? W : W - 1;
   AOD_CHECK_ARG(measure != 1 || used >= 2, "det_uncertainty: margin needs two used columns (layout %d reads %d of W = %d)", layout, used, W);
   AOD_CHECK_ARG(boxes && scores && dets && labels && num && unc, "det_uncertainty: null pointer");
-  AOD_CHECK_ARG(((((size_t)boxes) | ((size_t)scores) | ((size_t)dets) | ((size_t)num) | ((size_t)unc) | ((size_t)obj_out) | ((size_t)missing)) & 3) == 0 &&
+  AOD_CHECK_ARG(((((size_t)boxes) | ((size_t)scores) | ((size_t)dets) | ((size_t)num) | ((size_t)unc) | ((size_t)obj_out) | ((size_t)missing) |
+                   ((size_t)obj_cand)) & 3) == 0 &&
                     (((size_t)labels) & 7) == 0,
                 "det_uncertainty: pointers must be aligned to their element size");
   AOD_CHECK_ARG(score_thr == score_thr, "det_uncertainty: score_thr is NaN");
   AOD_CHECK_ARG(n <= (1 << 30), "det_uncertainty: up to 2^30 candidate rows per image (got n = %d)", n);
   hipLaunchKernelGGL(det_unc_kernel, dim3((unsigned)B), dim3(DU_TB), 0, (hipStream_t)stream, (const unsigned*)boxes, scores, dets,
-                     (const long long*)labels, num, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing);
+                     (const long long*)labels, num, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing, obj_cand);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int aod_det_uncertainty(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
+                                   int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
+                                   float* obj_out, int32_t* missing, aod_stream_t stream) {
+  return aod_det_uncertainty_ex(boxes, scores, dets, labels, num, B, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing,
+                                nullptr, stream);
 }

@@ -256,6 +256,11 @@ class Lambda_L2Net(L_AnchorHead):
         """Lambda_L2.py:398-420.  `_preds` = the result of test_heads() computed earlier (graphs.GraphedScore runs the conv half and the
         selection / HUA half as two graphs on two streams: the half below keeps at most 16 workgroups busy)."""
         from ...scoring import POSTERIOR_POOLS
+        if kwargs['isEval'] and kwargs.get('objDesc'):
+            # CCMS object descriptors (DESIGN 3o): the padded detections, their posterior score and the normalised neck rows of their
+            # anchors' cells.  Like the posterior pools it reads no lambda: the same conv half, so the score has the same bits
+            outs = _preds[0] if _preds is not None else self.test_heads(feats, with_L=False)[0]
+            return self.get_bboxes(*outs, img_metas, rescale=rescale, _feats=list(feats), **kwargs)
         if not kwargs['isEval'] and kwargs.get('isUnc') and kwargs.get('uPool') in POSTERIOR_POOLS:
             # posterior uncertainty pools (DESIGN 3l): the class posterior alone -- the lambda tower is neither run nor passed on
             outs = _preds[0] if _preds is not None else self.test_heads(feats, with_L=False)[0]

@@ -110,6 +110,8 @@ class MyRetinaHead(L_AnchorHead):
         refuse_hua(self, **kwargs)
         outs, _ = _preds if _preds is not None else self.test_heads(feats)
         with_nms = not (not kwargs['isEval'] and kwargs.get('uPool') == 'Entropy_NoNMS')
+        if kwargs['isEval'] and kwargs.get('objDesc'):      # CCMS object descriptors: score_batch reads the neck outputs
+            kwargs = dict(kwargs, _feats=list(feats))
         results_list = self.get_bboxes(*outs, img_metas, rescale=rescale, with_nms=with_nms, **kwargs)
         if not kwargs['isEval']:
             from ...scoring import POSTERIOR_POOLS

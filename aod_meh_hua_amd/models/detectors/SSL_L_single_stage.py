@@ -56,6 +56,12 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
         if kwargs['isEval'] and kwargs.get('justFeat'):
             # Core-set descriptors (apis/test.py single_gpu_descriptors): the neck outputs as they lie in the pyramid buffer; no head is launched
             return self._just_feat(img)
+        if kwargs['isEval'] and kwargs.get('objDesc'):
+            # CCMS object descriptors (apis/test.py single_gpu_object_descriptors): the static (dets, labels, num, unc, feat, cls, w, cnt,
+            # missing) of the padded evaluation form, max_obj = objDesc
+            if not kwargs.get('_padded'):
+                raise ValueError('objDesc is offered with the padded evaluation outputs only (isEval=True, _padded=True)')
+            self._check_obj_desc()
         feat = self.extract_feat(img)
         if kwargs['isEval'] and kwargs.get('justOut'):
             # MyRetinaSingleStage.py:46-49 (honoured with isEval only): the per-level classification maps [B, A*C, h, w] fp32 of an ensemble
@@ -83,6 +89,9 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
     def _just_feat(self, img):
         return tuple(self.extract_feat(img))
 
+    def _check_obj_desc(self):
+        pass
+
     def aug_test(self, imgs, img_metas, rescale=False):
         raise NotImplementedError('test-time augmentation is not on the MEH/HUA path')
 
@@ -102,6 +111,10 @@ class SSD_L_SingleStageDetector(SSL_L_SingleStageDetector):
     def _just_feat(self, img):
         raise NotImplementedError('justFeat / Core-set descriptors are built for the FPN pyramid of the RetinaNet detectors, not for SSD '
                                   '(its six source maps have different channel counts and do not lie in one row buffer)')
+
+    def _check_obj_desc(self):
+        raise NotImplementedError('objDesc / CCMS object descriptors are built for the FPN pyramid of the RetinaNet detectors, not for SSD '
+                                  '(its six source maps have different channel counts: the objects of an image would not share a feature space)')
 
 
 @DETECTORS.register_module()

@@ -486,7 +486,7 @@ ACTIVATION_LAYOUT = {'relu': 'cat', 'softmax': 'cat_bg', 'sigmoid': 'sigmoid'}  
 UNC_MAX_DET = 1024
 
 
-def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregate='max', score_thr=0.3, want_objects=False):
+def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregate='max', score_thr=0.3, want_objects=False, want_cand=False):
     """Posterior uncertainty of every image of a batch (aod_det_uncertainty): entropy, 1-vs-2 margin or least confidence of the
     class posterior of every detection, aggregated over the image's detections by max, mean or sum; an image without an object scores 0.
 
@@ -495,7 +495,9 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     family), 'cat_bg' (all W columns, background last: MyLSSDHead) or 'sigmoid' (the first W - 1 columns are independent Bernoulli
     posteriors: MyRetinaHead).  A detection row j < num[b] with a score > score_thr (strict) is an object; its score row is looked up among
     the candidates by its box and score bits.  Returns unc [B] fp32 on the device (no host sync), or with want_objects
-    (unc, obj_out [B, max_num] fp32 -- NaN where the row is no object --, missing [B] int32 -- objects without a candidate row: always 0)."""
+    (unc, obj_out [B, max_num] fp32 -- NaN where the row is no object --, missing [B] int32 -- objects without a candidate row: always 0).
+    want_cand (aod_det_uncertainty_ex; the same unc bits) appends obj_cand [B, max_num] int32: the candidate row matched to every object
+    row, -1 elsewhere -- what object_descriptors reads."""
     if layout not in UNC_LAYOUTS:
         raise ValueError(f"det_uncertainty: unknown layout {layout!r} (expected 'cat', 'cat_bg' or 'sigmoid')")
     if measure not in UNC_MEASURES:
@@ -539,9 +541,206 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     unc = torch.empty(B, dtype=torch.float32, device=dev)
     obj_out = torch.empty(B, max_num, dtype=torch.float32, device=dev) if want_objects else None
     missing = torch.empty(B, dtype=torch.int32, device=dev) if want_objects else None
+    if want_cand:
+        obj_cand = torch.empty(B, max_num, dtype=torch.int32, device=dev)
+        call('aod_det_uncertainty_ex', ptr(boxes), ptr(scores), ptr(dets), ptr(labels), ptr(num), B, n, W, max_num, UNC_LAYOUTS[layout],
+             UNC_MEASURES[measure], UNC_AGGREGATES[aggregate], score_thr, ptr(unc), ptr(obj_out), ptr(missing), ptr(obj_cand), stream())
+        return (unc, obj_out, missing, obj_cand) if want_objects else (unc, obj_cand)
     call('aod_det_uncertainty', ptr(boxes), ptr(scores), ptr(dets), ptr(labels), ptr(num), B, n, W, max_num, UNC_LAYOUTS[layout],
          UNC_MEASURES[measure], UNC_AGGREGATES[aggregate], score_thr, ptr(unc), ptr(obj_out), ptr(missing), stream())
     return (unc, obj_out, missing) if want_objects else unc
+
+
+CCMS_MAX_OBJ = 64
+CCMS_MAX_CHANNELS = 256
+CCMS_MAX_IMAGES = int(_C.lib.aod_ccms_max_images())      # (written once, in csrc/ccms.hip)
+
+
+def _cpu_refusal(name):
+    return _C.AodHipError(f'{name} needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+
+
+def object_descriptors(feats, cand, dets, labels, num, obj_cand, num_anchors, max_obj=32, score_thr=0.3, channels=None, x3=None):
+    """Object descriptors of every image of a batch (aod_object_descriptors; DESIGN 3o): per detection with a score > score_thr (strict;
+    the first max_obj of them in row order) the L2-normalised neck output row of the cell its anchor sits in.
+
+    feats: 1..8 per-level maps [B, width, h_l, w_l], bf16 channels_last device tensors as the neck hands them out (plain bf16 or X-layout
+    rows, as pool_descriptor takes them; `channels` / `x3` likewise).  cand: the Candidates of pre_nms (cand_anchor [B, n] int32 is read);
+    dets [B, max_num, 5], labels [B, max_num] int64, num [B] int32: the outputs of multiclass_nms_batch; obj_cand [B, max_num] int32: the
+    matched candidate rows of det_uncertainty(..., want_cand=True) with the same score_thr.  num_anchors: anchors per cell, one int or one
+    per level.  Returns (feat [B, max_obj, C] fp32, cls [B, max_obj] int32 (-1 pad), w [B, max_obj] fp32 (0 pad), cnt [B] int32,
+    missing [B] int32: objects without a candidate row, always 0) on the device, no host sync.  An image's rows have the same bits alone
+    and inside any batch."""
+    from . import hipops as ho
+    feats = list(feats)
+    L = len(feats)
+    if not 1 <= L <= 8:
+        raise ValueError(f'object_descriptors: 1..8 levels are supported, got {L}')
+    x3 = bool(ho.X3 if x3 is None else x3)
+    for l, t in enumerate(feats):
+        if not torch.is_tensor(t) or t.dtype != torch.bfloat16 or t.dim() != 4:
+            raise ValueError(f'object_descriptors: level {l} is not a bf16 [B, width, h, w] tensor')
+        if t.shape[0] != feats[0].shape[0] or t.shape[1] != feats[0].shape[1] or t.numel() == 0:
+            raise ValueError(f'object_descriptors: level {l} has shape {tuple(t.shape)}, level 0 has {tuple(feats[0].shape)}: every level needs '
+                             'the same positive batch size and width')
+        if not t.permute(0, 2, 3, 1).is_contiguous():
+            raise ValueError(f'object_descriptors: level {l} is not channels_last-dense; no copy is made here')
+    B, Wd = int(feats[0].shape[0]), int(feats[0].shape[1])
+    if x3 and Wd % 64:
+        raise ValueError(f'object_descriptors: X-layout rows are a multiple of 64 columns wide, got {Wd}')
+    Cc = int(channels) if channels is not None else (Wd // 2 if x3 else Wd)
+    if Cc < 8 or Cc % 8 or Cc > 1024 or (ho.xw(Cc) if x3 else Cc) != Wd:
+        raise ValueError(f'object_descriptors: {Cc} channels (a multiple of 8 in 8..1024) do not make rows of {Wd} columns')
+    na = [int(v) for v in num_anchors] if isinstance(num_anchors, (list, tuple)) else [int(num_anchors)] * L
+    if len(na) != L or min(na) < 1:
+        raise ValueError(f'object_descriptors: num_anchors {num_anchors!r} does not name a positive count for each of the {L} levels')
+    max_obj = int(max_obj)
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'object_descriptors: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('object_descriptors: score_thr is NaN')
+    anchor = getattr(cand, 'cand_anchor', None)
+    for name, t, dt, nd in (('cand.cand_anchor', anchor, torch.int32, 2), ('dets', dets, torch.float32, 3), ('labels', labels, torch.int64, 2),
+                            ('num', num, torch.int32, 1), ('obj_cand', obj_cand, torch.int32, 2)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"object_descriptors: {name} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'object_descriptors: {name} is not contiguous; no copy is made here')
+    n = int(anchor.shape[1])
+    if anchor.shape[0] != B or n < 1:
+        raise ValueError(f'object_descriptors: cand.cand_anchor has shape {tuple(anchor.shape)}: expected ({B}, n) with n >= 1')
+    if dets.shape[0] != B or dets.shape[2] != 5 or not 1 <= dets.shape[1] <= UNC_MAX_DET:
+        raise ValueError(f'object_descriptors: dets has shape {tuple(dets.shape)}: expected ({B}, max_num, 5) with 1 <= max_num <= {UNC_MAX_DET}')
+    max_num = int(dets.shape[1])
+    for name, t in (('labels', labels), ('obj_cand', obj_cand)):
+        if tuple(t.shape) != (B, max_num):
+            raise ValueError(f'object_descriptors: {name} has shape {tuple(t.shape)}, expected ({B}, {max_num})')
+    if tuple(num.shape) != (B,):
+        raise ValueError(f'object_descriptors: num has shape {tuple(num.shape)}, expected ({B},)')
+    ts = feats + [anchor, dets, labels, num, obj_cand]
+    for t in ts:
+        if not t.is_cuda:
+            raise _cpu_refusal('object_descriptors')
+    dev = dets.device
+    if any(t.device != dev for t in ts):
+        raise ValueError(f'object_descriptors: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    feat = torch.empty(B, max_obj, Cc, dtype=torch.float32, device=dev)
+    cls = torch.empty(B, max_obj, dtype=torch.int32, device=dev)
+    w = torch.empty(B, max_obj, dtype=torch.float32, device=dev)
+    cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    missing = torch.empty(B, dtype=torch.int32, device=dev)
+    call('aod_object_descriptors', (C.c_void_p * L)(*[t.data_ptr() for t in feats]), L, (C.c_int32 * L)(*[int(t.shape[2] * t.shape[3]) for t in feats]),
+         (C.c_int32 * L)(*na), Cc, int(x3), B, ptr(anchor), n, ptr(dets), ptr(labels), ptr(num), ptr(obj_cand), max_num, max_obj, score_thr,
+         ptr(feat), ptr(cls), ptr(w), ptr(cnt), ptr(missing), stream())
+    return feat, cls, w, cnt, missing
+
+
+def ccms_distance(feat, cls, w, cnt):
+    """Category-conditioned matching distance between the images of a candidate set (aod_ccms_distance; PPAL, Yang et al., CVPR
+    2024): d(a, b) = max(0, 1 - (S(a->b) + S(b->a)) / 2), S(a->b) the w-weighted mean over a's objects of the largest non-negative cosine
+    to an object of the same class in b.
+
+    feat [M, max_obj, C] fp32, cls [M, max_obj] int32, w [M, max_obj] fp32, cnt [M] int32: contiguous device tensors as object_descriptors
+    writes them (rows >= cnt are not used); M <= 32768, max_obj <= 64, C % 8 == 0, C <= 256.  Returns dist [M, M] fp32 on the device, no
+    host sync: exactly symmetric, zero diagonal, every entry a function of its two images alone."""
+    for name, t, dt, nd in (('feat', feat, torch.float32, 3), ('cls', cls, torch.int32, 2), ('w', w, torch.float32, 2), ('cnt', cnt, torch.int32, 1)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"ccms_distance: {name} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'ccms_distance: {name} is not contiguous; no copy is made here')
+    M, K, Cc = (int(v) for v in feat.shape)
+    if not 1 <= M <= CCMS_MAX_IMAGES:
+        raise ValueError(f'ccms_distance: feat has shape {tuple(feat.shape)}: 1..{CCMS_MAX_IMAGES} images are supported')
+    if not 1 <= K <= CCMS_MAX_OBJ:
+        raise ValueError(f'ccms_distance: feat has shape {tuple(feat.shape)}: 1..{CCMS_MAX_OBJ} objects per image are supported')
+    if Cc < 8 or Cc % 8 or Cc > CCMS_MAX_CHANNELS:
+        raise ValueError(f'ccms_distance: feat has shape {tuple(feat.shape)}: the channels must be a multiple of 8 in 8..{CCMS_MAX_CHANNELS}')
+    for name, t in (('cls', cls), ('w', w)):
+        if tuple(t.shape) != (M, K):
+            raise ValueError(f'ccms_distance: {name} has shape {tuple(t.shape)}, expected ({M}, {K})')
+    if tuple(cnt.shape) != (M,):
+        raise ValueError(f'ccms_distance: cnt has shape {tuple(cnt.shape)}, expected ({M},)')
+    ts = (feat, cls, w, cnt)
+    for t in ts:
+        if not t.is_cuda:
+            raise _cpu_refusal('ccms_distance')
+    dev = feat.device
+    if any(t.device != dev for t in ts):
+        raise ValueError(f'ccms_distance: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    dist = torch.empty(M, M, dtype=torch.float32, device=dev)
+    call('aod_ccms_distance', ptr(feat), ptr(cls), ptr(w), ptr(cnt), M, K, Cc, ptr(dist), stream())
+    return dist
+
+
+def kcenter_greedy_matrix(dist, labelled, budget):
+    """kcenter_greedy on a precomputed distance matrix (aod_kcenter_greedy_matrix): dist [N, N] fp32 contiguous device tensor with
+    non-negative entries; labelled, budget and the returned (picks [budget] int64, radius [budget] fp32) as kcenter_greedy's -- the same
+    tie rule (lowest index), the first pick is row 0 with radius inf when `labelled` is empty, no host sync, and the result does not depend
+    on the order of `labelled`."""
+    if not (torch.is_tensor(dist) and dist.dim() == 2 and dist.dtype == torch.float32 and dist.is_contiguous() and dist.numel() > 0
+            and dist.shape[0] == dist.shape[1]):
+        raise ValueError('kcenter_greedy_matrix: dist must be a non-empty contiguous square 2-D fp32 tensor'
+                         + (f', got shape {tuple(dist.shape)}' if torch.is_tensor(dist) else ''))
+    N = int(dist.shape[0])
+    lab = labelled.detach().cpu().numpy() if torch.is_tensor(labelled) else np.asarray(labelled)
+    lab = lab.reshape(-1)
+    if lab.size and not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f'kcenter_greedy_matrix: labelled must hold integer indices, got {lab.dtype}')
+    lab = lab.astype(np.int64)
+    if lab.size and (lab.min() < 0 or lab.max() >= N):
+        raise ValueError(f'kcenter_greedy_matrix: labelled index outside [0, {N})')
+    if np.unique(lab).size != lab.size:
+        raise ValueError('kcenter_greedy_matrix: labelled holds a duplicated index')
+    budget = int(budget)
+    if budget < 1:
+        raise ValueError(f'kcenter_greedy_matrix: budget must be at least 1, got {budget}')
+    if budget > N - lab.size:
+        raise ValueError(f'kcenter_greedy_matrix: budget {budget} exceeds the {N - lab.size} unselected rows')
+    if not dist.is_cuda:
+        raise _cpu_refusal('kcenter_greedy_matrix')
+    dev = dist.device
+    lab_d = torch.from_numpy(lab).to(dev) if lab.size else None
+    picks = torch.empty(budget, dtype=torch.int64, device=dev)
+    radius = torch.empty(budget, dtype=torch.float32, device=dev)
+    mind = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_C.lib.aod_kcenter_ws_len(N)), dtype=torch.uint8, device=dev)
+    call('aod_kcenter_greedy_matrix', ptr(dist), N, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
+    return picks, radius
+
+
+def ccms_candidates(unc, X_L, budget, factor=4):
+    """Stage 1 of the CCMS pick, on the host: the images not in X_L ordered by `unc` descending -- ties by ascending index --
+    cut to M = min(ceil(factor * budget), number of unlabelled images).  Returns the int64 index array [M]; row 0 is the most uncertain
+    candidate.  M < budget (too few unlabelled images, or factor < 1) and M > 32768 (the distance matrix's limit) raise ValueError."""
+    u = unc.detach().cpu().numpy() if torch.is_tensor(unc) else np.asarray(unc)
+    u = u.reshape(-1).astype(np.float64)
+    N = u.size
+    lab = X_L.detach().cpu().numpy() if torch.is_tensor(X_L) else np.asarray(X_L)
+    lab = lab.reshape(-1)
+    if lab.size and not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f'ccms_candidates: X_L must hold integer indices, got {lab.dtype}')
+    lab = lab.astype(np.int64)
+    if lab.size and (lab.min() < 0 or lab.max() >= N):
+        raise ValueError(f'ccms_candidates: labelled index outside [0, {N})')
+    budget, factor = int(budget), float(factor)
+    if budget < 1:
+        raise ValueError(f'ccms_candidates: budget must be at least 1, got {budget}')
+    if not factor > 0 or factor == float('inf'):
+        raise ValueError(f'ccms_candidates: candidate_factor must be positive and finite, got {factor}')
+    if np.isnan(u).any():
+        raise ValueError('ccms_candidates: the stage-1 scores hold a NaN')
+    free = np.ones(N, bool)
+    free[lab] = False
+    idx = np.nonzero(free)[0]
+    M = min(int(np.ceil(factor * budget)), idx.size)
+    if M < budget:
+        raise ValueError(f'ccms_candidates: {M} candidates (candidate_factor {factor:g}, {idx.size} unlabelled images) are fewer than the '
+                         f'budget {budget}')
+    if M > CCMS_MAX_IMAGES:
+        raise ValueError(f'ccms_candidates: {M} candidates exceed the {CCMS_MAX_IMAGES} images of one distance matrix; lower candidate_factor')
+    order = idx[np.argsort(-u[idx], kind='stable')]          # (idx ascends: a stable sort breaks ties by ascending index)
+    return order[:M].astype(np.int64)
 
 
 LOCSTAB_COMBINES = {'ls': 0, 'ls+c': 1}
@@ -684,6 +883,19 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
         # device metric (apis/test.py single_gpu_map): the padded triple stays on the device -- no num.cpu(), graph-capturable
         if kwargs.get('detUnc'):
             raise ValueError('detUnc is not offered with the padded evaluation outputs')
+        if kwargs.get('objDesc'):
+            # CCMS object descriptors (apis/test.py single_gpu_object_descriptors): two launches behind the NMS kernel -- the
+            # stage-1 posterior score, which also hands out the matched candidate rows, and the gather from the neck outputs; no host sync
+            feats = kwargs.get('_feats')
+            if feats is None:
+                raise ValueError('objDesc needs the neck outputs: the head passes them on as _feats')
+            thr = kwargs.get('score_thr')
+            thr = 0.3 if thr is None else thr
+            unc, obj_cand = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation], kwargs.get('unc_measure') or 'entropy',
+                                            kwargs.get('unc_aggregate') or 'sum', thr, want_cand=True)
+            desc = object_descriptors(feats, cand, dets, labels, num, obj_cand, list(na), int(kwargs['objDesc']), thr,
+                                      channels=getattr(head, 'in_channels', None))
+            return (dets, labels, num, unc) + desc
         return dets, labels, num
     if isUnc and not kwargs.get('isEval') and uPool in POSTERIOR_POOLS:
         # posterior uncertainty pools: one launch behind the NMS kernel on what it and pre_nms left on the device; no lambda is

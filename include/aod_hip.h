@@ -817,6 +817,49 @@ int aod_pixel_noise(const float* src, float* dst, int B, int C, int Hp, int Wp, 
 int aod_loc_stability(const float* dets, const int64_t* labels, const int32_t* num, int K, int B, int max_num, float score_thr, int same_class,
                       int combine, float* unc, float* stab_out, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ CCMS acquisition (csrc/ccms.hip, csrc/coreset.hip, csrc/det_unc.hip):
+ * pre-select the most uncertain images, then spread the picks by k-center greedy under a distance that matches objects of the same class
+ * between two images (PPAL: Yang, Huang, Crowley, "Plug and Play Active Learning for Object Detection", CVPR 2024; its class-difficulty
+ * EMA is not built).  No reference call site; the semantics are fixed in DESIGN 3o.
+ *   aod_det_uncertainty_ex: aod_det_uncertainty (the same arithmetic and bits; it forwards here) with obj_cand [B][max_num] int32
+ *     (nullable): the candidate row matched to detection row j, -1 where the row is no object or has no candidate.
+ *   aod_object_descriptors: the objects of image b are its detection rows j < num[b] with dets[b][j][4] > score_thr (strict), in row
+ *     order, the first max_obj of them (1 <= max_obj <= 64).  Object row j has class labels[b][j], weight dets[b][j][4], candidate row
+ *     k = obj_cand[b][j], global anchor g = cand_anchor[b][k] (cand_anchor [B][n] int32), level l with anchor0_l <= g < anchor0_{l+1}
+ *     (anchor0_{l+1} = anchor0_l + seg_hw[l] * seg_na[l]) and cell (g - anchor0_l) / seg_na[l].  Its raw feature v is row
+ *     b * seg_hw[l] + cell of the level's neck output seg_base[l] (nseg <= 8 HOST pointers to DEVICE rows, 16-B aligned): C bf16 columns
+ *     (x3 = 0) or X-layout rows of 2 * ceil32(C) columns, value = head + tail (x3 = 1); C % 8 == 0, C <= 1024; 16-B loads; pad columns
+ *     and rows outside the levels are never read.  f = v / sqrt(sum_k v_k^2) (IEEE sqrt and division), all zeros when the sum is 0.  An
+ *     object with obj_cand outside [0, n), a label outside int32 or an anchor outside every level is skipped -- it takes no slot -- and
+ *     counted in missing[b] (all such rows of the image, beyond the max_obj cut too; expected 0).  1 <= max_num <= 1024.
+ *     Outputs: feat [B][max_obj][C] fp32 (16-B aligned), cls [B][max_obj] int32, w [B][max_obj] fp32, cnt [B], missing [B] int32; slots
+ *     >= cnt[b] hold (zeros, -1, 0).  One launch, one workgroup per image, no atomics, no host sync.  The sum of squares runs per lane in
+ *     element order, then an xor butterfly: a function of the row alone, so an image has the same bits alone and inside any batch.
+ *   aod_ccms_distance: feat [M][max_obj][C] fp32 (16-B aligned), cls, w [M][max_obj], cnt [M] as above (rows >= cnt[a] are never used);
+ *     1 <= M <= aod_ccms_max_images() = 32768, 1 <= max_obj <= 64 (an image is one or two blocks of 32 objects), C % 8 == 0, C <= 256 (four
+ *     blocks of 32 x C fp32 stay resident in the 160 KB LDS).  dist [M][M] fp32:
+ *       m_i = max(0, max_{j in b, c_j = c_i} <f_i, f_j>) (0 if b has no object of that class), S(a->b) = sum_i w_i m_i / sum_i w_i
+ *       (0 if a has no object), d(a, b) = max(0, 1 - (S(a->b) + S(b->a)) / 2) for a != b, d(a, a) = 0.
+ *     All arithmetic fp32; the sums over i run in row order (separate multiply and add).  Every dot product is a k-ordered fmaf chain on
+ *     v_mfma_f32_32x32x2_f32 with the channels in the order 0 4 1 5 2 6 3 7 8 12 ... (C padded with zeros to 64 / 128 / 256): a function of
+ *     k alone.  No atomics.  An entry is a function of the two images alone -- not of M, its position or the tiling -- and dist[a][b] and
+ *     dist[b][a] hold the same bits.  NaN features are the caller's error.
+ *   aod_kcenter_greedy_matrix: aod_kcenter_greedy's selection (the same prepare / mark / keys / one-launch-per-pick scheme, tie rule, picks /
+ *     radius / mind outputs and aod_kcenter_ws_len(N) workspace) on a precomputed dist [N][N] fp32 with non-negative entries: the sweeps read
+ *     dist[p][i] of center p.  With n_labelled == 0 the first pick is row 0 with radius +inf. */
+int aod_det_uncertainty_ex(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B, int n,
+                           int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc, float* obj_out,
+                           int32_t* missing, int32_t* obj_cand, aod_stream_t stream);
+int aod_object_descriptors(const void* const* seg_base, int nseg, const int32_t* seg_hw, const int32_t* seg_na, int C, int x3, int B,
+                           const int32_t* cand_anchor, int n, const float* dets, const int64_t* labels, const int32_t* num,
+                           const int32_t* obj_cand, int max_num, int max_obj, float score_thr, float* feat, int32_t* cls, float* w, int32_t* cnt,
+                           int32_t* missing, aod_stream_t stream);
+int aod_ccms_max_images(void);
+int aod_ccms_distance(const float* feat, const int32_t* cls, const float* w, const int32_t* cnt, int M, int max_obj, int C, float* dist,
+                      aod_stream_t stream);
+int aod_kcenter_greedy_matrix(const float* dist, int64_t N, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
+                              float* radius, float* mind, void* ws, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

@@ -56,7 +56,14 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         'image by --unc-aggregate; every head has them, the plain RetinaNet and SSD included) '
                         '| LocStability | LocStability_C (localization stability, Kao et al., ACCV 2018: how far the boxes of the clean '
                         'detections move under Gaussian pixel noise of the strengths --noise-levels; LocStability_C adds 1 - the largest '
-                        'detection score; reads detections only, so every detector has them)')
+                        'detection score; reads detections only, so every detector has them) '
+                        '| CCMS (two-stage pick after PPAL, Yang et al., CVPR 2024: the --candidate-factor x budget most uncertain images by '
+                        'the summed posterior entropy, then k-center greedy under the category-conditioned matching distance between '
+                        'their objects; RetinaNet detectors, zeroRate off)')
+    p.add_argument('--candidate-factor', type=float, default=4.0,
+                   help='CCMS pool: the candidate set holds ceil(factor x budget) of the most uncertain unlabelled images (default: 4)')
+    p.add_argument('--max-objects', type=int, default=32,
+                   help='CCMS pool: objects described per image, the first K detections above --hua-score-thr (default: 32, at most 64)')
     p.add_argument('--noise-levels', default='8,16,24,32,40,48',
                    help='noise strengths of the LocStability pools: up to 16 comma-separated standard deviations in 0..255 pixel units '
                         '(default: 8,16,24,32,40,48)')
@@ -267,8 +274,11 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             poolModel = MMDataParallel(model, device_ids=cfg.gpu_ids)
             # Coreset and CDAL take the labelled set (their initial centers) and select by rank, not by score: their vector marks exactly
             # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
-            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL')
+            # CCMS (uncertainty pre-selection, then k-center greedy under the object-matching distance) is handled like them
+            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS'
             pool_kw = dict(X_L=X_L) if coreset else {}
+            if cfg.uncertainty_pool == 'CCMS':
+                pool_kw.update(candidate_factor=args.candidate_factor, max_obj=args.max_objects)
             if cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf'):    # the posterior pools: ordinary scores, zeroRate stays on
                 pool_kw = dict(unc_aggregate=args.unc_aggregate)
             if cfg.uncertainty_pool in ('LocStability', 'LocStability_C'):    # localization stability: ordinary scores too
