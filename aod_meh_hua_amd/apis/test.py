@@ -68,32 +68,24 @@ class Uncertainty_fns:
     def Coreset(cfg, *args, **kwargs):
         # diversity-based selection (Sener & Savarese, ICLR 2018): needs the labelled set as the initial centers.  The HUA options that
         # calculate_uncertainty's callers pass for the Entropy_* pools (score_thr, clsW, ...) have no meaning for a descriptor pass
-        if kwargs.get('X_L') is None:
-            raise TypeError("Uncertainty_fns.Coreset needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
         model, dataloader = args
-        return Coreset_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'))
+        return Coreset_uncertainty(cfg, model, dataloader, **_labelled_options('Coreset', kwargs, score_thr=False))
 
     @staticmethod
     def CDAL(cfg, *args, **kwargs):
         # contextual diversity (Agarwal et al., ECCV 2020), core-set form: like Coreset it needs the labelled set as the initial centers and
         # reads none of the HUA options -- but score_thr, which is its own region threshold too (default 0.3, the same foreground threshold)
-        if kwargs.get('X_L') is None:
-            raise TypeError("Uncertainty_fns.CDAL needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
         model, dataloader = args
-        thr = kwargs.get('score_thr')
-        return CDAL_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr)
+        return CDAL_uncertainty(cfg, model, dataloader, **_labelled_options('CDAL', kwargs))
 
     @staticmethod
     def CCMS(cfg, *args, **kwargs):
         # uncertainty pre-selection + instance-level diversity (PPAL, Yang et al., CVPR 2024): needs the labelled set (it is
         # excluded from the candidates) and selects by rank like Coreset.  Of the HUA options only score_thr is read (the object gate);
         # candidate_factor, max_obj, measure and aggregate are its own
-        if kwargs.get('X_L') is None:
-            raise TypeError("Uncertainty_fns.CCMS needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
         model, dataloader = args
         own = {k: kwargs[k] for k in ('candidate_factor', 'max_obj', 'measure', 'aggregate') if kwargs.get(k) is not None}
-        thr = kwargs.get('score_thr')
-        return CCMS_uncertainty(cfg, model, dataloader, X_L=kwargs['X_L'], budget=kwargs.get('budget'), score_thr=0.3 if thr is None else thr, **own)
+        return CCMS_uncertainty(cfg, model, dataloader, **_labelled_options('CCMS', kwargs), **own)
 
     @staticmethod
     def _loc_stability(combine, cfg, *args, **kwargs):
@@ -130,6 +122,18 @@ _SHARD_STATE = dict(interleaved=False, imbalance=None, over=0)       # pool part
 def calculate_uncertainty(cfg, *args, **kwargs):
     """test.py:65-70."""
     return getattr(Uncertainty_fns, cfg.uncertainty_pool)(cfg, *args, **kwargs)
+
+
+def _labelled_options(pool, kwargs, score_thr=True):
+    """what a diversity pool's wrapper hands on of calculate_uncertainty's kwargs: X_L (required), budget, and score_thr (default 0.3)
+    where the pool reads one"""
+    if kwargs.get('X_L') is None:
+        raise TypeError(f"Uncertainty_fns.{pool} needs the labelled indices: calculate_uncertainty(cfg, model, data_loader, X_L=X_L)")
+    own = dict(X_L=kwargs['X_L'], budget=kwargs.get('budget'))
+    if score_thr:
+        thr = kwargs.get('score_thr')
+        own['score_thr'] = 0.3 if thr is None else thr
+    return own
 
 
 def _unwrap(x):
@@ -460,6 +464,33 @@ def MCDropout_uncertainty(cfg, model, data_loader, **kwargs):
     return single_gpu_mcdropout(model, data_loader, **kwargs).cpu()
 
 
+def _fpn_neck(model, what):
+    """the model's FPN neck; `what` opens the refusal of a detector without one ('<driver>: <its descriptors>')"""
+    module = getattr(model, 'module', model)
+    neck = getattr(module, 'neck', None)
+    if not (hasattr(neck, 'num_outs') and isinstance(getattr(neck, 'out_channels', None), int)):
+        raise NotImplementedError(f'{what} are built for the FPN pyramid of the RetinaNet detectors, not for {type(module).__name__} / '
+                                  f'{type(neck).__name__} (SSD: its source maps do not share a channel count)')
+    return neck
+
+
+def _row_store_pass(model, data_loader, prefix, ctor, fkw, store, write):
+    """The pool pass under the three descriptor drivers, on _PoolPass's loop: one forward per batch (model(..., **ctor, **fkw); while the
+    batch shape repeats it replays the graph cached under `prefix`), then write(out, rows) puts the batch's rows into the preallocated
+    [N, ...] pool tensors `store` (a dict) behind it on the same stream, so the graph's static outputs have been read before the next replay
+    overwrites them.  Returns the dict of the pool tensors made whole on every rank (parallel.gather_rows)."""
+    model.eval()
+    dev = next(iter(store.values())).device
+    pool = _PoolPass(data_loader, dev)
+    gscore = _graphed(model, dev, prefix, fkw, **ctor)
+    for idxs, image_ids, data in pool.batches():
+        out = _replay_or_eager(gscore, data, image_ids, lambda: model(return_loss=False, rescale=True, **ctor, **data, **fkw))
+        write(out, slice(idxs[0], idxs[0] + len(idxs)))          # (a batch is a run of consecutive images)
+    owned = torch.zeros(pool.N, dtype=torch.bool, device=dev)
+    owned[pool.all_ids] = True
+    return {name: gather_rows(t, owned)[0] for name, t in store.items()}
+
+
 @torch.no_grad()
 def single_gpu_descriptors(model, data_loader, **kwargs):
     """Core-set descriptors of the whole pool on _PoolPass's loop: the pool is sharded over the ranks, batches come from the prefetch
@@ -470,24 +501,20 @@ def single_gpu_descriptors(model, data_loader, **kwargs):
     tensor, D = levels * channels of the neck (RetinaNet: 1280); a row's bits depend on its image alone -- not on the batch size, the rank
     count, or eager / replayed execution."""
     from ..scoring import pool_descriptor
-    module = getattr(model, 'module', model)
-    neck = getattr(module, 'neck', None)
-    if not (hasattr(neck, 'num_outs') and isinstance(getattr(neck, 'out_channels', None), int)):
-        raise NotImplementedError(f'single_gpu_descriptors: Core-set descriptors are built for the FPN pyramid of the RetinaNet detectors, not '
-                                  f'for {type(module).__name__} / {type(neck).__name__} (SSD: its source maps do not share a channel count)')
-    model.eval()
-    dev = next(model.parameters()).device
-    pool = _PoolPass(data_loader, dev)
+    neck = _fpn_neck(model, 'single_gpu_descriptors: Core-set descriptors')
     Cc, D = int(neck.out_channels), int(neck.num_outs) * int(neck.out_channels)
-    desc = torch.zeros(pool.N, D, dtype=torch.float32, device=dev)
-    gscore = _graphed(model, dev, ('just_feat',), kwargs, isEval=True, justFeat=True)
-    for idxs, image_ids, data in pool.batches():
-        feats = _replay_or_eager(gscore, data, image_ids,
-                                 lambda: model(return_loss=False, rescale=True, isEval=True, justFeat=True, **data, **kwargs))
-        pool_descriptor(feats, out=desc[idxs[0]:idxs[0] + len(idxs)], channels=Cc)          # (a batch is a run of consecutive images)
-    owned = torch.zeros(pool.N, dtype=torch.bool, device=dev)
-    owned[pool.all_ids] = True
-    return gather_rows(desc, owned)[0]
+    desc = torch.zeros(len(data_loader.dataset), D, dtype=torch.float32, device=next(model.parameters()).device)
+    return _row_store_pass(model, data_loader, ('just_feat',), dict(isEval=True, justFeat=True), kwargs, dict(desc=desc),
+                           lambda feats, rows: pool_descriptor(feats, out=desc[rows], channels=Cc))['desc']
+
+
+def _pick_scores(picks, N):
+    """the picks of a selection in the form update_X_L takes, a CPU [N] fp32 vector: pick t = 0 .. budget - 1 scores budget - t, every
+    other image 0"""
+    budget = picks.numel()
+    scores = torch.zeros(N, dtype=torch.float32, device=picks.device)
+    scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=picks.device)
+    return scores.cpu()
 
 
 def Coreset_uncertainty(cfg, model, data_loader, X_L=None, budget=None, **kwargs):
@@ -501,10 +528,7 @@ def Coreset_uncertainty(cfg, model, data_loader, X_L=None, budget=None, **kwargs
         raise TypeError('Coreset_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are the initial centers')
     budget = int(cfg.X_S_size if budget is None else budget)
     desc = single_gpu_descriptors(model, data_loader, **kwargs)
-    picks, _ = kcenter_greedy(desc, X_L, budget)
-    scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
-    scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
-    return scores.cpu()
+    return _pick_scores(kcenter_greedy(desc, X_L, budget)[0], desc.shape[0])
 
 
 @torch.no_grad()
@@ -527,18 +551,9 @@ def single_gpu_cdal_descriptors(model, data_loader, score_thr=0.3, **kwargs):
     if n_cls > CDAL_MAX_CLASSES:
         raise ValueError(f'single_gpu_cdal_descriptors: up to {CDAL_MAX_CLASSES} classes are supported (2 * C^2 <= 2048 descriptor columns), '
                          f'the head has {n_cls}')
-    model.eval()
-    dev = next(model.parameters()).device
-    pool = _PoolPass(data_loader, dev)
-    desc = torch.zeros(pool.N, 2 * n_cls * n_cls, dtype=torch.float32, device=dev)
-    gscore = _graphed(model, dev, ('just_out', 0), kwargs, isEval=True, justOut=True)
-    for idxs, image_ids, data in pool.batches():
-        maps = _replay_or_eager(gscore, data, image_ids,
-                                lambda: model(return_loss=False, rescale=True, isEval=True, justOut=True, **data, **kwargs))
-        cdal_descriptor(maps, n_cls, score_thr, out=desc[idxs[0]:idxs[0] + len(idxs)])          # (a batch is a run of consecutive images)
-    owned = torch.zeros(pool.N, dtype=torch.bool, device=dev)
-    owned[pool.all_ids] = True
-    return gather_rows(desc, owned)[0]
+    desc = torch.zeros(len(data_loader.dataset), 2 * n_cls * n_cls, dtype=torch.float32, device=next(model.parameters()).device)
+    return _row_store_pass(model, data_loader, ('just_out', 0), dict(isEval=True, justOut=True), kwargs, dict(desc=desc),
+                           lambda maps, rows: cdal_descriptor(maps, n_cls, score_thr, out=desc[rows]))['desc']
 
 
 def CDAL_uncertainty(cfg, model, data_loader, X_L=None, budget=None, score_thr=0.3, **kwargs):
@@ -553,10 +568,7 @@ def CDAL_uncertainty(cfg, model, data_loader, X_L=None, budget=None, score_thr=0
         raise TypeError('CDAL_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are the initial centers')
     budget = int(cfg.X_S_size if budget is None else budget)
     desc = single_gpu_cdal_descriptors(model, data_loader, score_thr=score_thr, **kwargs)
-    picks, _ = kcenter_greedy(desc, X_L, budget, metric='symkl')
-    scores = torch.zeros(desc.shape[0], dtype=torch.float32, device=desc.device)
-    scores[picks] = torch.arange(budget, 0, -1, dtype=torch.float32, device=desc.device)
-    return scores.cpu()
+    return _pick_scores(kcenter_greedy(desc, X_L, budget, metric='symkl')[0], desc.shape[0])
 
 
 @torch.no_grad()
@@ -583,31 +595,18 @@ def single_gpu_object_descriptors(model, data_loader, max_obj=32, score_thr=0.3,
         raise ValueError(f'single_gpu_object_descriptors: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
     if score_thr != score_thr:
         raise ValueError('single_gpu_object_descriptors: score_thr is NaN')
-    module = getattr(model, 'module', model)
-    neck = getattr(module, 'neck', None)
-    if not (hasattr(neck, 'num_outs') and isinstance(getattr(neck, 'out_channels', None), int)):
-        raise NotImplementedError(f'single_gpu_object_descriptors: CCMS object descriptors are built for the FPN pyramid of the RetinaNet '
-                                  f'detectors, not for {type(module).__name__} / {type(neck).__name__} (SSD: its source maps do not share a '
-                                  'channel count)')
-    model.eval()
-    dev = next(model.parameters()).device
-    pool = _PoolPass(data_loader, dev)
-    N, Cc = pool.N, int(neck.out_channels)
+    neck = _fpn_neck(model, 'single_gpu_object_descriptors: CCMS object descriptors')
+    N, Cc, dev = len(data_loader.dataset), int(neck.out_channels), next(model.parameters()).device
     store = dict(unc=torch.zeros(N, dtype=torch.float32, device=dev), feat=torch.zeros(N, max_obj, Cc, dtype=torch.float32, device=dev),
                  cls=torch.full((N, max_obj), -1, dtype=torch.int32, device=dev), w=torch.zeros(N, max_obj, dtype=torch.float32, device=dev),
                  cnt=torch.zeros(N, dtype=torch.int32, device=dev), missing=torch.zeros(N, dtype=torch.int32, device=dev))
     kwargs.setdefault('isUnc', False)
     fkw = dict(kwargs, objDesc=max_obj, score_thr=score_thr, unc_measure=measure, unc_aggregate=aggregate)
-    gscore = _graphed(model, dev, ('obj_desc',), fkw, isEval=True, _padded=True)
-    names = ('unc', 'feat', 'cls', 'w', 'cnt', 'missing')
-    for idxs, image_ids, data in pool.batches():
-        out = _replay_or_eager(gscore, data, image_ids,
-                               lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **data, **fkw))
-        for name, t in zip(names, out[3:]):                 # (a batch is a run of consecutive images)
-            store[name][idxs[0]:idxs[0] + len(idxs)].copy_(t)
-    owned = torch.zeros(N, dtype=torch.bool, device=dev)
-    owned[pool.all_ids] = True
-    return {name: gather_rows(t, owned)[0] for name, t in store.items()}
+
+    def write(out, rows):
+        for dst, t in zip(store.values(), out[3:]):
+            dst[rows].copy_(t)
+    return _row_store_pass(model, data_loader, ('obj_desc',), dict(isEval=True, _padded=True), fkw, store, write)
 
 
 def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_factor=4, max_obj=32, score_thr=0.3, measure='entropy',
@@ -627,13 +626,9 @@ def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_f
     budget = int(cfg.X_S_size if budget is None else budget)
     pool = single_gpu_object_descriptors(model, data_loader, max_obj=max_obj, score_thr=score_thr, measure=measure, aggregate=aggregate, **kwargs)
     cand = ccms_candidates(pool['unc'], X_L, budget, candidate_factor)
-    dev = pool['unc'].device
-    ci = torch.from_numpy(cand).to(dev)
+    ci = torch.from_numpy(cand).to(pool['unc'].device)
     dist = ccms_distance(pool['feat'][ci].contiguous(), pool['cls'][ci].contiguous(), pool['w'][ci].contiguous(), pool['cnt'][ci].contiguous())
-    picks, _ = kcenter_greedy_matrix(dist, [], budget)
-    scores = torch.zeros(pool['unc'].shape[0], dtype=torch.float32, device=dev)
-    scores[ci[picks]] = torch.arange(budget, 0, -1, dtype=torch.float32, device=dev)
-    return scores.cpu()
+    return _pick_scores(ci[kcenter_greedy_matrix(dist, [], budget)[0]], pool['unc'].shape[0])
 
 
 def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, **kwargs):

@@ -384,33 +384,44 @@ def kcenter_greedy(desc, labelled, budget, metric='sqeuclid'):
         raise ValueError(f'kcenter_greedy: up to 2048 descriptor columns are supported, got {D}')
     if metric == 'symkl' and D % 2:
         raise ValueError(f"kcenter_greedy: metric 'symkl' reads a row as two halves [P | ln P]; D = {D} is odd")
-    lab = labelled.detach().cpu().numpy() if torch.is_tensor(labelled) else np.asarray(labelled)
+    if metric == 'sqeuclid':
+        return _kcenter_run('kcenter_greedy', 'aod_kcenter_greedy', desc, (N, D), labelled, budget)
+    return _kcenter_run('kcenter_greedy', 'aod_kcenter_greedy_ex', desc, (N, D), labelled, budget, KCENTER_METRICS[metric])
+
+
+def _index_array(name, idx, N, arg='labelled', distinct=True):
+    """`idx` (tensor, array or sequence of row indices) as a validated int64 array; the messages carry the caller's `name`"""
+    lab = idx.detach().cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
     lab = lab.reshape(-1)
     if lab.size and not np.issubdtype(lab.dtype, np.integer):
-        raise ValueError(f'kcenter_greedy: labelled must hold integer indices, got {lab.dtype}')
+        raise ValueError(f'{name}: {arg} must hold integer indices, got {lab.dtype}')
     lab = lab.astype(np.int64)
     if lab.size and (lab.min() < 0 or lab.max() >= N):
-        raise ValueError(f'kcenter_greedy: labelled index outside [0, {N})')
-    if np.unique(lab).size != lab.size:
-        raise ValueError('kcenter_greedy: labelled holds a duplicated index')
+        raise ValueError(f'{name}: labelled index outside [0, {N})')
+    if distinct and np.unique(lab).size != lab.size:
+        raise ValueError(f'{name}: labelled holds a duplicated index')
+    return lab
+
+
+def _kcenter_run(name, entry, x, dims, labelled, budget, *tail):
+    """what kcenter_greedy and kcenter_greedy_matrix share once `x` (desc or dist; dims = the entry's size arguments, N first) is checked:
+    the labelled and budget checks, the CPU refusal, the outputs and the workspace, the call of `entry` and the return"""
+    N = dims[0]
+    lab = _index_array(name, labelled, N)
     budget = int(budget)
     if budget < 1:
-        raise ValueError(f'kcenter_greedy: budget must be at least 1, got {budget}')
+        raise ValueError(f'{name}: budget must be at least 1, got {budget}')
     if budget > N - lab.size:
-        raise ValueError(f'kcenter_greedy: budget {budget} exceeds the {N - lab.size} unselected rows')
-    if not desc.is_cuda:
-        raise _C.AodHipError('kcenter_greedy needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
-    dev = desc.device
+        raise ValueError(f'{name}: budget {budget} exceeds the {N - lab.size} unselected rows')
+    if not x.is_cuda:
+        raise _cpu_refusal(name)
+    dev = x.device
     lab_d = torch.from_numpy(lab).to(dev) if lab.size else None
     picks = torch.empty(budget, dtype=torch.int64, device=dev)
     radius = torch.empty(budget, dtype=torch.float32, device=dev)
     mind = torch.empty(N, dtype=torch.float32, device=dev)
     ws = torch.empty(int(_C.lib.aod_kcenter_ws_len(N)), dtype=torch.uint8, device=dev)
-    if metric == 'sqeuclid':
-        call('aod_kcenter_greedy', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
-    else:
-        call('aod_kcenter_greedy_ex', ptr(desc), N, D, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream(),
-             KCENTER_METRICS[metric])
+    call(entry, ptr(x), *dims, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream(), *tail)
     return picks, radius
 
 
@@ -682,31 +693,7 @@ def kcenter_greedy_matrix(dist, labelled, budget):
             and dist.shape[0] == dist.shape[1]):
         raise ValueError('kcenter_greedy_matrix: dist must be a non-empty contiguous square 2-D fp32 tensor'
                          + (f', got shape {tuple(dist.shape)}' if torch.is_tensor(dist) else ''))
-    N = int(dist.shape[0])
-    lab = labelled.detach().cpu().numpy() if torch.is_tensor(labelled) else np.asarray(labelled)
-    lab = lab.reshape(-1)
-    if lab.size and not np.issubdtype(lab.dtype, np.integer):
-        raise ValueError(f'kcenter_greedy_matrix: labelled must hold integer indices, got {lab.dtype}')
-    lab = lab.astype(np.int64)
-    if lab.size and (lab.min() < 0 or lab.max() >= N):
-        raise ValueError(f'kcenter_greedy_matrix: labelled index outside [0, {N})')
-    if np.unique(lab).size != lab.size:
-        raise ValueError('kcenter_greedy_matrix: labelled holds a duplicated index')
-    budget = int(budget)
-    if budget < 1:
-        raise ValueError(f'kcenter_greedy_matrix: budget must be at least 1, got {budget}')
-    if budget > N - lab.size:
-        raise ValueError(f'kcenter_greedy_matrix: budget {budget} exceeds the {N - lab.size} unselected rows')
-    if not dist.is_cuda:
-        raise _cpu_refusal('kcenter_greedy_matrix')
-    dev = dist.device
-    lab_d = torch.from_numpy(lab).to(dev) if lab.size else None
-    picks = torch.empty(budget, dtype=torch.int64, device=dev)
-    radius = torch.empty(budget, dtype=torch.float32, device=dev)
-    mind = torch.empty(N, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(_C.lib.aod_kcenter_ws_len(N)), dtype=torch.uint8, device=dev)
-    call('aod_kcenter_greedy_matrix', ptr(dist), N, ptr(lab_d), int(lab.size), budget, ptr(picks), ptr(radius), ptr(mind), ptr(ws), stream())
-    return picks, radius
+    return _kcenter_run('kcenter_greedy_matrix', 'aod_kcenter_greedy_matrix', dist, (int(dist.shape[0]),), labelled, budget)
 
 
 def ccms_candidates(unc, X_L, budget, factor=4):
@@ -716,13 +703,7 @@ def ccms_candidates(unc, X_L, budget, factor=4):
     u = unc.detach().cpu().numpy() if torch.is_tensor(unc) else np.asarray(unc)
     u = u.reshape(-1).astype(np.float64)
     N = u.size
-    lab = X_L.detach().cpu().numpy() if torch.is_tensor(X_L) else np.asarray(X_L)
-    lab = lab.reshape(-1)
-    if lab.size and not np.issubdtype(lab.dtype, np.integer):
-        raise ValueError(f'ccms_candidates: X_L must hold integer indices, got {lab.dtype}')
-    lab = lab.astype(np.int64)
-    if lab.size and (lab.min() < 0 or lab.max() >= N):
-        raise ValueError(f'ccms_candidates: labelled index outside [0, {N})')
+    lab = _index_array('ccms_candidates', X_L, N, arg='X_L', distinct=False)
     budget, factor = int(budget), float(factor)
     if budget < 1:
         raise ValueError(f'ccms_candidates: budget must be at least 1, got {budget}')

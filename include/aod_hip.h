@@ -713,8 +713,8 @@ int aod_dropout2d_apply_multi(void* x, const float* table, int64_t row_stride_T,
                               const int32_t* seg_hw, const int32_t* seg_off, int C, int x3, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ Core-set acquisition: pooled pyramid descriptors and k-center greedy
- * (csrc/coreset.hip).  No reference call site: O. Sener, S. Savarese, "Active Learning for Convolutional Neural Networks: A Core-Set
- * Approach", ICLR 2018, Algorithm 1 (k-Center-Greedy); the semantics are fixed in DESIGN 3i.
+ * (csrc/coreset.hip: the descriptor; csrc/kcenter.hip: the selection).  No reference call site: O. Sener, S. Savarese, "Active Learning
+ * for Convolutional Neural Networks: A Core-Set Approach", ICLR 2018, Algorithm 1 (k-Center-Greedy); the semantics are fixed in DESIGN 3i.
  *   aod_pool_descriptor: the descriptor of image b = concatenation over the nseg pyramid levels of the global average of the neck output:
  *     out[b * out_stride + s * C + c] = mean over the seg_hw[s] rows of image b in segment s of channel c, fp32.  Segment s = rows
  *     seg_row0[s] .. + B * seg_hw[s] of the row buffer `base` (1..8 segments, HOST arrays).  x3 = 0: bf16 rows of C columns; x3 = 1:
@@ -739,7 +739,7 @@ int aod_kcenter_greedy(const float* desc, int64_t N, int D, const int64_t* label
                        float* radius, float* mind, void* ws, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ CDAL acquisition: class-mixture descriptors and the symmetrised-KL
- * k-center metric (csrc/cdal.hip, csrc/coreset.hip).  No reference call site: S. Agarwal, H. Arora, S. Anand, C. Arora, "Contextual
+ * k-center metric (csrc/cdal.hip, csrc/kcenter.hip).  No reference call site: S. Agarwal, H. Arora, S. Anand, C. Arora, "Contextual
  * Diversity for Active Learning", ECCV 2020, in its core-set form (CDAL-CS); the semantics are fixed in DESIGN 3j.
  *   aod_cdal_descriptor: maps = L HOST-array device pointers (1..8 levels; they travel as kernel arguments), level l = fp32 [B][rows_l][C]
  *     logits, the C classes of an anchor row contiguous (rows_per_level: HOST array), 1 <= C <= 32 (2 C^2 <= 2048 descriptor columns).
@@ -817,7 +817,7 @@ int aod_pixel_noise(const float* src, float* dst, int B, int C, int Hp, int Wp, 
 int aod_loc_stability(const float* dets, const int64_t* labels, const int32_t* num, int K, int B, int max_num, float score_thr, int same_class,
                       int combine, float* unc, float* stab_out, aod_stream_t stream);
 
-/* ------------------------------------------------------------------ CCMS acquisition (csrc/ccms.hip, csrc/coreset.hip, csrc/det_unc.hip):
+/* ------------------------------------------------------------------ CCMS acquisition (csrc/ccms.hip, csrc/kcenter.hip, csrc/det_unc.hip):
  * pre-select the most uncertain images, then spread the picks by k-center greedy under a distance that matches objects of the same class
  * between two images (PPAL: Yang, Huang, Crowley, "Plug and Play Active Learning for Object Detection", CVPR 2024; its class-difficulty
  * EMA is not built).  No reference call site; the semantics are fixed in DESIGN 3o.

@@ -3,6 +3,8 @@ image, the directed category-conditioned matching similarity and the distance bu
 distance matrix with the lowest-index tie-break."""
 import numpy as np
 
+from tests.coreset_util import greedy
+
 
 def object_descriptors_float64(levels, num_anchors, cand_anchor, dets, labels, num, obj_cand, max_obj, score_thr):
     """levels: per-level float64 values [B, h * w, C] of the neck outputs; num_anchors: anchors per cell of every level; cand_anchor [B, n],
@@ -75,20 +77,4 @@ def greedy_matrix(D, labelled, budget):
     as the radius, selects the row and lowers every mind to D[pick].  Returns (picks [budget] int64, radius [budget], ties) with ties = the
     number of steps at which more than one unselected row held the maximum."""
     D = np.asarray(D)
-    N = D.shape[0]
-    mind = np.full(N, np.inf, D.dtype)
-    sel = np.zeros(N, bool)
-    for c in labelled:
-        mind = np.minimum(mind, D[int(c)])
-        sel[int(c)] = True
-    picks, radius, ties = [], [], 0
-    for _ in range(budget):
-        cand = np.where(sel, -np.inf, mind)
-        p = int(np.argmax(cand))
-        assert not sel[p], 'budget exceeds the unselected rows'
-        ties += int((cand == cand[p]).sum() > 1)
-        picks.append(p)
-        radius.append(mind[p])
-        sel[p] = True
-        mind = np.minimum(mind, D[p])
-    return np.array(picks, np.int64), np.array(radius, D.dtype), ties
+    return greedy(D, labelled, budget, dtype=D.dtype, dist=lambda D, c: D[c])

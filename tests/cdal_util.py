@@ -75,25 +75,9 @@ def symkl(X, c):
     return (np.maximum((X[:, :H] - X[c, :H]) * (X[:, H:] - X[c, H:]), 0) * X.dtype.type(0.5)).sum(axis=1)
 
 
-class _with_distance:
-    """coreset_util's greedy / replay_ratios look their distance up as the module global sqdist: swapped for the call"""
-
-    def __init__(self, dist):
-        self.dist = dist
-
-    def __enter__(self):
-        self.prev, coreset_util.sqdist = coreset_util.sqdist, self.dist
-
-    def __exit__(self, *exc):
-        coreset_util.sqdist = self.prev
-        return False
-
-
 def greedy(X, labelled, budget, dist=symkl, dtype=np.float64):
-    with _with_distance(dist):
-        return coreset_util.greedy(X, labelled, budget, dtype)
+    return coreset_util.greedy(X, labelled, budget, dtype, dist)
 
 
 def replay_ratios(X, labelled, picks, dist=symkl, return_radius=False):
-    with _with_distance(dist):
-        return coreset_util.replay_ratios(X, labelled, picks, return_radius=return_radius)
+    return coreset_util.replay_ratios(X, labelled, picks, return_radius=return_radius, dist=dist)

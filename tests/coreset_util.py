@@ -1,5 +1,6 @@
 """Float64 numpy restatements of the Core-set acquisition the tests compare the kernels against: the pooled pyramid
-descriptor, the exact k-center greedy with the lowest-index tie-break, and a replay checker for inexact (float) descriptors."""
+descriptor, the exact k-center greedy with the lowest-index tie-break, and a replay checker for inexact (float) descriptors.  The greedy
+and the checker take the distance as an argument: tests/cdal_util.py (symmetrised KL) and tests/ccms_util.py (a matrix row) call them."""
 import numpy as np
 
 
@@ -14,17 +15,18 @@ def sqdist(X, c):
     return (diff * diff).sum(axis=1)
 
 
-def greedy(X, labelled, budget, dtype=np.float64):
-    """k-center greedy (Sener & Savarese, Algorithm 1): mind = min over labelled centers (+inf without one), labelled rows selected; each
-    step picks the unselected row with the largest mind -- np.argmax returns the LOWEST index of a tie --, records that mind as the radius,
-    selects the row and lowers every mind to the distance to it.  Returns (picks [budget] int64, radius [budget] dtype, ties) with ties =
-    the number of steps at which more than one unselected row held the maximum."""
+def greedy(X, labelled, budget, dtype=np.float64, dist=sqdist):
+    """k-center greedy (Sener & Savarese, Algorithm 1) under the distance dist(X, c) -> [N] (X already in `dtype`): mind = min over
+    labelled centers (+inf without one), labelled rows selected; each step picks the unselected row with the largest mind -- np.argmax
+    returns the LOWEST index of a tie --, records that mind as the radius, selects the row and lowers every mind to the distance to it.
+    Returns (picks [budget] int64, radius [budget] dtype, ties) with ties = the number of steps at which more than one unselected row
+    held the maximum."""
     X = np.asarray(X, dtype)
     N = X.shape[0]
     mind = np.full(N, np.inf, dtype)
     sel = np.zeros(N, bool)
     for c in labelled:
-        mind = np.minimum(mind, sqdist(X, int(c)))
+        mind = np.minimum(mind, dist(X, int(c)))
         sel[int(c)] = True
     picks, radius, ties = [], [], 0
     for _ in range(budget):
@@ -35,20 +37,20 @@ def greedy(X, labelled, budget, dtype=np.float64):
         picks.append(p)
         radius.append(mind[p])
         sel[p] = True
-        mind = np.minimum(mind, sqdist(X, p))
+        mind = np.minimum(mind, dist(X, p))
     return np.array(picks, np.int64), np.array(radius, dtype), ties
 
 
-def replay_ratios(X, labelled, picks, return_radius=False):
-    """Given a device's own pick sequence: mind recomputed in float64 along it; per step mind64[pick] / max over unselected of mind64
-    (1.0 where the device took the exact float64 maximum, or where that maximum is 0 or inf and the pick holds it too).  A pick that was
+def replay_ratios(X, labelled, picks, return_radius=False, dist=sqdist):
+    """Given a device's own pick sequence: mind recomputed in float64 (under dist(X, c)) along it; per step mind64[pick] / max over
+    unselected of mind64 (1.0 where the device took the exact float64 maximum, or where that maximum is 0 or inf and the pick holds it too).  A pick that was
     already selected gives -1.  return_radius: also mind64[pick] per step."""
     X = np.asarray(X, np.float64)
     N = X.shape[0]
     mind = np.full(N, np.inf)
     sel = np.zeros(N, bool)
     for c in labelled:
-        mind = np.minimum(mind, sqdist(X, int(c)))
+        mind = np.minimum(mind, dist(X, int(c)))
         sel[int(c)] = True
     out, rad = [], []
     for p in picks:
@@ -60,7 +62,7 @@ def replay_ratios(X, labelled, picks, return_radius=False):
         best = np.where(sel, -np.inf, mind).max()
         out.append(1.0 if mind[p] == best else float(mind[p] / best))
         sel[p] = True
-        mind = np.minimum(mind, sqdist(X, p))
+        mind = np.minimum(mind, dist(X, p))
     return (np.array(out), np.array(rad)) if return_radius else np.array(out)
 
 

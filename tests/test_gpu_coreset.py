@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.coreset_util import descriptor_float64, greedy, pad_mask, replay_ratios, x_layout_rows
+from tests.coreset_util import descriptor_float64, greedy, pad_mask, replay_ratios, sqdist, x_layout_rows
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,6 +39,10 @@ EXACT = {
     'no_labelled_many_blocks': (1500, 96, 0, 64, -2, 3),
     'one_column': (70, 1, 2, 20, -8, 9),                  # D = 1: the scalar path (D % 4 != 0), ties everywhere
     'chunk_plus_one': (120, 24, 'chunk+1', 16, -2, 3),    # one full initialisation launch and one with a single center
+    # more rows than one trip of any grid covers: the wave-stride loop of the rows sweep (N > 4 * 1024) and the capped element grids of
+    # prepare and keys (N > 256 * 1024).  Row N - 7 (all 7) is the farthest row and lies past every grid's first trip; row N - 9
+    # (7, 7, 7, 6) is the next farthest until its mind is lowered against that pick
+    'beyond_every_grid': (256 * 1024 + 300, 4, 2, 6, -2, 3),
 }
 
 
@@ -49,6 +53,8 @@ def test_greedy_is_exact_on_integer_descriptors(name):
     N, D, n_lab, budget, lo, hi = EXACT[name]
     n_lab = _chunk() + 1 if n_lab == 'chunk+1' else n_lab
     X = _integer_case(N, D, lo, hi)
+    if name == 'beyond_every_grid':
+        X[N - 7], X[N - 9] = 7, (7, 7, 7, 6)
     lab = list(range(N - n_lab, N))
     picks, radius, ties = greedy(X, lab, budget)
     p32, r32, _ = greedy(X, lab, budget, np.float32)
@@ -63,6 +69,13 @@ def test_greedy_is_exact_on_integer_descriptors(name):
         assert got_p[0].item() == 0 and np.isinf(got_r[0].item())
     if name == 'budget_is_everything':
         assert sorted(got_p.tolist() + lab) == list(range(N))
+    if name == 'beyond_every_grid':
+        assert got_p[0].item() == N - 7 and N - 9 not in got_p.tolist()
+    if N <= 1500:
+        # the matrix path on the same (exact integer) distances: the same picks, and radii with the same bits
+        matrix = np.stack([sqdist(X, c) for c in range(N)]).astype(np.float32)
+        mat_p, mat_r = scoring.kcenter_greedy_matrix(torch.from_numpy(matrix).cuda(), lab, budget)
+        assert torch.equal(mat_p, got_p) and torch.equal(mat_r.view(torch.int32), got_r.view(torch.int32))
 
 
 @pytest.fixture(scope='module')
