@@ -71,6 +71,10 @@ _SIGS = {
     'aod_conv2d_plan': (C.c_int, [C.POINTER(ConvDesc), I32, C.c_uint, C.POINTER(ConvPlan)]),
     'aod_conv2d_grouped': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P]),
     'aod_conv2d_ws_map': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P, SZ, P, P, P]),
+    'aod_conv2d_ws_map_order': (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P, P, SZ, P, P, P, P]),
+    'aod_conv2d_x3p_item_order': (C.c_int, [I32, I32, I32, P, P, P, P]),
+    'aod_conv2d_x3p_mapped_grid': (C.c_int, [I32, I32, I32]),
+    'aod_conv_x3p_mapped_count': (C.c_int64, []),
     'aod_conv2d_grouped_map': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P, P, P, P]),
     'aod_fwd_row_maps': (C.c_int, [C.POINTER(ConvDesc), P, I32, I32, P, P]),
     'aod_conv2d_grouped_fwd_map': (C.c_int, [C.POINTER(ConvDesc), I32, P, P, P, P, P, P]),

@@ -1250,7 +1250,12 @@ struct TileOrderArgs {
   unsigned char* dil_out[4];
   int* order;
   int ngroups, tiles_m, tiles_n, bm, M;
+  int items;      // 1: the ITEM list of a mapped launch of the persistent kernel (conv_x3p.h): the ranking itself, live entries first -- the deal over
+                  // the blockIdx % 8 classes is the kernel's slot rule (x3p_item_slot), not a property of the list
 };
+__host__ __device__ __forceinline__ int tile_order_place(const TileOrderArgs& a, int live, int rank, int nlive) {
+  return a.items ? (live ? rank : nlive + rank) : conv_tile_order_slot(live, rank, nlive);
+}
 __host__ __device__ __forceinline__ int tile_order_live(const TileOrderArgs& a, int e) {
   const int nwg = a.tiles_m * a.tiles_n, g = e / nwg, tile_m = (e - g * nwg) / a.tiles_n;
   const unsigned char* const m = g == 0 ? a.omap[0] : (g == 1 ? a.omap[1] : (g == 2 ? a.omap[2] : a.omap[3]));
@@ -1286,7 +1291,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const TileOrderArgs a,
     for (int w = 0; w < 16; ++w) { before += w < wave ? wcnt[w] : 0; chunk += wcnt[w]; }
     if (e < total) {
       const int rank = live ? live_before + before : (base - live_before) + (t - before);
-      a.order[conv_tile_order_slot(live, rank, nlive)] = e;
+      a.order[tile_order_place(a, live, rank, nlive)] = e;
     }
     live_before += chunk;
     __syncthreads();
@@ -1300,7 +1305,7 @@ static void tile_order_host(const TileOrderArgs& a, int* order) {
   int nl = 0, nd = 0;
   for (int e = 0; e < total; ++e) {
     const int live = tile_order_live(a, e);
-    order[conv_tile_order_slot(live, live ? nl : nd, nlive)] = e;
+    order[tile_order_place(a, live, live ? nl : nd, nlive)] = e;
     (live ? nl : nd) += 1;
   }
 }
@@ -1326,11 +1331,38 @@ static int tile_order_launch(ConvKParams& p, const MapGeo& mg, int ngroups, cons
   return 0;
 }
 
+// ---- the mapped form of the persistent kernel (conv_x3p.hip): a PLAIN 3x3 dgrad that carries a map runs 128-column tiles -- a live row tile
+// is N / 128 items of half a 256-column tile's matrix work -- in the order of an item list that the launch which dilates the map writes
+// (tile_order_kernel, TileOrderArgs.items).  With 0.15 % of the anchors positive ~100 - 150 of the 682 row tiles of the bench's pyramid are
+// live: the static walk of 256-column tiles gave a quarter of the workgroups one to three of them and the launch lasted as long as the
+// unluckiest one; the list gives every workgroup ceil(live / G) items or one fewer.  AOD_X3P_MAPPED=0: the launch stays as planned.
+static bool x3p_mapped_applies(const ConvKParams& p, const ConvPlan& pl, const void* order, int& grid) {
+  if (!order || !p.omap || pl.kind != AOD_CONV_PLAN_X3P || pl.grouped || pl.taps != 9 || pl.lat != 0 || pl.pre != 0 || p.N % 128 != 0) return false;
+  ConvKnobs kn;
+  if (kn.is(ConvKnobs::X3P_MAPPED, '0')) return false;
+  const int tiles_n = p.N / 128;
+  grid = x3p_mapped_grid((long long)((p.M + XP_BM - 1) / XP_BM) * tiles_n, tiles_n, xp_cus());
+  return grid > 0;
+}
+static int x3p_mapped_launch(ConvKParams& p, ConvPlan& pl, int grid, const MapGeo& mg, const void* dil_in, void* dil_out, int* order, hipStream_t st) {
+  TileOrderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.omap[0] = p.omap; a.dil_in[0] = (const unsigned char*)dil_in; a.dil_out[0] = (unsigned char*)dil_out;
+  a.order = order; a.ngroups = 1; a.bm = XP_BM; a.M = p.M; a.items = 1;
+  a.tiles_m = (p.M + XP_BM - 1) / XP_BM; a.tiles_n = p.N / 128;
+  AOD_CHECK_ARG(((uintptr_t)order & 3) == 0, "conv (item list): the list must be 4-byte aligned");
+  hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, st, a, mg);
+  AOD_LAUNCH_CHECK();
+  p.order = order;
+  pl.wide = 0; pl.grid = grid;
+  return 0;
+}
+
 // in_map[g] / out_map[g] of a (grouped) dgrad launch: writes every out_map from its in_map (a small launch of its own, ahead of the conv) and
 // hands the conv kernel the OUT map of each member whose zero tiles are safe to skip.  ngroups = 0: the plain launch (p.omap).
 // order (grouped launches of the 256 x 256 tile, optional): the list of the launch is built by the same small launch (tile_order_kernel).
 static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map, void* const* out_map, hipStream_t st,
-                          const ConvPlan* pl = nullptr, int* order = nullptr) {
+                          ConvPlan* pl = nullptr, int* order = nullptr) {
   const int ng = ngroups ? ngroups : 1;
   bool any = false;
   for (int g = 0; g < ng; ++g) {
@@ -1365,6 +1397,9 @@ static int conv_map_setup(ConvKParams& p, int ngroups, const void* const* in_map
   }
   // the maps themselves: one launch with the list of the conv launch behind them, or a launch per mapped member
   if (ngroups && pl && tile_order_applies(p, *pl, order)) return tile_order_launch(p, mg, ngroups, in_map, out_map, order, st);
+  // (plain launch on the persistent kernel: the same launch writes the item list, and the plan becomes the 128-column form)
+  int mgrid = 0;
+  if (!ngroups && pl && x3p_mapped_applies(p, *pl, order, mgrid)) return x3p_mapped_launch(p, *pl, mgrid, mg, in_map[0], out_map[0], order, st);
   for (int g = 0; g < ng; ++g) {
     if (!in_map[g]) continue;
     hipLaunchKernelGGL(row_map_dilate_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, (const unsigned char*)in_map[g], (unsigned char*)out_map[g], mg);
@@ -1615,10 +1650,14 @@ static void x3p_args(const ConvKParams& p, const ConvPlan& plan, X3PArgs& a) {
   // the kernel reads its operands from grp[]: the groups of a grouped launch, else the one set above
   a.ngroups = p.ngroups > 1 ? p.ngroups : 1;
   a.grp[0].x = a.x; a.grp[0].w = a.w; a.grp[0].y = a.y; a.grp[0].shift = a.pre_shift; a.grp[0].mask = a.mask; a.grp[0].colsum = a.colsum;
-  a.grp[0].omap = p.omap;
+  // maps: the 256-column 3x3 instance follows them under its static walk; the 128-column one only as the mapped form, with its item list
+  // (x3p_mapped_launch) -- a 128-column launch without a list stays dense
+  a.order = (!plan.wide && p.ngroups <= 1) ? p.order : nullptr;
+  const bool maps = plan.wide || a.order;
+  a.grp[0].omap = maps ? p.omap : nullptr;
   for (int g = 0; g < p.ngroups; ++g) {
     a.grp[g].x = p.grp[g].x; a.grp[g].w = p.grp[g].w; a.grp[g].y = reinterpret_cast<bf16_t*>(p.grp[g].y); a.grp[g].shift = p.grp[g].pre_shift;
-    a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum; a.grp[g].omap = p.grp[g].omap;
+    a.grp[g].mask = p.grp[g].mask; a.grp[g].colsum = p.grp[g].colsum; a.grp[g].omap = maps ? p.grp[g].omap : nullptr;
   }
   a.lat = plan.lat; a.up_w = p.up_w; a.up_hw = p.up_hw;
   const long long rows = a.lat == 1 ? (long long)a.segB[0] * (a.segOH[0] / 2) * (a.segOW[0] / 2) : a.M;
@@ -1689,10 +1728,12 @@ static int conv_launch(const ConvPlan& pl, ConvKParams& p, void* workspace, size
 }
 
 // aod_conv2d_ws with the row-activity maps of the sparse backward (x3 stride-1 dgrad; both null: the plain launch)
-extern "C" int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
-                                 const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
-                                 const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
-                                 const void* in_map, void* out_map, aod_stream_t stream) {
+// order (optional): int32 [ceil(rows / 128) * N / 128], device memory -- a mapped 3x3 launch of the persistent kernel then takes its
+// 128-column form and follows the item list that the map's launch writes there (x3p_mapped_launch); null, or AOD_X3P_MAPPED=0: as planned
+extern "C" int aod_conv2d_ws_map_order(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
+                                       const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
+                                       const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
+                                       const void* in_map, void* out_map, void* order, aod_stream_t stream) {
   ConvKParams p;
   ConvPlan pl;
   int rc = conv_params(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, p);
@@ -1700,9 +1741,39 @@ extern "C" int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, c
   if (p.M == 0) return 0;
   rc = conv_plan(p, 0, workspace != nullptr, pl);
   if (rc) return rc;
-  rc = conv_map_setup(p, 0, &in_map, &out_map, (hipStream_t)stream);
+  rc = conv_map_setup(p, 0, &in_map, &out_map, (hipStream_t)stream, &pl, (int*)order);
   if (rc) return rc;
   return conv_launch(pl, p, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,
+                                 const float* pre_scale, const float* pre_shift, const void* res, const void* mask,
+                                 const float* post_scale, void* zraw, float* colsum, void* workspace, size_t workspace_bytes,
+                                 const void* in_map, void* out_map, aod_stream_t stream) {
+  return aod_conv2d_ws_map_order(desc, src, w_packed, dst, pre_scale, pre_shift, res, mask, post_scale, zraw, colsum, workspace, workspace_bytes,
+                                 in_map, out_map, nullptr, stream);
+}
+
+// The item list of a mapped launch of the persistent kernel as data (host logic only; the ranking is the one tile_order_kernel runs, the deal
+// the kernel's x3p_item_slot): `rows` GEMM rows, `tiles_n` = N / 128 column tiles, a grid of `grid` workgroups (x3p_mapped_grid), map = a HOST
+// copy of the row-activity map ((rows + 63) / 64 bytes).  item[pos] = tile_m * tiles_n + tile_n of list position pos, block[pos] / round[pos] =
+// the workgroup that runs it and as which of its items, pos < ceil(rows / 128) * tiles_n.
+extern "C" int aod_conv2d_x3p_item_order(int rows, int tiles_n, int grid, const void* map, int32_t* item, int32_t* block, int32_t* round) {
+  AOD_CHECK_ARG(rows >= 1 && tiles_n >= 1 && map && item && block && round, "conv_x3p_item_order: rows %d, tiles_n %d", rows, tiles_n);
+  const int tiles_m = (rows + XP_BM - 1) / XP_BM, ntiles = tiles_m * tiles_n;
+  AOD_CHECK_ARG(grid >= 1 && grid <= ntiles && grid % (8 * tiles_n) == 0, "conv_x3p_item_order: a grid of %d for %d tiles in %d columns", grid, ntiles, tiles_n);
+  TileOrderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.omap[0] = (const unsigned char*)map;
+  a.ngroups = 1; a.bm = XP_BM; a.M = rows; a.tiles_m = tiles_m; a.tiles_n = tiles_n; a.items = 1;
+  tile_order_host(a, item);
+  for (int pos = 0; pos < ntiles; ++pos) { block[pos] = x3p_slot_block(pos % grid, tiles_n); round[pos] = pos / grid; }
+  return 0;
+}
+// ... and the grid of that launch on a device of `cus` compute units (0: too few tiles for the deal, the launch keeps its planned form)
+extern "C" int aod_conv2d_x3p_mapped_grid(int rows, int tiles_n, int cus) {
+  AOD_CHECK_ARG(rows >= 1 && tiles_n >= 1 && cus >= 1, "conv_x3p_mapped_grid: rows %d, tiles_n %d, cus %d", rows, tiles_n, cus);
+  return x3p_mapped_grid((long long)((rows + XP_BM - 1) / XP_BM) * tiles_n, tiles_n, cus);
 }
 
 extern "C" int aod_conv2d_ws(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst,

@@ -29,6 +29,7 @@ struct ConvKParams {
   const int* order;   // mapped grouped launch of the 256 x 256 tile, optional: block b runs entry order[b] = member * tiles + tile, a permutation that
                       // tile_order_kernel (conv.hip) writes from the maps ahead of the launch -- live tiles first, dealt evenly over the blockIdx % 8
                       // classes.  nullptr: conv_grouped_deal (AOD_TILE_ORDER=0, or a caller without a list)
+                      // Plain mapped 3x3 dgrad on the persistent kernel: the ITEM list of its 128-column form (conv_x3p.h, X3PArgs.order)
   const unsigned char* omap;   // X3 stride-1 dgrad, optional (sparse backward, conv_map_setup): ROW-ACTIVITY MAP of the DESTINATION -- byte b = 0: no
                       // row of 64 b .. 64 b + 63 can receive anything but zeros (every dZ row the filter taps reach from there is zero); a tile whose
                       // blocks are all 0 stores zero rows and leaves.  nullptr: every tile is computed.  Grouped launches: grp[].omap
@@ -119,13 +120,13 @@ struct ConvKnobs {
   static const Once& once() { static const Once k{}; return k; }
 
   enum Call { X3P_OVER_256, X3_TILE_192, X3P_GROUPED, X3P, X3P_PRE, X3P_BN, X3P_DGRAD, X3P_LATTICE, X3P_MIN_STEPS, X3P_PRE_MIN_STEPS, X3P_MIN_TILES,
-              X3P_ROT, SPARSE_BWD, SPARSE_FWD, TILE_ORDER, NCALL };
+              X3P_ROT, SPARSE_BWD, SPARSE_FWD, TILE_ORDER, X3P_MAPPED, NCALL };
   const char* val[NCALL];
   unsigned seen = 0;
   const char* call(Call k) {
     static const char* const names[NCALL] = {"AOD_X3P_OVER_256", "AOD_X3_TILE_192", "AOD_X3P_GROUPED", "AOD_X3P", "AOD_X3P_PRE", "AOD_X3P_BN",
                                              "AOD_X3P_DGRAD", "AOD_X3P_LATTICE", "AOD_X3P_MIN_STEPS", "AOD_X3P_PRE_MIN_STEPS", "AOD_X3P_MIN_TILES",
-                                             "AOD_X3P_ROT", "AOD_SPARSE_BWD", "AOD_SPARSE_FWD", "AOD_TILE_ORDER"};
+                                             "AOD_X3P_ROT", "AOD_SPARSE_BWD", "AOD_SPARSE_FWD", "AOD_TILE_ORDER", "AOD_X3P_MAPPED"};
     if (!((seen >> k) & 1u)) { val[k] = getenv(names[k]); seen |= 1u << k; }
     return val[k];
   }

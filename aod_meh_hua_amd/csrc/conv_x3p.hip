@@ -86,9 +86,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int tpg = tpc * (LAT == 1 ? 4 : 1);                    // tiles per group
   const int ntiles = tpg * p.ngroups;
   const int G = (int)gridDim.x, bid = (int)blockIdx.x;
-  const int nmine = (ntiles - bid + G - 1) / G;              // tiles bid, bid + G, ... (launcher: G <= ntiles)
+  // SPARSE (the head towers' 3x3 dgrad, sparse backward): with a row-activity map of the destination (grp[].omap) a tile whose two 64-row blocks
+  // are 0 is DEAD -- the loaders issue no stage for it, the consumers run no K-step and store zero rows.  Both sides take the decision from the
+  // same two map bytes (written by an earlier launch), so the ring, which does not know about tiles, stays in step.
+  // The 128-column instance is the MAPPED form (launcher: one group, a map, an item list p.order -- conv_x3p.h): a live row tile is tiles_n
+  // items of half the matrix work of a 256-column tile, and the list, not the static walk, says which workgroup runs which.
+  constexpr bool SPARSE = TAPS == 9 && LAT == 0 && PRE == 0;
+  const int* const ord = (SPARSE && NBW == 4) ? p.order : nullptr;
+  const int slot0 = ord ? x3p_item_slot(bid, p.tiles_n) : bid;
+  const int nmine = (ntiles - slot0 + G - 1) / G;            // tiles slot0, slot0 + G, ... (launcher: G <= ntiles)
   const int CC = p.C >> 6;                                    // 64-column (= 32-channel) chunks per tap
   auto tile_of = [&](int j) {
+    if constexpr (SPARSE && NBW == 4) {
+      if (ord) {
+        // (clamped, like the grouped kernel's entry: a list the builder has not written must not send a workgroup outside the tensors)
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane(ord[j * G + slot0]), last = (unsigned)(ntiles - 1);
+        return (int)(e < last ? e : last);
+      }
+    }
     const int base = j * G, left = ntiles - base;
     return base + xp_swizzle(bid, left < G ? left : G);
   };
@@ -98,10 +113,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int cls = (tile % tpg) / tpc;
     return ((cls >> 1) ? 2 : 1) * ((cls & 1) ? 2 : 1);
   };
-  // SPARSE (the head towers' 3x3 / 256-column dgrad, sparse backward): with a row-activity map of the destination (grp[].omap) a tile whose two
-  // 64-row blocks are 0 is DEAD -- the loaders issue no stage for it, the consumers run no K-step and store zero rows.  Both sides take the
-  // decision from the same two map bytes (written by an earlier launch), so the ring, which does not know about tiles, stays in step.
-  constexpr bool SPARSE = TAPS == 9 && NBW == 8 && LAT == 0 && PRE == 0;
   auto tile_live = [&](int tile) {
     if constexpr (!SPARSE) return true;
     else {
@@ -480,7 +491,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 #undef XP_GSEL
 
-long long g_x3p_count = 0;
+long long g_x3p_count = 0, g_x3p_mapped_count = 0;
 
 template <int TAPS, int NBW, int LAT, int PRE>
 int xp_launch(const X3PArgs& a, int grid, hipStream_t st) {
@@ -505,6 +516,7 @@ int aod_conv_x3p_launch(const X3PArgs& a, const ConvPlan& plan, hipStream_t st) 
     xp_launch<TAPS, NBW, LAT, PRE>(a, plan.grid, st);                                   \
     AOD_LAUNCH_CHECK();                                                                 \
     __atomic_add_fetch(&g_x3p_count, 1, __ATOMIC_RELAXED);                              \
+    if (a.order) __atomic_add_fetch(&g_x3p_mapped_count, 1, __ATOMIC_RELAXED);          \
     return 0;                                                                           \
   }
   X3P_INSTANCES(X)
@@ -513,4 +525,5 @@ int aod_conv_x3p_launch(const X3PArgs& a, const ConvPlan& plan, hipStream_t st) 
   return -1;
 }
 
+extern "C" int64_t aod_conv_x3p_mapped_count(void) { return (int64_t)__atomic_load_n(&g_x3p_mapped_count, __ATOMIC_RELAXED); }
 extern "C" int64_t aod_conv_x3p_count(void) { return (int64_t)__atomic_load_n(&g_x3p_count, __ATOMIC_RELAXED); }

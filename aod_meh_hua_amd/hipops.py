@@ -341,11 +341,21 @@ def conv2d_dgrad_rows_grouped(dzs, dz_segs, x_segs, wds, Cin, R, S, stride=1, pa
 
 
 
+X3P_MAP_LOG = None   # tests: a list that receives (dX rows shape, whether the launch took the persistent kernel's mapped 128-column form) of every mapped dgrad
+
+
+def x3p_item_list(rows, Cin, device):
+    """the (unwritten) item list of a mapped dgrad on the persistent kernel: one int32 per 128-row x 128-column tile, written on the device
+    by the launch that writes the map of dX (aod_conv2d_ws_map_order; AOD_X3P_MAPPED=0, or a launch on another kernel: left unwritten)"""
+    return torch.empty(((rows + 127) // 128) * max(Cin // 128, 1), dtype=torch.int32, device=device)
+
+
 def conv2d_dgrad_rows(dz_rows, dz_segs, x_segs, w_dgrad, Cin, R, S, stride=1, pad=0, dil=1, *, res=None, mask=None,
-                      post_scale=None, out=None, x_rows_total=None, colsum=None, alg=None, out_f32=False, in_map=None):
+                      post_scale=None, out=None, x_rows_total=None, colsum=None, alg=None, out_f32=False, in_map=None, order=None):
     """dX = conv_transpose(dZ, W).  dz_rows [rows_out, Npad]; w_dgrad [Cin][R][S][Npad].
     res / mask / colsum: fused activation backward of the producer of x (see aod_conv2d).
-    in_map: row-activity map of dZ (pad_cast_colsum / an earlier dgrad) -- then returns (dX, the map of dX or None when maps do not apply)."""
+    in_map: row-activity map of dZ (pad_cast_colsum / an earlier dgrad) -- then returns (dX, the map of dX or None when maps do not apply).
+    order: a caller's x3p_item_list for the mapped launch, else a fresh one."""
     Npad = dz_rows.shape[1]
     rows = x_rows_total if x_rows_total is not None else sum(s.rows for s in x_segs)
     if out is None:
@@ -360,9 +370,14 @@ def conv2d_dgrad_rows(dz_rows, dz_segs, x_segs, w_dgrad, Cin, R, S, stride=1, pa
         if x_rows_total is None and _maps_apply(dz_segs, x_segs, stride, out_f32):
             assert in_map.dtype == torch.uint8 and in_map.numel() == (rows + 63) // 64
             out_map = row_map(rows, out.device)
-        _prof('dgrad', d, lambda: call('aod_conv2d_ws_map', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, None, ptr(res), ptr(mask),
+            if R == 3 and order is None:
+                order = x3p_item_list(rows, Cin, out.device)
+        n0 = lib.aod_conv_x3p_mapped_count() if X3P_MAP_LOG is not None else 0
+        _prof('dgrad', d, lambda: call('aod_conv2d_ws_map_order', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, None, ptr(res), ptr(mask),
                                        ptr(post_scale), None, ptr(colsum), ptr(ws), wsb, ptr(in_map) if out_map is not None else None,
-                                       ptr(out_map), stream()), alg)
+                                       ptr(out_map), ptr(order) if out_map is not None else None, stream()), alg)
+        if X3P_MAP_LOG is not None:
+            X3P_MAP_LOG.append((tuple(out.shape), lib.aod_conv_x3p_mapped_count() > n0))
         return out, out_map
     _prof('dgrad', d, lambda: call('aod_conv2d_ws', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, None, ptr(res), ptr(mask),
                                    ptr(post_scale), None, ptr(colsum), ptr(ws), wsb, stream()), alg)

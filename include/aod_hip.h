@@ -197,6 +197,22 @@ int aod_conv2d_ws_map(const aod_conv_desc_t* desc, const void* src, const void* 
 int aod_conv2d_grouped_map(const aod_conv_desc_t* desc, int ngroups, const void* const* src, const void* const* w_packed, void* const* dst,
                            const float* const* pre_shift, const void* const* mask, float* const* colsum, const void* const* in_map,
                            void* const* out_map, aod_stream_t stream);
+/* The mapped form of the persistent kernel.  `order`: int32 [ceil(rows / 128) * N / 128], device memory.  A 3x3 launch of aod_conv2d_ws_map
+ * that the persistent kernel takes and whose map may skip tiles then runs 128-column tiles -- a live 128-row tile is N / 128 ITEMS -- in the
+ * order of a list that the launch which writes out_map also writes there: a permutation of the items tile_m * (N / 128) + tile_n, ranked in
+ * that order, every live one ahead of every dead one.  List position pos is item pos / G of the workgroup whose slot is pos % G (G = the grid,
+ * a multiple of 8 * N / 128); slots go to the blocks one row tile at a time, round-robin over the blockIdx % 8 classes, so a row tile's column
+ * tiles share a class and every workgroup owns ceil(live / G) live items or one fewer, ahead of its dead ones (which still store their zero
+ * rows).  Same bits per row as aod_conv2d_ws_map.  order = NULL, AOD_X3P_MAPPED=0 (read per call), fewer than 8 * N / 128 items, or a launch
+ * the form does not apply to: aod_conv2d_ws_map unchanged.  aod_conv2d_x3p_item_order applies the rule to a HOST copy of the map (item, block
+ * and round of every list position for a grid of `grid` workgroups); aod_conv2d_x3p_mapped_grid is the grid on a device of `cus` compute
+ * units (0: the form is not taken); aod_conv_x3p_mapped_count() counts the launches that took the form in this process. */
+int aod_conv2d_ws_map_order(const aod_conv_desc_t* desc, const void* src, const void* w_packed, void* dst, const float* pre_scale,
+                            const float* pre_shift, const void* res, const void* mask, const float* post_scale, void* zraw, float* colsum,
+                            void* workspace, size_t workspace_bytes, const void* in_map, void* out_map, void* order, aod_stream_t stream);
+int aod_conv2d_x3p_item_order(int rows, int tiles_n, int grid, const void* map, int32_t* item, int32_t* block, int32_t* round);
+int aod_conv2d_x3p_mapped_grid(int rows, int tiles_n, int cus);
+int64_t aod_conv_x3p_mapped_count(void);
 
 /* Sparse forward (reference-precision mode, the reg and MEH towers in training).  The box-regression and the MEH loss multiply by the assigner's
  * bbox_weights, 0 at every anchor that is not positive, so those towers' activations are read only inside the receptive field of the positives.
