@@ -361,7 +361,9 @@ def conv2d_dgrad_rows(dz_rows, dz_segs, x_segs, w_dgrad, Cin, R, S, stride=1, pa
     if out is None:
         out = torch.empty(rows, Cin if out_f32 else width(Cin), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dz_rows.device)
     d = make_desc(Npad, Cin, R, S, stride, pad, dil, dz_segs, x_segs, True, False, out_f32)
-    if R == 3 and _halo_applies(d, Npad, res, post_scale, dgrad=True):
+    # (deterministic mode: aod_halo_conv3x3 sums its columns with atomics and has no ordered form -- a launch with column sums stays on the
+    # general kernel, whose tiles write partial rows)
+    if R == 3 and not (DETERMINISTIC and colsum is not None) and _halo_applies(d, Npad, res, post_scale, dgrad=True):
         _prof('dgrad', d, lambda: call('aod_halo_conv3x3', C.byref(d), ptr(dz_rows), ptr(w_dgrad), ptr(out), None, ptr(mask), ptr(colsum), stream()), alg)
         return out
     ws, wsb = _splitk_ws(d, dz_rows.device)

@@ -81,6 +81,8 @@ _case('bg128_1', B, 256, 256, 3, [(2, 21, 19)], igemm(128, 128, 512, 1, grouped=
 _case('bsplit128', B, 512, 512, 3, [(2, 16, 16)], splitk(4, 128), SH)      # 1.3e-02 (0.26)
 _case('bsplit64', B, 512, 64, 3, [(2, 16, 16)], splitk(9, 64), SH)      # 7.8e-03 (0.26)
 _case('bsplitP6', B, 2048, 256, 3, [(2, 15, 17)], splitk(28, 128), SH, stride=2)      # 1.2e-02 (0.26)
+# ... with column sums (conv_splitk_finalize_kernel's): K = 4608, 78 rows = 9 blocks of 8 and one of 6, 320 columns = a second, partly filled panel
+_case('bsplit_d', B, 320, 512, 3, [(2, 6, 5), (2, 3, 3)], splitk(9, 128), MASK | COLSUM, dgrad=True)      # 1.6e-02 (0.28), cs 1.4e-07
 # the streaming 1x1 kernel by its own heuristic (64 columns over >= 65 536 rows).  Its tile form follows from aod_pw_gemm: at 66 049 rows the
 # 517 tiles of 128 rows waste more of their last round than the 1 033 of 64 rows -> <64, 64>; at exactly 65 536 rows -> <128, 64>
 _case('bpw', B, 256, 64, 1, [(1, 257, 257)], PW_STREAM, pw_tile=(64, 64))      # 1.6e-02 (0.31)
@@ -105,6 +107,7 @@ _case('xg256_0', X, 256, 256, 3, [(2, 21, 19)], igemm(256, 256, 512, 0, x3=1, gr
 _case('xg256_1', X, 256, 256, 3, [(2, 21, 19)], igemm(256, 256, 512, 1, x3=1, grouped=1), MASK | COLSUM, members=2, dgrad=True)      # 7.6e-06, cs 3.6e-06
 _case('xsplit128', X, 512, 512, 3, [(2, 16, 16)], splitk(4, 128, x3=1), SH)      # 5.7e-06
 _case('xsplit64', X, 512, 64, 3, [(2, 16, 16)], splitk(16, 64, x3=1), SH)      # 6.3e-06
+_case('xsplit_d', X, 320, 512, 3, [(2, 6, 5), (2, 3, 3)], splitk(18, 128, x3=1), MASK | COLSUM, dgrad=True)      # 4.6e-06, cs 2.4e-06
 # the persistent kernel: X3P (taps, wide, pre, lat, grid)
 _case('p1400', X, 768, 384, 1, [(2, 64, 65)], x3p(1, grid=195), SC | SH)      # 5.8e-06
 _case('p1401', X, 1024, 256, 1, [(4, 64, 63)], x3p(1, pre=1, grid=252), SC | SH | RES, relu=True)      # 5.4e-06
@@ -291,18 +294,21 @@ def _acc(c, src, wt):
 Member = namedtuple('Member', 'got ref full before cs_got cs_ref')
 
 
-def run(name):
-    """launches the case through hipops in its mode -> one Member per group member (a plain launch: one): got / ref fp64 [M, N], `full` the
-    destination buffer with its guard rows, `before` what an in-place destination held, the column sums fp32 and their fp64 reference"""
+def _dims(c):
     from aod_meh_hua_amd import hipops as ho
+    src_segs, dst_segs = geometry(c)
+    N = c.cin if c.dgrad else c.cout
+    return src_segs, dst_segs, sum(s.rows for s in src_segs), sum(s.rows for s in dst_segs), N, (N if (c.out_f32 or c.mode == B) else ho.xw(N))
+
+
+def operands(name):
+    """the operands of the case, one dict per group member (a plain launch: one), with the fp64 reference of the destination rows (`ref`) and of
+    the column sums (`cs_ref`, from their start `cs0`) -- built once; launch() can run them any number of times"""
     c = CASES[name]
     with _mode(c):
-        src_segs, dst_segs = geometry(c)
-        rows_src, M = sum(s.rows for s in src_segs), sum(s.rows for s in dst_segs)
-        c_src, N = (c.cout, c.cin) if c.dgrad else (c.cin, c.cout)
-        f32 = c.out_f32
-        wide = N if (f32 or c.mode == B) else ho.xw(N)
-        k, pad = c.k, c.k // 2
+        src_segs, dst_segs, rows_src, M, N, wide = _dims(c)
+        c_src = c.cout if c.dgrad else c.cin
+        k = c.k
         ops = []
         for g in range(max(c.members, 1)):          # every member its own operands and filter
             gen = synth.gen(zlib.crc32(name.encode()) % 100000 + g)
@@ -313,14 +319,7 @@ def run(name):
             o['sh'] = (0.1 * torch.randn(N, generator=gen)).cuda() if c.ops & SH else None
             o['res'], res64 = _rows(torch.randn(M, N, generator=gen), c.mode) if c.ops & RES else (None, None)
             o['mask'], mask64 = _rows(torch.randn(M, N, generator=gen), c.mode) if c.ops & MASK else (None, None)
-            cs0 = torch.randn(N, generator=gen).cuda() if c.ops & COLSUM else None          # colsum is +=: it starts non-zero
-            o['cs'] = cs0.clone() if cs0 is not None else None
-            o['full'] = torch.full((M + GUARD, wide * (2 if f32 else 1)), SENTINEL, dtype=torch.int16, device='cuda').view(
-                torch.float32 if f32 else torch.bfloat16)
-            o['out'] = o['full'][:M]
-            if c.inplace:
-                o['out'].copy_(o['res'])
-                o['res'], o['before'] = o['out'], o['out'].clone()
+            o['cs0'] = cs0 = torch.randn(N, generator=gen).cuda() if c.ops & COLSUM else None          # colsum is +=: it starts non-zero
             v = _acc(c, src64, wt)
             if o['sc'] is not None:
                 v = v * o['sc'].double()
@@ -334,8 +333,31 @@ def run(name):
                 v = v.clamp_min(0)
             o['ref'], o['cs_ref'] = v, (cs0.double() + v.sum(0) if cs0 is not None else None)
             ops.append(o)
+        return ops
+
+
+def launch(name, members):
+    """launches the case through hipops in its mode on the operands() `members`, into a fresh destination and fresh column sums -> one Member
+    each: got / ref fp64 [M, N], `full` the destination buffer with its guard rows, `before` what an in-place destination held, the column
+    sums fp32 and their fp64 reference"""
+    from aod_meh_hua_amd import hipops as ho
+    c = CASES[name]
+    with _mode(c):
+        src_segs, dst_segs, rows_src, M, N, wide = _dims(c)
+        f32 = c.out_f32
+        ops = []
+        for o in members:
+            o = dict(o)
+            o['cs'] = o['cs0'].clone() if o['cs0'] is not None else None
+            o['full'] = torch.full((M + GUARD, wide * (2 if f32 else 1)), SENTINEL, dtype=torch.int16, device='cuda').view(
+                torch.float32 if f32 else torch.bfloat16)
+            o['out'] = o['full'][:M]
+            if c.inplace:
+                o['out'].copy_(o['res'])
+                o['res'], o['before'] = o['out'], o['out'].clone()
+            ops.append(o)
         col = lambda key: [o[key] for o in ops]
-        geo = (k, k, c.stride, pad, 1)
+        geo = (c.k, c.k, c.stride, c.k // 2, 1)
         if c.members and c.dgrad:
             ho.conv2d_dgrad_rows_grouped(col('src'), src_segs, dst_segs, col('w'), N, *geo, masks=col('mask') if c.ops & MASK else None,
                                          colsums=col('cs') if c.ops & COLSUM else None, outs=col('out'))
@@ -357,6 +379,11 @@ def run(name):
             got = ho.x3_merge(o['out'], N).double() if (c.mode == X and not f32) else o['out'].double()
             res.append(Member(got, o['ref'], o['full'], o.get('before'), o['cs'], o['cs_ref']))
         return res
+
+
+def run(name):
+    """operands() and one launch() of the case"""
+    return launch(name, operands(name))
 
 
 def bounds(c):

@@ -2,7 +2,11 @@
 tools/train_RetinaNet.py:56-68).  Everything on the training path is order-deterministic by construction except the bias / BN-shift column
 sums (fp32 atomics); in this mode they are ordered sums of per-workgroup partials (csrc/determinism.hip).  Two runs from the same seeded
 weights must then end in the SAME bits -- eagerly and through the captured graphs, in both arithmetic modes -- where the default mode's
-reference-precision runs drift apart within three iterations (tools/dbg/emu_twice.py)."""
+reference-precision runs drift apart within three iterations (tools/dbg/emu_twice.py).
+
+What is checked here is REPEATABILITY (and, loosely, that one step stays within 2e-6 of the default mode's weights): a sum that is wrong
+but repeatable passes.  The VALUES of the ordered sums -- every producer of partial rows and the finalize, against fp64, behind a poisoned
+scratch -- and the dispatch the mode changes are checked in tests/test_gpu_det_colsum.py."""
 import hashlib
 import os
 import sys
