@@ -200,6 +200,10 @@ _SIGS = {
     'aod_loc_stability_max_levels': (C.c_int, []),
     'aod_pixel_noise': (C.c_int, [P, P, I32, I32, I32, I32, P, P, F32, I32, U64, P, P]),
     'aod_loc_stability': (C.c_int, [P, P, P, I32, I32, I32, F32, I32, I32, P, P, P]),
+    'aod_class_difficulty_ws_len': (SZ, [I64, I32]),
+    'aod_class_difficulty_accum': (C.c_int, [P, P, P, P, P, I64, I32, I32, P, P, F32, F32, P, P, P]),
+    'aod_class_difficulty_update': (C.c_int, [P, P, I32, F32, P]),
+    'aod_det_uncertainty_w': (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P, P, P, P, P, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -49,6 +49,10 @@ class Uncertainty_fns:
         # and no uPool2 are read: every head offers these pools, MyRetinaHead and the SSD head included
         model, dataloader = args
         model.eval()
+        if kwargs.get('class_weighted'):
+            sync_class_difficulty(model)
+        else:
+            kwargs.pop('class_weighted', None)      # (off: the default kwargs, and with them the key of the captured scoring graph)
         unc = single_gpu_uncertainty(model, dataloader, isUnc=getattr(cfg, 'uncertainty_type', None) or 'Epistemic', uPool=pool, **kwargs)
         return unc.cpu() if torch.is_tensor(unc) else [u.cpu() if torch.is_tensor(u) else u for u in unc]
 
@@ -85,7 +89,15 @@ class Uncertainty_fns:
         # candidate_factor, max_obj, measure and aggregate are its own
         model, dataloader = args
         own = {k: kwargs[k] for k in ('candidate_factor', 'max_obj', 'measure', 'aggregate') if kwargs.get(k) is not None}
+        if kwargs.get('class_weighted'):
+            own['class_weighted'] = True
         return CCMS_uncertainty(cfg, model, dataloader, **_labelled_options('CCMS', kwargs), **own)
+
+    @staticmethod
+    def PPAL(cfg, *args, **kwargs):
+        # PPAL (Yang et al., CVPR 2024) whole: CCMS with stage 1 ranked by the difficulty-calibrated entropy -- every detection's
+        # entropy times the weight of its class, from the class-difficulty EMA the head kept while it trained (bbox_head.class_difficulty)
+        return Uncertainty_fns.CCMS(cfg, *args, **dict(kwargs, class_weighted=True))
 
     @staticmethod
     def _loc_stability(combine, cfg, *args, **kwargs):
@@ -122,6 +134,23 @@ _SHARD_STATE = dict(interleaved=False, imbalance=None, over=0)       # pool part
 def calculate_uncertainty(cfg, *args, **kwargs):
     """test.py:65-70."""
     return getattr(Uncertainty_fns, cfg.uncertainty_pool)(cfg, *args, **kwargs)
+
+
+def sync_class_difficulty(model, src=0):
+    """Before a class-weighted pool pass: with torch.distributed initialised, rank `src`'s class_difficulty goes to every rank --
+    each rank's EMA followed its own batches, and the ranks must weight alike to rank one pool -- then the head's class_weight buffer is
+    recomputed from it in place (head.refresh_class_weight: device ops, no host sync), so a captured scoring graph reads current values.
+    A head without the option raises (ValueError; the SSD heads NotImplementedError) before any batch is scored.  Returns the head."""
+    m = getattr(model, 'module', model)
+    head = getattr(m, 'bbox_head', m)
+    if getattr(head, 'class_difficulty_cfg', None) is None:
+        from ..scoring import _class_weight
+        _class_weight(head, None, dict(class_weighted=True))
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.broadcast(head.class_difficulty, src=src)
+    head.refresh_class_weight()
+    return head
 
 
 def _labelled_options(pool, kwargs, score_thr=True):
@@ -610,20 +639,25 @@ def single_gpu_object_descriptors(model, data_loader, max_obj=32, score_thr=0.3,
 
 
 def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_factor=4, max_obj=32, score_thr=0.3, measure='entropy',
-                     aggregate='sum', **kwargs):
+                     aggregate='sum', class_weighted=False, **kwargs):
     """CCMS acquisition (the two-stage pick of PPAL: C. Yang, L. Huang, E. J. Crowley, "Plug and Play Active Learning for Object
-    Detection", CVPR 2024, without its training-side class-difficulty EMA; the reference has none) in the form update_X_L takes.
+    Detection", CVPR 2024; its training-side class-difficulty EMA: class_weighted below; the reference has none) in the form update_X_L takes.
     Stage 1: the posterior score of every image (single_gpu_object_descriptors) ranks the unlabelled images; the top
     M = min(ceil(candidate_factor * budget), #unlabelled) are the candidates (scoring.ccms_candidates).  Stage 2: the [M, M]
     category-conditioned matching distance between them (scoring.ccms_distance), then k-center greedy on it with no initial centers
     (scoring.kcenter_greedy_matrix): the first pick is the most uncertain candidate, every later one the candidate farthest from the picks
     so far.  Every rank runs stage 2 on the same tensors and gets the same picks.  budget: default cfg.X_S_size.  Returns a CPU [N] fp32
     vector: the image picked at step t = 0 .. budget - 1 scores budget - t, every other image 0 -- with a falsy zeroRate update_X_L's
-    arg[-X_S_size:] selects exactly the picks."""
+    arg[-X_S_size:] selects exactly the picks.
+    class_weighted=True (Uncertainty_fns.PPAL): stage 1 ranks by the difficulty-calibrated measure -- every detection's value times
+    the weight of its class, from the class-difficulty EMA of a head built with bbox_head.class_difficulty; the published PPAL rule."""
     from ..scoring import ccms_candidates, ccms_distance, kcenter_greedy_matrix
     if X_L is None:
         raise TypeError('CCMS_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are excluded from the candidates')
     budget = int(cfg.X_S_size if budget is None else budget)
+    if class_weighted:
+        sync_class_difficulty(model)
+        kwargs['class_weighted'] = True
     pool = single_gpu_object_descriptors(model, data_loader, max_obj=max_obj, score_thr=score_thr, measure=measure, aggregate=aggregate, **kwargs)
     cand = ccms_candidates(pool['unc'], X_L, budget, candidate_factor)
     ci = torch.from_numpy(cand).to(pool['unc'].device)
@@ -631,14 +665,16 @@ def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_f
     return _pick_scores(ci[kcenter_greedy_matrix(dist, [], budget)[0]], pool['unc'].shape[0])
 
 
-def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, **kwargs):
+def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, class_weighted=False, **kwargs):
     """Uncertainty sampling on the detector's own class posterior ("Entropy" in the paper's tables, margin and least confidence
     after Brust et al., VISAPP 2019, and Roy et al., BMVC 2018; the reference has none) in the form update_X_L takes: per detection whose
     score exceeds score_thr the entropy / 1-vs-2 margin / least confidence of its class posterior, aggregated over the image's detections
     by max / mean / sum; an image without such a detection scores 0.  One forward per image; the pool pass is single_gpu_uncertainty's
     (sharded, prefetched, one captured graph while the batch shape repeats, one gather).  Every detector has it: the evidence heads (their
     EDL-normalised scores), the plain RetinaNet (sigmoid scores) and SSD (softmax with background); the config's uncertainty_pool is not
-    read.  Returns the CPU [N] fp32 vector; these are ordinary scores, zeroRate stays on."""
+    read.  Returns the CPU [N] fp32 vector; these are ordinary scores, zeroRate stays on.
+    class_weighted=True: every detection's value is multiplied by the weight of its class, from the class-difficulty EMA of a head
+    built with bbox_head.class_difficulty (the evidence heads and MyRetinaHead; any other head raises)."""
     from ..scoring import UNC_AGGREGATES, UNC_MEASURES
     if measure not in UNC_MEASURES:
         raise ValueError(f"Posterior_uncertainty: unknown measure {measure!r} (expected 'entropy', 'margin' or 'leastconf')")
@@ -648,6 +684,8 @@ def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate=
     if score_thr != score_thr:
         raise ValueError('Posterior_uncertainty: score_thr is NaN')
     pool = {'entropy': 'Entropy', 'margin': 'Margin', 'leastconf': 'LeastConf'}[measure]
+    if class_weighted:
+        kwargs['class_weighted'] = True
     return getattr(Uncertainty_fns, pool)(cfg, model, data_loader, unc_aggregate=aggregate, score_thr=score_thr, **kwargs)
 
 

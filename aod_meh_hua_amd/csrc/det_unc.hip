@@ -18,7 +18,8 @@
 //      on a hash hit.  With max_num <= 128 the idle waves take further parts of the tile: wave w scans part w / ndw for the detection rows
 //      of wave w % ndw; the lowest index over the parts is the minimum of the parts' own lowest.
 //   3. a thread per detection row: the measure of its row (the classes in column order), written to obj_out and to LDS; the matched
-//      candidate row itself goes to obj_cand (aod_det_uncertainty_ex: what the CCMS object descriptors of DESIGN 3o are gathered by)
+//      candidate row itself goes to obj_cand (aod_det_uncertainty_ex: what the CCMS object descriptors of DESIGN 3o are gathered by).
+//      With class_w (aod_det_uncertainty_w: the class-weighted pools of DESIGN 3p) the measure is first multiplied by class_w[label]
 //   4. the aggregate: a pairwise tree over the next power of two >= max_num in LDS -- rows that are no object hold 0 -- so the association of
 //      the sum depends on j and max_num alone: an image has the same score bits alone, at any place of any batch, eager or replayed.
 #include <hip/hip_runtime.h>
@@ -67,7 +68,8 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
                                                         const float* __restrict__ dets, const long long* __restrict__ labels,
                                                         const int* __restrict__ num, int n, int W, int max_num, int layout, int measure,
                                                         int aggregate, float thr, float* __restrict__ unc, float* __restrict__ obj_out,
-                                                        int* __restrict__ missing, int* __restrict__ obj_cand) {
+                                                        int* __restrict__ missing, int* __restrict__ obj_cand,
+                                                        const float* __restrict__ class_w) {
   __shared__ __align__(16) unsigned tile[DU_TILE];
   __shared__ unsigned dhash[DU_MAX_DET];
   __shared__ int lab[DU_MAX_DET];          // the label of an object row; -1: no object; -2: an object whose label names no column
@@ -158,7 +160,9 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
         if (k == INT_MAX) {
           flag = 1 << 16;
         } else {
-          m = o = du_measure(sc + (long long)k * W, used, layout, measure);
+          m = du_measure(sc + (long long)k * W, used, layout, measure);
+          if (class_w) m = __fmul_rn(m, class_w[l]);         // (class-weighted pools, DESIGN 3p: one multiply in front of the tree)
+          o = m;
           flag = 1;
           kc = k;
         }
@@ -192,9 +196,11 @@ __global__ __launch_bounds__(DU_TB) void det_unc_kernel(const unsigned* __restri
 
 // obj_cand [B][max_num] int32 (nullable): the candidate row the lookup matched to every object row, -1 for a row that is no object or has none
 // (aod_object_descriptors reads the neck row of that candidate's anchor: no second matching pass).  The other outputs are aod_det_uncertainty's.
-extern "C" int aod_det_uncertainty_ex(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
-                                      int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
-                                      float* obj_out, int32_t* missing, int32_t* obj_cand, aod_stream_t stream) {
+// class_w [W] (nullable): the measure of an object row with label l is multiplied by class_w[l] before it goes to obj_out and into the aggregate
+// (aod_class_difficulty_*: DESIGN 3p).  NULL: no multiply, aod_det_uncertainty_ex's bits.
+extern "C" int aod_det_uncertainty_w(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
+                                     int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
+                                     float* obj_out, int32_t* missing, int32_t* obj_cand, const float* class_w, aod_stream_t stream) {
   AOD_CHECK_ARG(layout >= 0 && layout <= 2, "det_uncertainty: layout %d is none of 0 (cat), 1 (cat_bg), 2 (sigmoid)", layout);
   AOD_CHECK_ARG(measure >= 0 && measure <= 2, "det_uncertainty: measure %d is none of 0 (entropy), 1 (margin), 2 (leastconf)", measure);
   AOD_CHECK_ARG(aggregate >= 0 && aggregate <= 2, "det_uncertainty: aggregate %d is none of 0 (max), 1 (mean), 2 (sum)", aggregate);
@@ -206,15 +212,23 @@ extern "C" int aod_det_uncertainty_ex(const float* boxes, const float* scores, c
   AOD_CHECK_ARG(measure != 1 || used >= 2, "det_uncertainty: margin needs two used columns (layout %d reads %d of W = %d)", layout, used, W);
   AOD_CHECK_ARG(boxes && scores && dets && labels && num && unc, "det_uncertainty: null pointer");
   AOD_CHECK_ARG(((((size_t)boxes) | ((size_t)scores) | ((size_t)dets) | ((size_t)num) | ((size_t)unc) | ((size_t)obj_out) | ((size_t)missing) |
-                   ((size_t)obj_cand)) & 3) == 0 &&
+                   ((size_t)obj_cand) | ((size_t)class_w)) & 3) == 0 &&
                     (((size_t)labels) & 7) == 0,
                 "det_uncertainty: pointers must be aligned to their element size");
   AOD_CHECK_ARG(score_thr == score_thr, "det_uncertainty: score_thr is NaN");
   AOD_CHECK_ARG(n <= (1 << 30), "det_uncertainty: up to 2^30 candidate rows per image (got n = %d)", n);
   hipLaunchKernelGGL(det_unc_kernel, dim3((unsigned)B), dim3(DU_TB), 0, (hipStream_t)stream, (const unsigned*)boxes, scores, dets,
-                     (const long long*)labels, num, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing, obj_cand);
+                     (const long long*)labels, num, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing, obj_cand,
+                     class_w);
   AOD_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int aod_det_uncertainty_ex(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,
+                                      int n, int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc,
+                                      float* obj_out, int32_t* missing, int32_t* obj_cand, aod_stream_t stream) {
+  return aod_det_uncertainty_w(boxes, scores, dets, labels, num, B, n, W, max_num, layout, measure, aggregate, score_thr, unc, obj_out, missing,
+                               obj_cand, nullptr, stream);
 }
 
 extern "C" int aod_det_uncertainty(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B,

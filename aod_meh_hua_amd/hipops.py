@@ -926,6 +926,85 @@ def pad_cast_colsum(g, npad, relu_out=None, want_map=False):
 
 _F4 = C.c_float * 4
 
+CLASS_DIFFICULTY_MAX_C = 128
+CLASS_DIFFICULTY_FORMS = {'edl': 0, 'sigmoid': 1}      # the loss form's own probability of the target class: softmax | per-class sigmoid
+
+
+def _cd_f32(name, arg, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name}: {arg} must be an fp32 tensor of shape {tuple(shape)}'
+                         + (f', got {str(t.dtype).replace("torch.", "")} {tuple(t.shape)}' if torch.is_tensor(t) else ''))
+    if not t.is_contiguous():
+        raise ValueError(f'{name}: {arg} is not contiguous; no copy is made here')
+
+
+def class_difficulty_accum(cls, labels, label_w, bbox_pred, bbox_tgt, acc, form='edl', means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.),
+                           wh_ratio_clip=16 / 1000, xi=0.6):
+    """Adds one batch's per-class difficulty statistic into acc (aod_class_difficulty_accum).
+
+    cls [rows, C] fp32 logits, labels [rows] int64, label_w [rows] fp32, bbox_pred / bbox_tgt [rows, 4] fp32 deltas: the operands of
+    edl_focal_l1_fwd.  A positive is a row with 0 <= label < C and label_w > 0; per positive q = 1 - P^xi IoU^(1 - xi) with P the
+    probability `form` ('edl': softmax, 'sigmoid') gives its label and IoU that of the boxes decoded from the two deltas.  acc [2C] fp32:
+    acc[:C] += the sums of q per class, acc[C:] += the counts.  Rows that are no positive may hold NaN in cls / bbox_pred.  Returns acc;
+    no host sync, no atomics, the same bits on every run."""
+    nm = 'class_difficulty_accum'
+    if form not in CLASS_DIFFICULTY_FORMS:
+        raise ValueError(f"{nm}: unknown form {form!r} (expected 'edl' or 'sigmoid')")
+    xi, wh_ratio_clip = float(xi), float(wh_ratio_clip)
+    if not 0.0 <= xi <= 1.0:
+        raise ValueError(f'{nm}: xi must be in [0, 1], got {xi}')
+    if not 0.0 < wh_ratio_clip < float('inf'):
+        raise ValueError(f'{nm}: wh_ratio_clip must be positive and finite, got {wh_ratio_clip}')
+    means, stds = tuple(float(v) for v in means), tuple(float(v) for v in stds)
+    if len(means) != 4 or len(stds) != 4 or not all(abs(v) < float('inf') for v in means + stds):
+        raise ValueError(f'{nm}: means / stds must hold four finite numbers each')
+    if not torch.is_tensor(cls) or cls.dim() != 2 or cls.dtype != torch.float32:
+        raise ValueError(f'{nm}: cls must be a 2-D fp32 tensor [rows, C]')
+    rows, Cc = (int(v) for v in cls.shape)
+    if not 1 <= Cc <= CLASS_DIFFICULTY_MAX_C:
+        raise ValueError(f'{nm}: 1..{CLASS_DIFFICULTY_MAX_C} classes are supported, got C = {Cc}')
+    if not cls.is_contiguous():
+        raise ValueError(f'{nm}: cls is not contiguous; no copy is made here')
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64 or tuple(labels.shape) != (rows,) or not labels.is_contiguous():
+        raise ValueError(f'{nm}: labels must be a contiguous int64 tensor of shape ({rows},)')
+    _cd_f32(nm, 'label_w', label_w, (rows,))
+    _cd_f32(nm, 'bbox_pred', bbox_pred, (rows, 4))
+    _cd_f32(nm, 'bbox_tgt', bbox_tgt, (rows, 4))
+    _cd_f32(nm, 'acc', acc, (2 * Cc,))
+    ts = (cls, labels, label_w, bbox_pred, bbox_tgt, acc)
+    for t in ts:
+        if not t.is_cuda:
+            raise _C.AodHipError(f'{nm} needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    if any(t.device != cls.device for t in ts):
+        raise ValueError(f'{nm}: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    if rows == 0:
+        return acc
+    if bbox_pred.data_ptr() % 16 or bbox_tgt.data_ptr() % 16:
+        raise ValueError(f'{nm}: bbox_pred / bbox_tgt must be 16-byte aligned')
+    ws = torch.empty(max(int(_C.lib.aod_class_difficulty_ws_len(rows, Cc)), 1), dtype=torch.float32, device=cls.device)
+    call('aod_class_difficulty_accum', ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), rows, Cc, CLASS_DIFFICULTY_FORMS[form],
+         _F4(*means), _F4(*stds), wh_ratio_clip, xi, ptr(acc), ptr(ws), stream())
+    return acc
+
+
+def class_difficulty_update(acc, d, momentum=0.99):
+    """The EMA step (aod_class_difficulty_update): d[c] = momentum d[c] + (1 - momentum) acc[c] / acc[C + c] for every class
+    with a positive count, every other d[c] keeps its bits; acc [2C] is zeroed.  d [C] fp32, in place.  Returns d."""
+    nm = 'class_difficulty_update'
+    momentum = float(momentum)
+    if not 0.0 <= momentum <= 1.0:
+        raise ValueError(f'{nm}: momentum must be in [0, 1], got {momentum}')
+    if not torch.is_tensor(d) or d.dim() != 1 or d.dtype != torch.float32 or not 1 <= d.numel() <= CLASS_DIFFICULTY_MAX_C or not d.is_contiguous():
+        raise ValueError(f'{nm}: d must be a contiguous 1-D fp32 tensor of 1..{CLASS_DIFFICULTY_MAX_C} classes')
+    _cd_f32(nm, 'acc', acc, (2 * d.numel(),))
+    for t in (acc, d):
+        if not t.is_cuda:
+            raise _C.AodHipError(f'{nm} needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
+    if acc.device != d.device:
+        raise ValueError(f'{nm}: acc and d live on different devices')
+    call('aod_class_difficulty_update', ptr(acc), ptr(d), int(d.numel()), momentum, stream())
+    return d
+
 
 def max_iou_assign(anchors, valid, gts, gt_count, gt_labels, pos_thr=0.5, neg_thr=0.4, min_pos_iou=0.0, assign_all=True,
                    num_classes=20, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), level_start=None):

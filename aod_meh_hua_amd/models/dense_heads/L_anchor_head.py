@@ -59,7 +59,7 @@ class L_AnchorHead(BaseModule):
                  bbox_coder=dict(type='DeltaXYWHBBoxCoder', clip_border=True, target_means=(.0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0)),
                  reg_decoded_bbox=False, loss_cls=dict(type='CrossEntropyLoss', last_activation='sigmoid', loss_weight=1.0),
                  loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None,
-                 init_cfg=dict(type='Normal', layer='Conv2d', std=0.01)):
+                 init_cfg=dict(type='Normal', layer='Conv2d', std=0.01), class_difficulty=None):
         super().__init__(init_cfg)
         self.in_channels, self.num_classes, self.feat_channels = in_channels, num_classes, feat_channels
         self.last_activation = loss_cls.get('last_activation')
@@ -84,6 +84,84 @@ class L_AnchorHead(BaseModule):
         self.anchor_generator = build_anchor_generator(anchor_generator)
         self.num_anchors = self.anchor_generator.num_base_anchors[0]
         self._init_layers()
+        self._init_class_difficulty(class_difficulty)
+
+    # ------------------------------------------------------------------ class difficulty
+    class_difficulty_cfg = None      # None: nothing is tracked -- no buffer, no launch, no state_dict key
+
+    def _init_class_difficulty(self, cfg):
+        """class_difficulty=dict(xi=0.6, momentum=0.99, alpha=0.3, beta=0.2): PPAL's per-class difficulty EMA (Yang et al., CVPR 2024).  The head
+        then owns `class_difficulty` [C] (ones: a fresh model weights every class alike), `class_weight` [C + 1] (what the class-weighted
+        pools multiply by; the pad / background column stays 1) -- both persistent -- and the statistic of the running iteration (not saved)."""
+        if cfg is None:
+            return
+        if type(self).loss_all_levels is L_AnchorHead.loss_all_levels:
+            raise NotImplementedError(f'{type(self).__name__}: class_difficulty is built for the heads on the fused focal + L1 loss launches')
+        cfg = dict(cfg)
+        unknown = sorted(set(cfg) - {'xi', 'momentum', 'alpha', 'beta'})
+        if unknown:
+            raise ValueError(f'class_difficulty: unknown keys {unknown} (expected xi, momentum, alpha, beta)')
+        cfg = dict(xi=float(cfg.get('xi', 0.6)), momentum=float(cfg.get('momentum', 0.99)), alpha=float(cfg.get('alpha', 0.3)),
+                   beta=float(cfg.get('beta', 0.2)))
+        if not (0.0 <= cfg['xi'] <= 1.0 and 0.0 <= cfg['momentum'] <= 1.0):
+            raise ValueError(f"class_difficulty: xi and momentum must be in [0, 1] (got {cfg['xi']}, {cfg['momentum']})")
+        if not (0.0 < cfg['alpha'] < float('inf') and 0.0 <= cfg['beta'] < float('inf')):
+            raise ValueError(f"class_difficulty: alpha must be positive and beta non-negative (got {cfg['alpha']}, {cfg['beta']})")
+        C = self.cls_out_channels
+        if not 1 <= C <= 128:
+            raise ValueError(f'class_difficulty: 1..128 classes are supported, the head has {C}')
+        self.class_difficulty_cfg = cfg
+        self.register_buffer('class_difficulty', torch.ones(C))
+        self.register_buffer('class_weight', torch.ones(C + 1))
+        self.register_buffer('_class_difficulty_acc', torch.zeros(2 * C), persistent=False)
+        self._class_difficulty_due = False
+        self._class_difficulty_warned = False
+        self.refresh_class_weight()
+
+    @torch.no_grad()
+    def refresh_class_weight(self):
+        """class_weight[c] = 1 + alpha beta ln(1 + gamma d[c]), gamma = e^(1 / alpha) - 1, in place from class_difficulty: device ops, no host
+        sync.  d in [0, 1] gives a weight in [1, 1 + beta].  The pool passes call it once before their first batch, so a captured scoring
+        graph -- which holds the buffer's address -- reads current values at replay."""
+        if self.class_difficulty_cfg is None:
+            raise ValueError(f'{type(self).__name__} tracks no class difficulty: build it with bbox_head.class_difficulty=dict(...)')
+        import math
+        a, b = self.class_difficulty_cfg['alpha'], self.class_difficulty_cfg['beta']
+        C = self.class_difficulty.numel()
+        w = torch.log1p(self.class_difficulty * math.expm1(1.0 / a)) * (a * b) + 1.0
+        self.class_weight[:C].copy_(w)
+        return self.class_weight
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        if self.class_difficulty_cfg is not None and prefix + 'class_difficulty' not in state_dict:
+            # a checkpoint written without the option: the fresh state (ones) stays
+            if not self._class_difficulty_warned:
+                import warnings
+                warnings.warn(f'{prefix}class_difficulty is not in the checkpoint: the class difficulty starts from ones')
+                self._class_difficulty_warned = True
+            state_dict[prefix + 'class_difficulty'] = self.class_difficulty.detach().clone()
+            state_dict[prefix + 'class_weight'] = self.class_weight.detach().clone()
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def _track_class_difficulty(self, cls_rows, labels, label_w, box_rows, bbox_t):
+        """behind a loss forward: the launch's operands (all levels, or one level) add their positives' statistic to the iteration's"""
+        if self.class_difficulty_cfg is None or not self.training:
+            return
+        from ... import hipops as ho
+        with torch.no_grad():
+            ho.class_difficulty_accum(cls_rows.detach(), labels, label_w, box_rows.detach(), bbox_t, self._class_difficulty_acc,
+                                      form=getattr(self, '_focal_form', 'edl'), means=tuple(self.bbox_coder.means), stds=tuple(self.bbox_coder.stds),
+                                      xi=self.class_difficulty_cfg['xi'])
+        self._class_difficulty_due = True
+
+    def _step_class_difficulty(self):
+        """one EMA update per training iteration, behind the last accumulate"""
+        if self.class_difficulty_cfg is None or not self._class_difficulty_due:
+            return
+        from ... import hipops as ho
+        with torch.no_grad():
+            ho.class_difficulty_update(self._class_difficulty_acc, self.class_difficulty, self.class_difficulty_cfg['momentum'])
+        self._class_difficulty_due = False
 
     def _init_layers(self):
         self.conv_cls = Conv2d(self.in_channels, self.num_anchors * self.cls_out_channels, 1)
@@ -200,6 +278,7 @@ class L_AnchorHead(BaseModule):
                                list(range(len(cls_scores))), num_total_samples=num_total_samples, featmap_sizes=featmap_sizes,
                                defer_avg=self._can_defer_avg, **kwargs)
             losses_cls, losses_bbox, losses_noR = outs[0], outs[1], outs[2]
+        self._step_class_difficulty()
         if self._can_defer_avg:
             # the per-level "sum / num_total_samples" of loss_single (L_anchor_head.py:266-288) and the "mean(loss_noR)" of
             # _parse_losses (SSL_Lambda.py:136-141) for all levels at once: the same quotients from three launches (stack, divisor, divide)

@@ -177,6 +177,11 @@ class Lambda_L2Net(L_AnchorHead):
         sum_cls, sum_box, loss_noR, sum_noR = AF.RetinaLossFn.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
                                                                     float(self.loss_cls.gamma), float(self.loss_cls.alpha), self.cls_out_channels,
                                                                     kwargs.get('grad_arena'), int(sIdx), self._focal_form)
+        if self.class_difficulty_cfg is not None and self.training:      # (the operands as RetinaLossFn.forward hands them to the launch)
+            C = self.cls_out_channels
+            self._track_class_difficulty(AF.as_rows(cls_score.detach()).view(-1, C), labels.reshape(-1).contiguous(),
+                                         label_weights.reshape(-1).contiguous(), AF.as_rows(bbox_pred.detach()).view(-1, 4),
+                                         bbox_targets.reshape(-1, 4).contiguous())
         wc, wb = self.loss_cls.loss_weight, self.loss_bbox.loss_weight
         scaled = lambda w, t: t if w == 1.0 else w * t          # (1.0 * t == t exactly: no launch for the default weights)
         if kwargs.get('defer_avg'):                               # loss() divides all levels by their counts in one launch
@@ -205,6 +210,8 @@ class Lambda_L2Net(L_AnchorHead):
         out = AF.RetinaLossLevelsFn.apply(cls_d.view(-1, C), box_d.view(-1, 4), flat[0], flat[1], flat[2], flat[3],
                                           float(self.loss_cls.gamma), float(self.loss_cls.alpha), level_rows,
                                           (A, cls_d.shape[1], box_d.shape[1]), num_pos, self._focal_form)
+        if self.class_difficulty_cfg is not None:
+            self._track_class_difficulty(cls_d.view(-1, C), flat[0], flat[1], box_d.view(-1, 4), flat[2])
         return (out[0], list(out[1].split(level_rows))) + tuple(out[2:])
 
     def loss_all_levels_L(self, L_scores, losses, bw_list, **kwargs):

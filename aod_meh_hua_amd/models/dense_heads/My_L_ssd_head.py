@@ -30,8 +30,11 @@ class MyLSSDHead(L_AnchorHead):
                                        ratios=([2], [2, 3], [2, 3], [2, 3], [2], [2]), basesize_ratio_range=(0.1, 0.9)),
                  bbox_coder=dict(type='DeltaXYWHBBoxCoder', clip_border=True, target_means=[.0, .0, .0, .0], target_stds=[1.0, 1.0, 1.0, 1.0]),
                  reg_decoded_bbox=False, train_cfg=None, test_cfg=None,
-                 init_cfg=dict(type='Xavier', layer='Conv2d', distribution='uniform', bias=0)):
+                 init_cfg=dict(type='Xavier', layer='Conv2d', distribution='uniform', bias=0), class_difficulty=None):
         BaseModule.__init__(self, init_cfg)
+        if class_difficulty is not None:
+            raise NotImplementedError('MyLSSDHead: class_difficulty (the class-difficulty EMA of DESIGN 3p) is built for the RetinaNet heads; '
+                                      'the SSD loss launches are a follow-up')
         assert stacked_convs == 0 and not use_depthwise and not reg_decoded_bbox
         self.num_classes, self.in_channels, self.feat_channels = num_classes, in_channels, feat_channels
         self.last_activation = 'softmax'

@@ -497,7 +497,8 @@ ACTIVATION_LAYOUT = {'relu': 'cat', 'softmax': 'cat_bg', 'sigmoid': 'sigmoid'}  
 UNC_MAX_DET = 1024
 
 
-def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregate='max', score_thr=0.3, want_objects=False, want_cand=False):
+def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregate='max', score_thr=0.3, want_objects=False, want_cand=False,
+                    class_w=None):
     """Posterior uncertainty of every image of a batch (aod_det_uncertainty): entropy, 1-vs-2 margin or least confidence of the
     class posterior of every detection, aggregated over the image's detections by max, mean or sum; an image without an object scores 0.
 
@@ -508,7 +509,9 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     the candidates by its box and score bits.  Returns unc [B] fp32 on the device (no host sync), or with want_objects
     (unc, obj_out [B, max_num] fp32 -- NaN where the row is no object --, missing [B] int32 -- objects without a candidate row: always 0).
     want_cand (aod_det_uncertainty_ex; the same unc bits) appends obj_cand [B, max_num] int32: the candidate row matched to every object
-    row, -1 elsewhere -- what object_descriptors reads."""
+    row, -1 elsewhere -- what object_descriptors reads.
+    class_w (aod_det_uncertainty_w): fp32 [W] device tensor; the measure of an object with label l is multiplied by class_w[l]
+    before it is written to obj_out and enters the aggregate.  None: no multiply (all ones give the same bits)."""
     if layout not in UNC_LAYOUTS:
         raise ValueError(f"det_uncertainty: unknown layout {layout!r} (expected 'cat', 'cat_bg' or 'sigmoid')")
     if measure not in UNC_MEASURES:
@@ -543,6 +546,12 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     if tuple(num.shape) != (B,):
         raise ValueError(f'det_uncertainty: num has shape {tuple(num.shape)}, expected ({B},)')
     ts = (boxes, scores, dets, labels, num)
+    if class_w is not None:
+        if not torch.is_tensor(class_w) or class_w.dtype != torch.float32 or tuple(class_w.shape) != (W,):
+            raise ValueError(f'det_uncertainty: class_w must be an fp32 tensor of shape ({W},): one weight per column of cand.scores')
+        if not class_w.is_contiguous():
+            raise ValueError('det_uncertainty: class_w is not contiguous; no copy is made here')
+        ts = ts + (class_w,)
     for t in ts:
         if not t.is_cuda:
             raise _C.AodHipError('det_uncertainty needs tensors on the MI355X (cuda:N); got a CPU tensor. There is no CPU fallback.')
@@ -552,6 +561,12 @@ def det_uncertainty(cand, dets, labels, num, layout, measure='entropy', aggregat
     unc = torch.empty(B, dtype=torch.float32, device=dev)
     obj_out = torch.empty(B, max_num, dtype=torch.float32, device=dev) if want_objects else None
     missing = torch.empty(B, dtype=torch.int32, device=dev) if want_objects else None
+    if class_w is not None:
+        obj_cand = torch.empty(B, max_num, dtype=torch.int32, device=dev) if want_cand else None
+        call('aod_det_uncertainty_w', ptr(boxes), ptr(scores), ptr(dets), ptr(labels), ptr(num), B, n, W, max_num, UNC_LAYOUTS[layout],
+             UNC_MEASURES[measure], UNC_AGGREGATES[aggregate], score_thr, ptr(unc), ptr(obj_out), ptr(missing), ptr(obj_cand), ptr(class_w), stream())
+        out = (unc,) + ((obj_out, missing) if want_objects else ()) + ((obj_cand,) if want_cand else ())
+        return out if len(out) > 1 else unc
     if want_cand:
         obj_cand = torch.empty(B, max_num, dtype=torch.int32, device=dev)
         call('aod_det_uncertainty_ex', ptr(boxes), ptr(scores), ptr(dets), ptr(labels), ptr(num), B, n, W, max_num, UNC_LAYOUTS[layout],
@@ -785,6 +800,24 @@ def refuse_hua(head, **kwargs):
                          'use Random, Coreset, CDAL, or the Ensemble / MC-dropout scores')
 
 
+def _class_weight(head, cand, kwargs):
+    """class_weighted=True: the head's `class_weight` buffer [W] -- refreshed by head.refresh_class_weight() before the pool pass, read
+    by the launch at replay time -- or None.  A head without class-difficulty tracking has no such buffer: ValueError."""
+    if not kwargs.get('class_weighted'):
+        return None
+    w = getattr(head, 'class_weight', None)
+    if w is None and getattr(head, 'last_activation', None) == 'softmax':
+        raise NotImplementedError(f'class_weighted=True: {type(head).__name__} tracks no class difficulty (DESIGN 3p is built for the RetinaNet '
+                                  'heads; the SSD heads are a follow-up)')
+    if w is None:
+        raise ValueError(f"class_weighted=True needs a head that tracks the class difficulty: build {type(head).__name__} with "
+                         'bbox_head.class_difficulty=dict(xi=0.6, momentum=0.99, alpha=0.3, beta=0.2) '
+                         '(tools/train_RetinaNet.py: --class-difficulty or --uncertainty-pool PPAL)')
+    if cand is not None and w.numel() != cand.scores.shape[2]:
+        raise ValueError(f'class_weighted=True: the head holds {w.numel()} class weights, the score rows have {cand.scores.shape[2]} columns')
+    return w
+
+
 def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes, scale_factors, cfg, rescale=False, with_nms=True,
                 **kwargs):
     """Body of Lambda_L2Net._get_bboxes for `last_activation == 'relu'`.
@@ -817,6 +850,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     uPool = kwargs.get('uPool')
     if sigmoid:
         refuse_hua(head, **kwargs)
+    _class_weight(head, None, kwargs)          # (class_weighted on a head without the option: refused before the first launch)
     if isUnc and uPool == 'Entropy_NoNMS':
         raise NotImplementedError('uncertainty_pool=Entropy_NoNMS crashes in the reference too (ComputeScaleUnc with L_scores=None)')
     lam_mode = getattr(head, '_hua_lam', 'scaled')
@@ -873,7 +907,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
             thr = kwargs.get('score_thr')
             thr = 0.3 if thr is None else thr
             unc, obj_cand = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation], kwargs.get('unc_measure') or 'entropy',
-                                            kwargs.get('unc_aggregate') or 'sum', thr, want_cand=True)
+                                            kwargs.get('unc_aggregate') or 'sum', thr, want_cand=True, class_w=_class_weight(head, cand, kwargs))
             desc = object_descriptors(feats, cand, dets, labels, num, obj_cand, list(na), int(kwargs['objDesc']), thr,
                                       channels=getattr(head, 'in_channels', None))
             return (dets, labels, num, unc) + desc
@@ -883,7 +917,7 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
         # read (L_scores may be None: every head has these pools, the plain RetinaNet and the SSD heads included), no host sync
         thr = kwargs.get('score_thr')
         unc = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation], POOL_MEASURE[uPool],
-                              kwargs.get('unc_aggregate') or 'max', 0.3 if thr is None else thr)
+                              kwargs.get('unc_aggregate') or 'max', 0.3 if thr is None else thr, class_w=_class_weight(head, cand, kwargs))
         det_results = [(dets[b], labels[b]) for b in range(B)]   # zero-padded to max_per_img rows (num rows are valid)
         if kwargs.get('_return_internals'):
             return det_results, unc, dict(cand=cand, dets=dets, labels=labels, keep=keep, num=num)

@@ -836,7 +836,7 @@ int aod_loc_stability(const float* dets, const int64_t* labels, const int32_t* n
 /* ------------------------------------------------------------------ CCMS acquisition (csrc/ccms.hip, csrc/kcenter.hip, csrc/det_unc.hip):
  * pre-select the most uncertain images, then spread the picks by k-center greedy under a distance that matches objects of the same class
  * between two images (PPAL: Yang, Huang, Crowley, "Plug and Play Active Learning for Object Detection", CVPR 2024; its class-difficulty
- * EMA is not built).  No reference call site; the semantics are fixed in DESIGN 3o.
+ * EMA: the next section).  No reference call site; the semantics are fixed in DESIGN 3o.
  *   aod_det_uncertainty_ex: aod_det_uncertainty (the same arithmetic and bits; it forwards here) with obj_cand [B][max_num] int32
  *     (nullable): the candidate row matched to detection row j, -1 where the row is no object or has no candidate.
  *   aod_object_descriptors: the objects of image b are its detection rows j < num[b] with dets[b][j][4] > score_thr (strict), in row
@@ -875,6 +875,35 @@ int aod_ccms_distance(const float* feat, const int32_t* cls, const float* w, con
                       aod_stream_t stream);
 int aod_kcenter_greedy_matrix(const float* dist, int64_t N, const int64_t* labelled, int64_t n_labelled, int64_t budget, int64_t* picks,
                               float* radius, float* mind, void* ws, aod_stream_t stream);
+
+/* ------------------------------------------------------------------ class difficulty (csrc/difficulty.hip, csrc/det_unc.hip): the
+ * training-side half of PPAL's Difficulty-Calibrated Uncertainty Sampling (Yang, Huang, Crowley, CVPR 2024).  No reference call site; the
+ * semantics are fixed in DESIGN 3p.
+ *   aod_class_difficulty_accum: over the loss operands of aod_*_focal_l1_*_fwd -- cls [nrows][C] fp32 logits, labels [nrows] int64,
+ *     label_w [nrows], bbox_pred / bbox_tgt [nrows][4] fp32 deltas (16-B aligned) -- a positive is a row r with 0 <= labels[r] < C and
+ *     label_w[r] > 0; cls / bbox_pred / bbox_tgt of every other row are never read (they may hold NaN).  With c = labels[r]:
+ *       P    form 0: softmax(cls[r])[c], the maximum subtracted;  form 1: 1 / (1 + exp(-cls[r][c]))
+ *       IoU  of the boxes (centre (t0, t1), size (exp(clamp(t2)), exp(clamp(t3)))), t = delta * stds4 + means4 (HOST float[4] each), clamp
+ *            to +-|ln(wh_ratio_clip)|, for delta = bbox_pred[r] and bbox_tgt[r]:  ov / max(un, 1e-6) as in aod_loc_stability.  Both boxes
+ *            are decoded from the same anchor and IoU is unchanged by translation and per-axis scaling: no anchor is read.
+ *       q    1 - powf(P, xi) * powf(IoU, 1 - xi), 1 when P or IoU is 0, clamped to [0, 1];  0 <= xi <= 1
+ *     acc [2C] fp32: acc[c] += sum of q, acc[C + c] += count over the call's positives of class c (the count is an fp32 integer).  Several
+ *     calls add up (one per pyramid level; a rank may all-reduce acc before the update).  ws: aod_class_difficulty_ws_len(nrows, C) floats.
+ *     1 <= C <= 128; nrows == 0 is a no-op.  Two launches (block partials; one block adds them in block order), no atomics; every sum's
+ *     order depends on nrows and the row indices alone: the same inputs give the same bits on every run, eager or replayed.
+ *   aod_class_difficulty_update: for c < C with acc[C + c] > 0: d[c] = momentum * d[c] + (1 - momentum) * (acc[c] / acc[C + c]); any other
+ *     d[c] keeps its bits.  acc is zeroed.  0 <= momentum <= 1.  One launch.
+ *   aod_det_uncertainty_w: aod_det_uncertainty_ex with class_w [W] fp32 (nullable): the measure of an object row with label l is multiplied
+ *     by class_w[l] (one fp32 multiply) before it is written to obj_out and enters the aggregate.  NULL: aod_det_uncertainty_ex's bits (it
+ *     forwards here). */
+size_t aod_class_difficulty_ws_len(int64_t nrows, int C);
+int aod_class_difficulty_accum(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred, const float* bbox_tgt,
+                               int64_t nrows, int C, int form, const float* means4, const float* stds4, float wh_ratio_clip, float xi, float* acc,
+                               float* ws, aod_stream_t stream);
+int aod_class_difficulty_update(float* acc, float* d, int C, float momentum, aod_stream_t stream);
+int aod_det_uncertainty_w(const float* boxes, const float* scores, const float* dets, const int64_t* labels, const int32_t* num, int B, int n,
+                          int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc, float* obj_out,
+                          int32_t* missing, int32_t* obj_cand, const float* class_w, aod_stream_t stream);
 
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of

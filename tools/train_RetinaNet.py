@@ -37,6 +37,7 @@ saveMaxConf = False
 useMaxConf = 'False'
 score_thr = 0.3
 iou_thr = 0.9
+CLASS_DIFFICULTY = dict(xi=0.6, momentum=0.99, alpha=0.3, beta=0.2)      # PPAL's constants (--class-difficulty, --uncertainty-pool PPAL)
 
 
 def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
@@ -59,7 +60,13 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         'detection score; reads detections only, so every detector has them) '
                         '| CCMS (two-stage pick after PPAL, Yang et al., CVPR 2024: the --candidate-factor x budget most uncertain images by '
                         'the summed posterior entropy, then k-center greedy under the category-conditioned matching distance between '
-                        'their objects; RetinaNet detectors, zeroRate off)')
+                        'their objects; RetinaNet detectors, zeroRate off) '
+                        '| PPAL (CCMS with its first stage ranked by the difficulty-calibrated entropy: every detection times the weight of its '
+                        "class, from the class-difficulty EMA the head keeps while it trains; switches --class-difficulty on, zeroRate off)")
+    p.add_argument('--class-difficulty', action='store_true',
+                   help="track PPAL's per-class difficulty EMA while training (config key model.bbox_head.class_difficulty = dict(xi=0.6, "
+                        'momentum=0.99, alpha=0.3, beta=0.2)); the Entropy / Margin / LeastConf / CCMS pools then weight every detection by its '
+                        "class (class_weighted).  RetinaNet heads; each rank's EMA follows its own batches, rank 0's is used for the pool pass")
     p.add_argument('--candidate-factor', type=float, default=4.0,
                    help='CCMS pool: the candidate set holds ceil(factor x budget) of the most uncertain unlabelled images (default: 4)')
     p.add_argument('--max-objects', type=int, default=32,
@@ -150,6 +157,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
     cfg.seed, cfg.onlyEval = seed, onlyEval
     if args.bbox_head:
         cfg.model.bbox_head.type = args.bbox_head
+    if args.uncertainty_pool == 'PPAL' or args.class_difficulty:
+        cfg.model.bbox_head.class_difficulty = dict(CLASS_DIFFICULTY)
     str2unc = {'SACA': 'scaleAvg_classAvg', 'SSCS': 'scaleSum_classSum', 'SACS': 'scaleAvg_classSum', 'SSCA': 'scaleSum_classAvg'}
     if args.Unc_type:
         cfg.uncertainty_pool2 = str2unc[args.Unc_type]
@@ -275,12 +284,15 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             # Coreset and CDAL take the labelled set (their initial centers) and select by rank, not by score: their vector marks exactly
             # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
             # CCMS (uncertainty pre-selection, then k-center greedy under the object-matching distance) is handled like them
-            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS'
+            # PPAL is CCMS with the class-weighted first stage
+            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS' or cfg.uncertainty_pool == 'PPAL'
             pool_kw = dict(X_L=X_L) if coreset else {}
-            if cfg.uncertainty_pool == 'CCMS':
+            if cfg.uncertainty_pool in ('CCMS', 'PPAL'):
                 pool_kw.update(candidate_factor=args.candidate_factor, max_obj=args.max_objects)
             if cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf'):    # the posterior pools: ordinary scores, zeroRate stays on
                 pool_kw = dict(unc_aggregate=args.unc_aggregate)
+            if args.class_difficulty and cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf', 'CCMS'):
+                pool_kw['class_weighted'] = True                              # (PPAL sets it itself)
             if cfg.uncertainty_pool in ('LocStability', 'LocStability_C'):    # localization stability: ordinary scores too
                 pool_kw = dict(sigmas=args.noise_sigmas, seed=args.noise_seed)
             if coreset and zeroRate and cycle == cfg.cycles[0]:
