@@ -204,6 +204,10 @@ _SIGS = {
     'aod_class_difficulty_accum': (C.c_int, [P, P, P, P, P, I64, I32, I32, P, P, F32, F32, P, P, P]),
     'aod_class_difficulty_update': (C.c_int, [P, P, I32, F32, P]),
     'aod_det_uncertainty_w': (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P, P, P, P, P, P]),
+    'aod_consistency_max_views': (C.c_int, []),
+    'aod_flip_images': (C.c_int, [P, P, I32, I32, I32, I32, P, I32, P]),
+    'aod_det_posterior': (C.c_int, [P, P, P, I32, I32, I32, I32, P, P, P]),
+    'aod_det_consistency': (C.c_int, [P, P, P, P, I32, P, P, I32, I32, I32, I32, I32, I32, F32, I32, P, P, P, P, P, P]),
 }
 for _n, (_r, _a) in _SIGS.items():
     if hasattr(lib, _n):

@@ -117,6 +117,18 @@ class Uncertainty_fns:
         return Uncertainty_fns._loc_stability('ls+c', cfg, *args, **kwargs)
 
     @staticmethod
+    def Consistency(cfg, *args, **kwargs):
+        # prediction consistency under mirroring (Elezi et al., CVPR 2022; CALD): reads score_thr (the object gate, default 0.3),
+        # views, mode, unc_aggregate and same_class; the HUA options that calculate_uncertainty's callers pass for the Entropy_* pools have
+        # no meaning for it
+        model, dataloader = args
+        own = {k: kwargs[k] for k in ('views', 'mode', 'same_class') if kwargs.get(k) is not None}
+        if kwargs.get('unc_aggregate') is not None:
+            own['aggregate'] = kwargs['unc_aggregate']
+        thr = kwargs.get('score_thr')
+        return Consistency_uncertainty(cfg, model, dataloader, score_thr=0.3 if thr is None else thr, **own)
+
+    @staticmethod
     def Entropy_NoNMS(cfg, *args, **kwargs):
         # the reference's own Entropy_NoNMS path calls ComputeScaleUnc with L_scores=None (Lambda_L2.py:404-405,364) and raises a
         # TypeError on the first batch: there is no behaviour to reproduce
@@ -689,6 +701,73 @@ def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate=
     return getattr(Uncertainty_fns, pool)(cfg, model, data_loader, unc_aggregate=aggregate, score_thr=score_thr, **kwargs)
 
 
+def _batch_sizes(dev):
+    """sizes(metas) -> int32 [B, 2] (h, w) of a batch on the device, kept by value (a pool re-uses a handful of them)"""
+    cache = {}
+
+    def sizes(metas):
+        key = tuple((int(m['img_shape'][0]), int(m['img_shape'][1])) for m in metas)
+        hw = cache.get(key)
+        if hw is None:
+            if len(cache) > 256:
+                cache.clear()
+            hw = cache[key] = torch.tensor(key, dtype=torch.int32).to(dev)
+        return hw
+    return sizes
+
+
+def _view_stacks(who, model, pool, gscore, n_views, prep, view, fkw, kwargs):
+    """The batch loop of the pool passes that score an image by several detection forwards on copies of it (single_gpu_loc_stability: noisy
+    copies; single_gpu_consistency: mirrored copies).  Per batch: the clean forward model(return_loss=False, rescale=True, **fkw, **kwargs),
+    then per view k = 0 .. n_views - 1 one view(k, img, out, prep(img, metas), image_ids) launch into a reused scratch batch and one
+    forward; the outputs of every forward are copied into slot k + 1 of a preallocated stack (slot 0: the clean ones; a replay overwrites
+    the graph's static outputs).  Yields (stack, preps) per batch: the tuple of stacked outputs [n_views + 1, ...] and prep's value for
+    every image tensor of the batch.
+    While the batch shape repeats the n_views + 1 forwards are replays of gscore's ONE captured graph: a shape is captured when a batch
+    repeats the previous batch's shape, as in single_gpu_map.  A batch whose shape is seen for the first time (a ragged last batch, every
+    batch of a variable-shape pool) makes all its forwards eagerly, and so does a batch that is a list of several image tensors, every one
+    of which gets its own view launch."""
+    from .. import functional as AF
+    dev = pool.dev
+    stacks, scratch = {}, {}
+    for idxs, image_ids, data in pool.batches(to_device=True):          # the n_views + 1 forwards read the one device tensor
+        # the batch as the model takes it: a list of image tensors (one entry; test-time augmentation lists have more) and their metas
+        listed = isinstance(data['img'], (list, tuple))
+        imgs = list(data['img']) if listed else [data['img']]
+        metas = list(data['img_metas']) if listed else [data['img_metas']]
+        if len(imgs) != len(metas) or not all(torch.is_tensor(t) and t.dim() == 4 for t in imgs):
+            raise ValueError(f'{who}: a batch must hold [B, C, H, W] image tensors, one list of metas for each')
+        imgs = [t.to(dev, non_blocking=True).float().contiguous() for t in imgs]      # (a one-tensor batch is on the device already)
+        preps = [prep(t, m) for t, m in zip(imgs, metas)]
+        g = None
+        if gscore is not None and _single(data):
+            gkey = (tuple(imgs[0].shape), AF.mode_key())
+            if gkey in gscore.cache or gkey == gscore.pending:
+                g = gscore
+            else:
+                gscore.pending = gkey
+        stack = None
+        for k in range(-1, n_views):
+            xs = imgs
+            if k >= 0:
+                xs = []
+                for a, (t, p) in enumerate(zip(imgs, preps)):
+                    out = scratch.get((a, tuple(t.shape)))
+                    if out is None:
+                        out = scratch[(a, tuple(t.shape))] = torch.empty_like(t)
+                    xs.append(view(k, t, out, p, image_ids))
+            d = dict(data, img=xs if listed else xs[0])
+            outs = _replay_or_eager(g, d, image_ids, lambda: model(return_loss=False, rescale=True, **fkw, **d, **kwargs))
+            if stack is None:
+                key = tuple((tuple(t.shape), t.dtype) for t in outs)
+                stack = stacks.get(key)
+                if stack is None:
+                    stack = stacks[key] = tuple(torch.empty((n_views + 1,) + tuple(t.shape), dtype=t.dtype, device=dev) for t in outs)
+            for dst, t in zip(stack, outs):
+                dst[k + 1].copy_(t)
+        yield stack, preps
+
+
 def _noise_inv_std(img_metas, channels):
     """1 / std_c of a batch's normalisation in the tensor's channel order (img_metas[...]['img_norm_cfg']['std']; a meta without one was
     not normalised by the pipeline: std 1, Collect's own default).  One value for the whole batch, else ValueError."""
@@ -736,7 +815,6 @@ def single_gpu_loc_stability(model, data_loader, sigmas=(8, 16, 24, 32, 40, 48),
     tensors, every one of which gets its own noise launch (the detectors here refuse such test-time augmentation lists themselves).  It
     needs nothing but detections, so every detector has it.  An image's score is a function of (weights, image, seed, image id, sigmas) only: the same bits
     alone, in any batch, on any rank count, eager or replayed."""
-    from .. import functional as AF
     from .. import hipops as ho
     from ..scoring import LOCSTAB_COMBINES, loc_stability
     sigmas = _check_sigmas(sigmas)
@@ -751,60 +829,16 @@ def single_gpu_loc_stability(model, data_loader, sigmas=(8, 16, 24, 32, 40, 48),
     dev = next(model.parameters()).device
     pool = _PoolPass(data_loader, dev)
     gscore = _graphed(model, dev, ('eval_padded',), kwargs, isEval=True, _padded=True)
-    K = len(sigmas)
-    chunks, stacks, scratch, hw_cache = [], {}, {}, {}
+    sizes, chunks = _batch_sizes(dev), []
 
-    def sizes(metas):
-        """int32 [B, 2] (h, w) of a batch on the device, kept by value (a pool re-uses a handful of them)"""
-        key = tuple((int(m['img_shape'][0]), int(m['img_shape'][1])) for m in metas)
-        hw = hw_cache.get(key)
-        if hw is None:
-            if len(hw_cache) > 256:
-                hw_cache.clear()
-            hw = hw_cache[key] = torch.tensor(key, dtype=torch.int32).to(dev)
-        return hw
+    def prep(t, metas):
+        return _noise_inv_std(metas, int(t.shape[1])), sizes(metas)
 
-    for idxs, image_ids, data in pool.batches(to_device=True):          # the K + 1 forwards read the one device tensor
-        # the batch as the model takes it: a list of image tensors (one entry; test-time augmentation lists have more) and their metas
-        listed = isinstance(data['img'], (list, tuple))
-        imgs = list(data['img']) if listed else [data['img']]
-        metas = list(data['img_metas']) if listed else [data['img_metas']]
-        if len(imgs) != len(metas) or not all(torch.is_tensor(t) and t.dim() == 4 for t in imgs):
-            raise ValueError('single_gpu_loc_stability: a batch must hold [B, C, H, W] image tensors, one list of metas for each')
-        imgs = [t.to(dev, non_blocking=True).float().contiguous() for t in imgs]      # (a one-tensor batch is on the device already)
-        prep = [(_noise_inv_std(m, int(t.shape[1])), sizes(m)) for t, m in zip(imgs, metas)]
-        # the graph serves a batch whose shape it has captured, or captures one that repeats the previous batch's shape (as single_gpu_map
-        # does); a shape seen for the first time -- a ragged last batch, every batch of a variable-shape pool -- runs its K + 1 forwards
-        # eagerly, and so does a list batch
-        g = None
-        if gscore is not None and _single(data):
-            gkey = (tuple(imgs[0].shape), AF.mode_key())
-            if gkey in gscore.cache or gkey == gscore.pending:
-                g = gscore
-            else:
-                gscore.pending = gkey
-        stack = None
-        for k in range(-1, K):
-            xs = imgs
-            if k >= 0:
-                xs = []
-                for a, (t, (inv_std, hw)) in enumerate(zip(imgs, prep)):
-                    noisy = scratch.get((a, tuple(t.shape)))
-                    if noisy is None:
-                        noisy = scratch[(a, tuple(t.shape))] = torch.empty_like(t)
-                    xs.append(ho.pixel_noise(t, noisy, hw, inv_std, sigmas[k], k, seed, image_ids))
-            d = dict(data, img=xs if listed else xs[0])
-            dets, labels, num = _replay_or_eager(g, d, image_ids,
-                                                 lambda: model(return_loss=False, rescale=True, isEval=True, _padded=True, **d, **kwargs))
-            if stack is None:
-                key = (int(dets.shape[0]), int(dets.shape[1]))
-                stack = stacks.get(key)
-                if stack is None:
-                    stack = stacks[key] = (torch.empty((K + 1,) + tuple(dets.shape), dtype=torch.float32, device=dev),
-                                           torch.empty((K + 1,) + tuple(labels.shape), dtype=torch.int64, device=dev),
-                                           torch.empty((K + 1,) + tuple(num.shape), dtype=torch.int32, device=dev))
-            # (a replay overwrites the graph's static outputs: every forward is copied out)
-            stack[0][k + 1].copy_(dets), stack[1][k + 1].copy_(labels), stack[2][k + 1].copy_(num)
+    def noisy(k, t, out, p, image_ids):
+        return ho.pixel_noise(t, out, p[1], p[0], sigmas[k], k, seed, image_ids)
+
+    for stack, _ in _view_stacks('single_gpu_loc_stability', model, pool, gscore, len(sigmas), prep, noisy, dict(isEval=True, _padded=True),
+                                 kwargs):
         chunks.append(loc_stability(*stack, score_thr=score_thr, same_class=same_class, combine=combine))
     return pool.gather(pool.cat(chunks))
 
@@ -814,6 +848,95 @@ def LocStability_uncertainty(cfg, model, data_loader, **kwargs):
     same_class, combine 'ls' | 'ls+c').  Larger scores are selected first; these are ordinary scores, zeroRate stays on.  The config is not
     read.  Returns the CPU [N] fp32 vector."""
     return single_gpu_loc_stability(model, data_loader, **kwargs).cpu()
+
+
+def _frame_extent(img_metas):
+    """(w / scale_x, h / scale_y) of every image of a batch in Python floats: the extent of the frame that rescaled detections lie in
+    (img_shape (h, w, ...), scale_factor (sx, sy, sx, sy) or one number; a meta without a scale factor was not resized: 1)"""
+    out = []
+    for m in img_metas:
+        h, w = float(m['img_shape'][0]), float(m['img_shape'][1])
+        sf = m.get('scale_factor') if hasattr(m, 'get') else None
+        sf = np.ones(2, np.float64) if sf is None else np.asarray(sf, np.float64).reshape(-1)
+        sx, sy = (float(sf[0]), float(sf[1])) if sf.size >= 2 else (float(sf[0]), float(sf[0]))
+        if not (sx > 0.0 and sy > 0.0 and sx != float('inf') and sy != float('inf')):
+            raise ValueError(f'single_gpu_consistency: scale_factor {sf.tolist()} does not hold finite positive values')
+        out.append((w / sx, h / sy))
+    return tuple(out)
+
+
+@torch.no_grad()
+def single_gpu_consistency(model, data_loader, views=('hflip',), mode='both', aggregate='max', score_thr=0.3, same_class=False, _stats=None,
+                           **kwargs):
+    """Prediction consistency under mirroring (I. Elezi et al., "Not All Labels Are Equal: Rationalizing the Labeling Costs for Training
+    Object Detection", CVPR 2022; CALD: W. Yu et al., "Consistency-based Active Learning for Object Detection", CVPR Workshops 2022; DESIGN
+    3q; the reference has none) on _PoolPass's loop: the pool is sharded over the ranks, batches come from the prefetch workers through
+    pinned memory (one H2D copy per batch), the scores stay on the device and are gathered once.  Returns a [N] fp32 tensor identical on
+    every rank.
+
+    Per batch: the clean detection forward (isEval=True, padded outputs, detPost=True: the detections and the class-posterior row of every
+    one), then per view one aod_flip_images launch into a reused scratch batch (the image mirrored inside its img_shape, the pad left where
+    the collate put it; the metas are passed unchanged) and one forward; the five outputs are copied into slot v of a preallocated stack
+    after every forward, then ONE scoring.det_consistency launch: the views' boxes are mapped back into the rescaled frame of extent
+    (w / scale_x, h / scale_y), every clean detection above score_thr is matched to the box of largest IoU of every view, and the image is
+    scored by 1 - IoU (mode 'box'), the Jensen-Shannon divergence of the two posterior rows ('cls') or their mean ('both'), averaged over the
+    views and aggregated over the detections by max / mean / sum.  While the batch shape repeats (and AOD_HIP_GRAPH != 0) the V + 1 forwards
+    are V + 1 replays of ONE captured graph under its own key ('eval_post',): a shape is captured when a batch repeats the previous batch's
+    shape, as in single_gpu_map.  A batch whose shape is seen for the first time makes all its V + 1 forwards eagerly, and so does a batch
+    that is a list of several image tensors, every one of which gets its own flip launch.  It needs nothing but detections and their score
+    rows, so every detector has it.  An image's score is a function of (weights, image, metas, views, options) only: the same bits alone, in
+    any batch, on any rank count, eager or replayed.  _stats (a dict): receives 'missing', the [N] count of detections without a posterior
+    row (always 0)."""
+    from .. import hipops as ho
+    from ..scoring import ACTIVATION_LAYOUT, CONSISTENCY_MODES, UNC_AGGREGATES, consistency_views, det_consistency
+    views = tuple(views) if isinstance(views, (list, tuple)) else views
+    consistency_views(views, 'single_gpu_consistency')
+    if mode not in CONSISTENCY_MODES:
+        raise ValueError(f"single_gpu_consistency: unknown mode {mode!r} (expected 'box', 'cls' or 'both')")
+    if aggregate not in UNC_AGGREGATES:
+        raise ValueError(f"single_gpu_consistency: unknown aggregate {aggregate!r} (expected 'max', 'mean' or 'sum')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('single_gpu_consistency: score_thr is NaN')
+    kwargs.setdefault('isUnc', False)
+    model.eval()
+    dev = next(model.parameters()).device
+    module = getattr(model, 'module', model)
+    layout = ACTIVATION_LAYOUT[getattr(getattr(module, 'bbox_head', module), 'last_activation')]
+    pool = _PoolPass(data_loader, dev)
+    gscore = _graphed(model, dev, ('eval_post',), kwargs, isEval=True, _padded=True, detPost=True)
+    sizes, ext_cache, chunks, miss_chunks = _batch_sizes(dev), {}, [], []
+
+    def prep(t, metas):
+        """(int32 [B, 2] (h, w), fp32 [B, 2] extent (w, h)) of a batch on the device, the extents kept by value like the sizes"""
+        key = _frame_extent(metas)
+        ext = ext_cache.get(key)
+        if ext is None:
+            if len(ext_cache) > 256:
+                ext_cache.clear()
+            ext = ext_cache[key] = torch.tensor(key, dtype=torch.float32).to(dev)
+        return sizes(metas), ext
+
+    def mirrored(v, t, out, p, image_ids):
+        return ho.flip_images(t, out, p[0], views[v])
+
+    for stack, preps in _view_stacks('single_gpu_consistency', model, pool, gscore, len(views), prep, mirrored,
+                                     dict(isEval=True, _padded=True, detPost=True), kwargs):
+        ext = preps[0][1]                 # (rescaled detections of every entry of a list batch lie in the one original frame)
+        chunks.append(det_consistency(*stack[:4], views, ext, layout, mode=mode, aggregate=aggregate, score_thr=score_thr,
+                                      same_class=same_class))
+        if _stats is not None:
+            miss_chunks.append(stack[4].sum(0).float())
+    if _stats is not None:
+        _stats['missing'] = pool.gather(pool.cat(miss_chunks))
+    return pool.gather(pool.cat(chunks))
+
+
+def Consistency_uncertainty(cfg, model, data_loader, **kwargs):
+    """Consistency acquisition in the form update_X_L takes (single_gpu_consistency; kwargs: views, mode 'both' | 'box' | 'cls', aggregate
+    'max' | 'mean' | 'sum', score_thr, same_class).  Larger scores are selected first; these are ordinary scores, zeroRate stays on.  The
+    config is not read.  Returns the CPU [N] fp32 vector."""
+    return single_gpu_consistency(model, data_loader, **kwargs).cpu()
 
 
 @torch.no_grad()

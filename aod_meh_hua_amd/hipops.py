@@ -1136,3 +1136,39 @@ def pixel_noise(src, dst, hw, inv_std, sigma, level, seed, image_ids):
     call('aod_pixel_noise', ptr(src), ptr(dst), B, Cc, Hp, Wp, ptr(hw), (C.c_float * Cc)(*inv_std), sigma, int(level),
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(image_ids), stream())
     return dst
+
+
+FLIP_VIEWS = {'hflip': 1, 'vflip': 2, 'hvflip': 3}      # flip codes: bit 0 horizontal, bit 1 vertical
+
+
+def flip_code(view, who='flip_images'):
+    """the flip code of a view name ('hflip' | 'vflip' | 'hvflip') or of a code 1..3"""
+    if isinstance(view, str) and view in FLIP_VIEWS:
+        return FLIP_VIEWS[view]
+    if isinstance(view, int) and not isinstance(view, bool) and 1 <= view <= 3:
+        return view
+    raise ValueError(f"{who}: unknown view {view!r} (expected 'hflip', 'vflip', 'hvflip' or a flip code 1..3)")
+
+
+def flip_images(src, dst, hw, view):
+    """dst = the mirrored copy of src inside every image's img_shape, src's bits in the pad (aod_flip_images): the views of the
+    consistency pool.  src, dst: contiguous fp32 [B, C, Hp, Wp] on the device, out of place, any Wp; hw: device int32 [B, 2] (h, w) per
+    image; view: 'hflip' | 'vflip' | 'hvflip' or its code (bit 0 horizontal, bit 1 vertical).  A bit copy: nothing is computed."""
+    for name, t in (('src', src), ('dst', dst)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+            raise ValueError(f'flip_images: {name} must be a contiguous fp32 [B, C, Hp, Wp] tensor')
+    if tuple(dst.shape) != tuple(src.shape):
+        raise ValueError(f'flip_images: dst has shape {tuple(dst.shape)}, src {tuple(src.shape)}')
+    B, Cc, Hp, Wp = (int(v) for v in src.shape)
+    if not (1 <= B <= 65535 and 1 <= Cc <= 65535):
+        raise ValueError(f'flip_images: a batch and a channel count in 1..65535 are needed, got {tuple(src.shape)}')
+    if not (1 <= Hp <= 65536 and 1 <= Wp <= 262144):
+        raise ValueError(f'flip_images: padded size {Hp} x {Wp}: 1 <= Hp <= 65536 and 1 <= Wp <= 262144 are needed')
+    code = flip_code(view)
+    if not (torch.is_tensor(hw) and hw.dtype == torch.int32 and tuple(hw.shape) == (B, 2) and hw.is_contiguous()):
+        raise ValueError(f'flip_images: hw must be a contiguous int32 [{B}, 2] tensor')
+    a, b, n = src.data_ptr(), dst.data_ptr(), 4 * src.numel()
+    if a == b or (a < b + n and b < a + n):
+        raise ValueError('flip_images: dst == src (or overlaps it): the kernel is out of place')
+    call('aod_flip_images', ptr(src), ptr(dst), B, Cc, Hp, Wp, ptr(hw), code, stream())
+    return dst

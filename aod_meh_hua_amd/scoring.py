@@ -788,6 +788,106 @@ def loc_stability(dets, labels, num, score_thr=0.3, same_class=False, combine='l
     return (unc, stab) if want_objects else unc
 
 
+from .hipops import FLIP_VIEWS as CONSISTENCY_VIEWS      # noqa: E402  ('hflip': 1, 'vflip': 2, 'hvflip': 3: bit 0 horizontal, bit 1 vertical)
+CONSISTENCY_MODES = {'box': 0, 'cls': 1, 'both': 2}
+CONSISTENCY_MAX_VIEWS = int(_C.lib.aod_consistency_max_views())      # (written once, in csrc/consistency.hip)
+
+
+def consistency_views(views, who='det_consistency'):
+    """the flip codes of `views`, a sequence of 1..CONSISTENCY_MAX_VIEWS distinct view names; ValueError otherwise"""
+    if isinstance(views, str) or not hasattr(views, '__iter__'):
+        raise ValueError(f"{who}: views must be a sequence of view names, got {views!r}")
+    views = tuple(views)
+    if not 1 <= len(views) <= CONSISTENCY_MAX_VIEWS:
+        raise ValueError(f'{who}: 1..{CONSISTENCY_MAX_VIEWS} views are supported, got {len(views)}')
+    for v in views:
+        if not isinstance(v, str) or v not in CONSISTENCY_VIEWS:
+            raise ValueError(f"{who}: unknown view {v!r} (expected 'hflip', 'vflip' or 'hvflip')")
+    if len(set(views)) != len(views):
+        raise ValueError(f'{who}: the views must be distinct, got {views}')
+    return [CONSISTENCY_VIEWS[v] for v in views]
+
+
+def det_posterior(cand, dets, labels, num):
+    """The class-posterior row of every detection of a batch (aod_det_posterior): post [B, max_num, W] fp32 with
+    post[b, j] = cand.scores[b, k] for the candidate row k that detection j < num[b] was made of -- looked up by its box and score bits
+    with the one lookup of det_uncertainty (score_thr = -inf: every row j < num) --, zero rows elsewhere (every word is written: a replayed
+    graph never exposes stale rows).  Returns (post, missing [B] int32: the rows j < num[b] without a candidate row, always 0 behind
+    multiclass_nms_batch).  Two launches, no host sync."""
+    _, obj_cand = det_uncertainty(cand, dets, labels, num, 'cat_bg', 'entropy', 'sum', float('-inf'), want_cand=True)
+    scores = cand.scores
+    B, n, W = (int(v) for v in scores.shape)
+    max_num = int(dets.shape[1])
+    post = torch.empty(B, max_num, W, dtype=torch.float32, device=scores.device)
+    missing = torch.empty(B, dtype=torch.int32, device=scores.device)
+    call('aod_det_posterior', ptr(scores), ptr(obj_cand), ptr(num), B, n, W, max_num, ptr(post), ptr(missing), stream())
+    return post, missing
+
+
+def det_consistency(dets, labels, num, post, views, ext, layout, mode='both', aggregate='max', score_thr=0.3, same_class=False,
+                    want_objects=False, want_parts=False):
+    """Prediction consistency under mirroring of every image of a batch (aod_det_consistency; Elezi et al., CVPR 2022; CALD, Yu
+    et al., CVPRW 2022): how much the detections of the image and of its mirrored views disagree, in box position and in class posterior.
+
+    dets [V+1, B, max_num, 5] fp32, labels [V+1, B, max_num] int64, num [V+1, B] int32, post [V+1, B, max_num, W] fp32: the stacked padded
+    detections and their posterior rows (det_posterior), slot 0 of the clean batch, slot v + 1 of the view views[v] ('hflip' | 'vflip' |
+    'hvflip', distinct, 1 <= V <= 3); 1 <= max_num <= 1024.  ext [B, 2] fp32: the extent (w, h) of the frame the boxes lie in; a view's boxes
+    are mapped back into it first.  A row j < num[0][b] of slot 0 with a score > score_thr (strict) is an object; per view it is matched to
+    the un-flipped row of largest IoU (same_class: rows of its label only; none, or IoU 0: iou 0, js 1) and js is the Jensen-Shannon
+    divergence in bits of the two posterior rows under `layout` ('cat' | 'cat_bg' | 'sigmoid': UNC_LAYOUTS).  mode 'box': u = 1 - iou,
+    'cls': js, 'both': their mean; averaged over the views, then max / mean / sum over the image's objects; an image without one scores 0.
+    Returns unc [B] fp32 on the device (no host sync); with want_objects also obj [B, max_num] (u_j, NaN where the row is no object); with
+    want_parts also (iou, js, match): [V, B, max_num] fp32 / fp32 / int32 (NaN / NaN / -1 where the row is no object)."""
+    codes = consistency_views(views)
+    if layout not in UNC_LAYOUTS:
+        raise ValueError(f"det_consistency: unknown layout {layout!r} (expected 'cat', 'cat_bg' or 'sigmoid')")
+    if mode not in CONSISTENCY_MODES:
+        raise ValueError(f"det_consistency: unknown mode {mode!r} (expected 'box', 'cls' or 'both')")
+    if aggregate not in UNC_AGGREGATES:
+        raise ValueError(f"det_consistency: unknown aggregate {aggregate!r} (expected 'max', 'mean' or 'sum')")
+    score_thr = float(score_thr)
+    if score_thr != score_thr:
+        raise ValueError('det_consistency: score_thr is NaN')
+    for name, t, dt, nd in (('dets', dets, torch.float32, 4), ('labels', labels, torch.int64, 3), ('num', num, torch.int32, 2),
+                            ('post', post, torch.float32, 4), ('ext', ext, torch.float32, 2)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"det_consistency: {name} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'det_consistency: {name} is not contiguous; no copy is made here')
+    V1, B, max_num, five = (int(v) for v in dets.shape)
+    if V1 - 1 != len(codes):
+        raise ValueError(f'det_consistency: dets holds {V1} slots, {len(codes)} views need {len(codes) + 1} (the clean one and one per view)')
+    if B < 1 or five != 5 or not 1 <= max_num <= UNC_MAX_DET:
+        raise ValueError(f'det_consistency: dets has shape {tuple(dets.shape)}: expected (V + 1, B, max_num, 5) with B >= 1 and '
+                         f'1 <= max_num <= {UNC_MAX_DET}')
+    if tuple(labels.shape) != (V1, B, max_num):
+        raise ValueError(f'det_consistency: labels has shape {tuple(labels.shape)}, expected ({V1}, {B}, {max_num})')
+    if tuple(num.shape) != (V1, B):
+        raise ValueError(f'det_consistency: num has shape {tuple(num.shape)}, expected ({V1}, {B})')
+    if tuple(post.shape[:3]) != (V1, B, max_num) or post.shape[3] < 2:
+        raise ValueError(f'det_consistency: post has shape {tuple(post.shape)}, expected ({V1}, {B}, {max_num}, W) with W >= 2')
+    if tuple(ext.shape) != (B, 2):
+        raise ValueError(f'det_consistency: ext has shape {tuple(ext.shape)}, expected ({B}, 2)')
+    ts = (dets, labels, num, post, ext)
+    for t in ts:
+        if not t.is_cuda:
+            raise _cpu_refusal('det_consistency')
+    dev = dets.device
+    if any(t.device != dev for t in ts):
+        raise ValueError(f'det_consistency: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+    V, W = V1 - 1, int(post.shape[3])
+    unc = torch.empty(B, dtype=torch.float32, device=dev)
+    obj = torch.empty(B, max_num, dtype=torch.float32, device=dev) if want_objects else None
+    iou = torch.empty(V, B, max_num, dtype=torch.float32, device=dev) if want_parts else None
+    js = torch.empty(V, B, max_num, dtype=torch.float32, device=dev) if want_parts else None
+    match = torch.empty(V, B, max_num, dtype=torch.int32, device=dev) if want_parts else None
+    call('aod_det_consistency', ptr(dets), ptr(labels), ptr(num), ptr(post), V, (C.c_int32 * V)(*codes), ptr(ext), B, max_num, W,
+         UNC_LAYOUTS[layout], CONSISTENCY_MODES[mode], UNC_AGGREGATES[aggregate], score_thr, 1 if same_class else 0, ptr(unc), ptr(obj),
+         ptr(iou), ptr(js), ptr(match), stream())
+    out = (unc,) + ((obj,) if want_objects else ()) + ((iou, js, match) if want_parts else ())
+    return out if len(out) > 1 else unc
+
+
 HUA_POOLS = ('Entropy_NMS', 'Entropy_ALL', 'Entropy_Avg')
 
 
@@ -824,6 +924,9 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
 
     isEval=True (detection for mAP)  -> list of (det_bboxes [k,5], det_labels [k]) per image;
                  with _padded=True   -> (dets [B,max,5], labels [B,max] int64, num [B] int32) on the device, no host sync;
+                 with _padded=True, detPost=True -> (dets, labels, num, post [B,max,W] fp32, missing [B] int32): the same triple
+                                        and det_posterior's outputs, the class-posterior row of every detection (zero rows >= num);
+                                        ValueError together with objDesc or detUnc
                  with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
     hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / Entropy_Avg / detUnc paths.
@@ -898,6 +1001,12 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
         # device metric (apis/test.py single_gpu_map): the padded triple stays on the device -- no num.cpu(), graph-capturable
         if kwargs.get('detUnc'):
             raise ValueError('detUnc is not offered with the padded evaluation outputs')
+        if kwargs.get('detPost'):
+            # consistency pool (apis/test.py single_gpu_consistency): the posterior row of every detection behind the NMS kernel
+            # -- the lookup of det_uncertainty over every row j < num, then the gather; two launches, no host sync
+            if kwargs.get('objDesc'):
+                raise ValueError('detPost is not offered together with objDesc: the two options return different tuples')
+            return (dets, labels, num) + det_posterior(cand, dets, labels, num)
         if kwargs.get('objDesc'):
             # CCMS object descriptors (apis/test.py single_gpu_object_descriptors): two launches behind the NMS kernel -- the
             # stage-1 posterior score, which also hands out the matched candidate rows, and the gather from the neck outputs; no host sync

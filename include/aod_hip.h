@@ -905,6 +905,46 @@ int aod_det_uncertainty_w(const float* boxes, const float* scores, const float* 
                           int W, int max_num, int layout, int measure, int aggregate, float score_thr, float* unc, float* obj_out,
                           int32_t* missing, int32_t* obj_cand, const float* class_w, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ Consistency acquisition (csrc/consistency.hip): detect on the image and
+ * on mirrored copies, map the boxes back, score the image by how much the detection lists disagree in box position and in class posterior
+ * (Elezi, Yu, Anandkumar, Leal-Taixe, Alvarez, "Not All Labels Are Equal: Rationalizing the Labeling Costs for Training Object Detection",
+ * CVPR 2022; CALD: Yu, Zhu, Yang, Chen, "Consistency-based Active Learning for Object Detection", CVPR Workshops 2022).  No reference call
+ * site; the semantics are fixed in DESIGN 3q.  Flip codes: bit 0 horizontal, bit 1 vertical (1 hflip, 2 vflip, 3 hvflip).
+ *   aod_flip_images: src, dst fp32 [B][C][Hp][Wp] (the padded model input), out of place (dst == src or overlapping: refused); any Wp >= 1.
+ *     hw [B][2] int32 (device): img_shape (h, w) per image, clamped to Hp / Wp.  dst[b][c][y][x] = src[b][c][fy ? h-1-y : y][fx ? w-1-x : x]
+ *     for y < h and x < w, src's bits elsewhere (the pad stays where the collate put it): a bit copy, nothing is computed.  16-B stores when
+ *     Wp % 4 == 0 and both buffers are 16-B aligned, one element per thread otherwise; the same bits either way.  flip in {1, 2, 3}.
+ *   aod_det_posterior: scores [B][n][W] (the candidates' score rows), obj_cand [B][max_num] int32 (aod_det_uncertainty_ex's, called with
+ *     score_thr = -inf so that every row j < num[b] is looked up), num [B].  post [B][max_num][W]: post[b][j][:] = scores[b][obj_cand[b][j]][:]
+ *     for j < num[b] with a candidate row (0 <= obj_cand < n), zero rows elsewhere -- every word of post is written; missing [B] (nullable):
+ *     the rows j < num[b] without one.
+ *   aod_det_consistency: the stacked slots dets [V+1][B][max_num][5], labels [V+1][B][max_num] int64, num [V+1][B], post [V+1][B][max_num][W]:
+ *     slot 0 the clean detections, slot v + 1 those of view v; flips: V HOST codes; ext [B][2] fp32 (device): the extent (w, h) of the frame
+ *     the boxes lie in (rescaled detections: (w / scale_x, h / scale_y)).  1 <= V <= 3, 1 <= max_num <= 1024, W >= 2.
+ *     Row j of slot 0 is an object iff j < num[0][b] and dets[0][b][j][4] > score_thr (strict).  A view box is un-flipped first:
+ *     horizontal x1' = ext_w - x2, x2' = ext_w - x1, vertical likewise with ext_h (one fp32 subtraction each); scores and labels unchanged.
+ *     match_jv = argmax of the IoU over the un-flipped rows i < num[v+1][b] (same_class = 1: rows with j's label only), lowest index on a tie,
+ *       iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih likewise, ov = iw * ih, un = area_a + area_b - ov, IoU = ov / max(un, 1e-6)
+ *     (aod_loc_stability's form).  No such row, or a best IoU of 0: match -1, iou_jv = 0, js_jv = 1.  Otherwise, with p = post[0][b][j] and
+ *     q = post[v+1][b][match], t(a, b) = [a > 0] a (ln a - ln m) + [b > 0] b (ln b - ln m), m = (a + b) / 2 (>= 0; exactly 0 for equal bits; a
+ *     term whose m rounds to 0 -- a + b = 2^-149 -- is taken as 0):
+ *       layout 0 (cat: the first W - 1 columns) / 1 (cat_bg: all W): js = (sum_c t(p_c, q_c) / 2) / ln 2, the columns added in order;
+ *       layout 2 (sigmoid: the first W - 1 columns, independent Bernoulli): js = (sum_c (t(p_c, q_c) + t(1 - p_c, 1 - q_c)) / 2 / used) / ln 2.
+ *     mode 0 (box): u_jv = 1 - iou_jv; 1 (cls): js_jv; 2 (both): ((1 - iou_jv) + js_jv) / 2.  u_j = (u_j0 + ... + u_j,V-1) / V, the views
+ *     added in order.  aggregate 0 / 1 / 2: unc[b] = max / mean / sum of u_j over the objects; an image without one scores 0.
+ *     Nullable outputs: obj_out [B][max_num] (u_j), iou_out / js_out [V][B][max_num]: NaN where the row is no object; match_out
+ *     [V][B][max_num] int32: -1 where unmatched or no object.  Rows >= num of any slot are never read.
+ *     One launch, one workgroup per image, no atomics, no workspace, no host sync.  The aggregate runs in a pairwise tree over the next power
+ *     of two >= max_num (rows that are no object hold 0): a function of j and max_num alone, so an image has the same score bits alone, at
+ *     any position of any batch, eager or replayed. */
+int aod_consistency_max_views(void); /* 3: the largest V of aod_det_consistency */
+int aod_flip_images(const float* src, float* dst, int B, int C, int Hp, int Wp, const int32_t* hw, int flip, aod_stream_t stream);
+int aod_det_posterior(const float* scores, const int32_t* obj_cand, const int32_t* num, int B, int n, int W, int max_num, float* post,
+                      int32_t* missing, aod_stream_t stream);
+int aod_det_consistency(const float* dets, const int64_t* labels, const int32_t* num, const float* post, int V, const int32_t* flips,
+                        const float* ext, int B, int max_num, int W, int layout, int mode, int aggregate, float score_thr, int same_class,
+                        float* unc, float* obj_out, float* iou_out, float* js_out, int32_t* match_out, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

@@ -58,6 +58,10 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         '| LocStability | LocStability_C (localization stability, Kao et al., ACCV 2018: how far the boxes of the clean '
                         'detections move under Gaussian pixel noise of the strengths --noise-levels; LocStability_C adds 1 - the largest '
                         'detection score; reads detections only, so every detector has them) '
+                        '| Consistency (prediction consistency under mirroring, Elezi et al., CVPR 2022, and CALD, Yu et al., CVPRW 2022: '
+                        'detect on the image and on the mirrored copies --consistency-views, map the boxes back and score the disagreement '
+                        'in box position and class posterior, --consistency-mode, aggregated per image by --unc-aggregate; every detector '
+                        'has it) '
                         '| CCMS (two-stage pick after PPAL, Yang et al., CVPR 2024: the --candidate-factor x budget most uncertain images by '
                         'the summed posterior entropy, then k-center greedy under the category-conditioned matching distance between '
                         'their objects; RetinaNet detectors, zeroRate off) '
@@ -75,8 +79,13 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                    help='noise strengths of the LocStability pools: up to 16 comma-separated standard deviations in 0..255 pixel units '
                         '(default: 8,16,24,32,40,48)')
     p.add_argument('--noise-seed', type=int, default=0, help='seed of the pixel noise of the LocStability pools (default: 0)')
+    p.add_argument('--consistency-views', default='hflip',
+                   help='views of the Consistency pool: 1..3 distinct comma-separated names of hflip, vflip, hvflip (default: hflip)')
+    p.add_argument('--consistency-mode', default='both',
+                   help='what the Consistency pool scores: box (1 - IoU of the matched boxes), cls (Jensen-Shannon divergence of their class '
+                        'posteriors) or both (their mean; default)')
     p.add_argument('--unc-aggregate', choices=['max', 'mean', 'sum'], default='max',
-                   help="how the Entropy / Margin / LeastConf pools aggregate an image's per-detection values (default: max)")
+                   help="how the Entropy / Margin / LeastConf / Consistency pools aggregate an image's per-detection values (default: max)")
     p.add_argument('--hua-score-thr', type=float, default=score_thr,
                    help='score_thr handed to calculate_uncertainty; read by Lambda_L2Net_ablation / Lambda_L2Net_NoL, as the region '
                         'threshold by the CDAL pool, and as the object gate by the Entropy / Margin / LeastConf pools')
@@ -117,6 +126,14 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     from aod_meh_hua_amd.scoring import LOCSTAB_MAX_LEVELS
     if not 1 <= len(args.noise_sigmas) <= LOCSTAB_MAX_LEVELS or not all(0.0 <= s < float('inf') for s in args.noise_sigmas):
         p.error(f'--noise-levels: 1..{LOCSTAB_MAX_LEVELS} finite values >= 0 are needed, got {args.noise_levels!r}')
+    from aod_meh_hua_amd.scoring import CONSISTENCY_MODES, consistency_views
+    args.consistency_view_names = tuple(s.strip() for s in args.consistency_views.split(',') if s.strip())
+    try:
+        consistency_views(args.consistency_view_names, '--consistency-views')
+    except ValueError as e:
+        p.error(str(e))
+    if args.consistency_mode not in CONSISTENCY_MODES:
+        p.error(f"--consistency-mode: {args.consistency_mode!r} is none of 'both', 'box', 'cls'")
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
 
@@ -295,6 +312,8 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
                 pool_kw['class_weighted'] = True                              # (PPAL sets it itself)
             if cfg.uncertainty_pool in ('LocStability', 'LocStability_C'):    # localization stability: ordinary scores too
                 pool_kw = dict(sigmas=args.noise_sigmas, seed=args.noise_seed)
+            if cfg.uncertainty_pool == 'Consistency':                         # prediction consistency under mirroring: ordinary scores too
+                pool_kw = dict(views=args.consistency_view_names, mode=args.consistency_mode, unc_aggregate=args.unc_aggregate)
             if coreset and zeroRate and cycle == cfg.cycles[0]:
                 logger.info(f'uncertainty_pool={cfg.uncertainty_pool}: zeroRate {zeroRate} -> 0 (the picks are the selection)')
             with torch.no_grad():
