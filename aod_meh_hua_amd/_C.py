@@ -132,6 +132,11 @@ _SIGS = {
     'aod_loss_levels_partials_len': (SZ, [I32, P]),
     'aod_edl_focal_l1_levels_fwd': (C.c_int, [P, P, P, P, P, P, I32, P, I32, F32, F32, P, P, P, P, I32, P, P, P]),
     'aod_edl_focal_l1_levels_bwd': (C.c_int, [P, P, P, P, P, P, I32, P, I32, F32, F32, P, P, P, P, P, I32, I32, I32, I32, P]),
+    # (focal form, box form, box eps, box linear, means4, stds4, wh_ratio_clip) in front of the arguments of the entries above
+    'aod_focal_box_fwd_ex': (C.c_int, [I32, I32, F32, I32, P, P, F32, P, P, P, P, P, P, I64, I32, F32, F32, P, P, P, P]),
+    'aod_focal_box_bwd_ex': (C.c_int, [I32, I32, F32, I32, P, P, F32, P, P, P, P, P, P, I64, I32, F32, F32, P, P, P, F32, I32, P, P, I32, I32, I32, I32, P]),
+    'aod_focal_box_levels_fwd_ex': (C.c_int, [I32, I32, F32, I32, P, P, F32, P, P, P, P, P, P, I32, P, I32, F32, F32, P, P, P, P, I32, P, P, P]),
+    'aod_focal_box_levels_bwd_ex': (C.c_int, [I32, I32, F32, I32, P, P, F32, P, P, P, P, P, P, I32, P, I32, F32, F32, P, P, P, P, P, I32, I32, I32, I32, P]),
     'aod_meh_loss_levels_fwd': (C.c_int, [P, P, P, I32, P, P, P, P]),
     'aod_meh_loss_levels_bwd': (C.c_int, [P, P, P, I32, P, P, P, I32, I32, I32, P]),
     'aod_meh_loss_fwd_ex': (C.c_int, [P, P, P, I64, I32, P, P, P]),

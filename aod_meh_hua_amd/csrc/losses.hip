@@ -104,6 +104,102 @@ __device__ __forceinline__ float sig_row_fwd(const float* x, int n, int c0, long
   return grp_sum<LPR>(tot);
 }
 
+// BOX (compile-time, next to FORM): the box term of a row whose lane part == 0 adds it to the block's second partial sum
+//   0  l1    sum_j |pred_j - tgt_j| * bw_j on the encoded deltas                                            smooth_l1_loss.py:33-45 (L1Loss)
+//   1  iou   w * -log(max(IoU, eps))  (w * (1 - max(IoU, eps)) when `linear`)                                 iou_loss.py:14-36  (IoULoss)
+//   2  giou  w * (1 - (IoU - (E - U) / E)),  U = max(U, eps), E = max(E, eps)                                 iou_loss.py:87-102 (GIoULoss)
+// with w = mean_j bw_j (iou_loss.py:275-280 `weight.mean(-1)`); a row with w == 0 is not evaluated: it adds exactly 0 and its four gradients
+// are +0 whatever its deltas hold (the sparse forward leaves arbitrary values there; the sparse backward skips all-zero rows).
+// Forms 1 and 2 decode the prediction row AND the target row in the anchor-normalised frame (delta2bbox of delta_xywh_bbox_coder.py:205-246
+// on the anchor (-.5, -.5, .5, .5)): t = d * std + mean, centre (t0, t1), size exp(clamp(t2 | t3, +-max_ratio)), corners centre -+ size / 2.
+// The map from that frame to pixels is a per-axis scaling plus a translation, under which intersection, union and enclosing area all scale by
+// the same factor: IoU and GIoU are the numbers of the pixel frame and no anchor is read.  bbox_overlaps(is_aligned=True)
+// (iou2d_calculator.py:212-260) in its order; the gradients are autograd's, subgradients included: torch.max(a, b) / torch.min(a, b) hand a
+// tie half the gradient each, clamp(min=m) passes where x >= m, clamp(min, max) passes on the closed interval.
+constexpr int BOX_L1 = 0, BOX_IOU = 1, BOX_GIOU = 2;
+struct BoxForm { float mean[4], std[4]; float max_ratio, eps; int linear; };
+// d max(a, b) / d a and d min(a, b) / d a
+__device__ __forceinline__ float sub_max(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
+__device__ __forceinline__ float sub_min(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
+
+__device__ __forceinline__ float box_exp(float x) { return (float)exp((double)x); }
+__device__ __forceinline__ float box_log(float x) { return (float)log((double)x); }
+
+// one row: the loss term l(pred deltas dp, target deltas dt) and, with GRAD, g[4] = d l / d dp  (constant indices only: all in registers).
+// IEEE divisions and correctly rounded exp / log (evaluated in double, rounded once), not the l_exp / l_div / l_log of the class terms: the
+// row sits at the end of cancelling differences of O(1) corners, -log(eps) = 13.8 has an ulp of 1e-6, and the row is held to a few ulps of
+// the float64 value; only rows with a box weight -- the positives -- pay.
+template <int BOX, bool GRAD>
+__device__ __forceinline__ float box_row(const f32x4 dp, const f32x4 dt, const BoxForm& k, float* g) {
+  float p1[2], p2[2], t1[2], t2[2], ps[2], pin[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float pc = dp[j] * k.std[j] + k.mean[j], tc = dt[j] * k.std[j] + k.mean[j];
+    const float pl = dp[2 + j] * k.std[2 + j] + k.mean[2 + j], tl = dt[2 + j] * k.std[2 + j] + k.mean[2 + j];
+    pin[j] = (pl >= -k.max_ratio && pl <= k.max_ratio) ? 1.f : 0.f;
+    ps[j] = box_exp(fminf(fmaxf(pl, -k.max_ratio), k.max_ratio));
+    const float ts = box_exp(fminf(fmaxf(tl, -k.max_ratio), k.max_ratio));
+    p1[j] = pc - ps[j] * 0.5f; p2[j] = pc + ps[j] * 0.5f;
+    t1[j] = tc - ts * 0.5f; t2[j] = tc + ts * 0.5f;
+  }
+  const float a1 = (p2[0] - p1[0]) * (p2[1] - p1[1]), a2 = (t2[0] - t1[0]) * (t2[1] - t1[1]);
+  float iwr[2], iw[2], ewr[2], ew[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    iwr[j] = fminf(p2[j], t2[j]) - fmaxf(p1[j], t1[j]);
+    iw[j] = fmaxf(iwr[j], 0.f);
+    if (BOX == BOX_GIOU) {
+      ewr[j] = fmaxf(p2[j], t2[j]) - fminf(p1[j], t1[j]);
+      ew[j] = fmaxf(ewr[j], 0.f);
+    }
+  }
+  const float ov = iw[0] * iw[1];
+  const float un = a1 + a2 - ov;
+  // (giou_loss hands its eps to bbox_overlaps; iou_loss calls it with the default 1e-6 and clamps the IoU at its own eps, iou_loss.py:31,100)
+  const float ueps = BOX == BOX_GIOU ? k.eps : 1e-6f;
+  const float U = fmaxf(un, ueps);
+  const float iou = ov / U;
+  float loss, Er = 0.f, E = 0.f, ic = 0.f;
+  if (BOX == BOX_GIOU) {
+    Er = ew[0] * ew[1];
+    E = fmaxf(Er, k.eps);
+    loss = 1.f - (iou - (E - U) / E);
+  } else {
+    ic = fmaxf(iou, k.eps);
+    loss = k.linear ? 1.f - ic : -box_log(ic);
+  }
+  if (GRAD) {
+    float g_ov, g_U, g_Er = 0.f;     // d l / d ov through IoU alone, d l / d (clamped union), d l / d (unclamped enclosing area)
+    if (BOX == BOX_GIOU) {
+      g_ov = -1.f / U;
+      g_U = ov / (U * U) - 1.f / E;
+      g_Er = U / (E * E) * sub_max(Er, k.eps);
+    } else {
+      const float gi = iou >= k.eps ? (k.linear ? -1.f : -1.f / ic) : 0.f;
+      g_ov = gi / U;
+      g_U = -gi * ov / (U * U);
+    }
+    const float g_un = g_U * sub_max(un, ueps);     // = d l / d a1 as well
+    const float g_ovt = g_ov - g_un;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int o = 1 - j;
+      float g2 = g_un * (p2[o] - p1[o]), g1 = -g2;    // the prediction's own area
+      const float giw = iwr[j] >= 0.f ? g_ovt * iw[o] : 0.f;
+      g2 += giw * sub_min(p2[j], t2[j]);
+      g1 -= giw * sub_max(p1[j], t1[j]);
+      if (BOX == BOX_GIOU) {
+        const float gew = ewr[j] >= 0.f ? g_Er * ew[o] : 0.f;
+        g2 += gew * sub_max(p2[j], t2[j]);
+        g1 -= gew * sub_min(p1[j], t1[j]);
+      }
+      g[j] = (g1 + g2) * k.std[j];
+      g[2 + j] = (g2 - g1) * 0.5f * ps[j] * pin[j] * k.std[2 + j];
+    }
+  }
+  return loss;
+}
+
 // One launch over ALL pyramid levels (Lambda_L2.py:105-121 runs loss_single once per level through multi_apply): the levels' anchor rows are
 // adjacent row ranges of the same buffers (level-batched prediction convs, level-major targets), and a block belongs to exactly one level --
 // level l owns the blocks [blk_end[l-1], blk_end[l]) and the rows [row_end[l-1], row_end[l]), its blocks start at its first row.  Blocks, rows
@@ -129,11 +225,12 @@ static int fill_levels(LossLevels& lv, int nlevels, const int64_t* level_rows, i
   return (int)b;
 }
 
-template <int FORM, int CT, int LPR>
+template <int FORM, int BOX, int CT, int LPR>
 __global__ __launch_bounds__(LB) void edl_l1_fwd_kernel(const float* __restrict__ cls, const long long* __restrict__ labels,
                                                         const float* __restrict__ lw, const float* __restrict__ bp,
                                                         const float* __restrict__ bt, const float* __restrict__ bw, const LossLevels lv, int C,
-                                                        float gamma, float alpha, float* __restrict__ loss_noR, float* __restrict__ partials) {
+                                                        float gamma, float alpha, float* __restrict__ loss_noR, float* __restrict__ partials,
+                                                        const BoxForm bf) {
   extern __shared__ __attribute__((aligned(16))) float srow[];
   constexpr int RB = LB / LPR;   // rows per block
   const int P = C | 1;  // odd pitch -> conflict-free row reads
@@ -163,7 +260,12 @@ __global__ __launch_bounds__(LB) void edl_l1_fwd_kernel(const float* __restrict_
       if (bp) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(bp + r * 4), b = *reinterpret_cast<const f32x4*>(bt + r * 4),
                     w = *reinterpret_cast<const f32x4*>(bw + r * 4);
-        for (int j = 0; j < 4; ++j) s_box += fabsf(a[j] - b[j]) * w[j];
+        if constexpr (BOX == BOX_L1) {
+          for (int j = 0; j < 4; ++j) s_box += fabsf(a[j] - b[j]) * w[j];
+        } else {
+          const float wm = (((w[0] + w[1]) + w[2]) + w[3]) * 0.25f;
+          if (wm != 0.f) s_box = wm * box_row<BOX, false>(a, b, bf, nullptr);
+        }
       }
     }
   }
@@ -241,17 +343,47 @@ static inline long long edl_blocks(int64_t nrows, int C) { const int rb = LB / e
 extern "C" size_t aod_loss_partials_len(int64_t nrows) { return (size_t)((nrows + LB / 4 - 1) / (LB / 4)) * 3; }
 
 // (one body per entry pair: `form` picks the kernel instantiation, `nm` names the entry in the error text)
-#define AOD_FOCAL_FWD_(FORM_, LPR_)                                                                                                        \
-  hipLaunchKernelGGL((edl_l1_fwd_kernel<FORM_, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
-                     (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials)
+#define AOD_FOCAL_FWD_(FORM_, LPR_, BOX_)                                                                                                  \
+  hipLaunchKernelGGL((edl_l1_fwd_kernel<FORM_, BOX_, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
+                     (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, loss_noR, partials, bf)
+#define AOD_FOCAL_FWD_B(FORM_, LPR_)                                                                                                       \
+  do {                                                                                                                                     \
+    if (box == BOX_GIOU) AOD_FOCAL_FWD_(FORM_, LPR_, BOX_GIOU); else if (box == BOX_IOU) AOD_FOCAL_FWD_(FORM_, LPR_, BOX_IOU);             \
+    else AOD_FOCAL_FWD_(FORM_, LPR_, BOX_L1);                                                                                              \
+  } while (0)
 #define AOD_FOCAL_FWD()                                                                                                                    \
   do {                                                                                                                                     \
-    if (form == FORM_SIGMOID) { if (C <= 24) AOD_FOCAL_FWD_(FORM_SIGMOID, 1); else AOD_FOCAL_FWD_(FORM_SIGMOID, 4); }                      \
-    else { if (C <= 24) AOD_FOCAL_FWD_(FORM_EDL, 1); else AOD_FOCAL_FWD_(FORM_EDL, 4); }                                                   \
+    if (form == FORM_SIGMOID) { if (C <= 24) AOD_FOCAL_FWD_B(FORM_SIGMOID, 1); else AOD_FOCAL_FWD_B(FORM_SIGMOID, 4); }                    \
+    else { if (C <= 24) AOD_FOCAL_FWD_B(FORM_EDL, 1); else AOD_FOCAL_FWD_B(FORM_EDL, 4); }                                                 \
   } while (0)
-static int focal_l1_fwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
-                        const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, float* loss_noR,
-                        float* sums3, float* partials, aod_stream_t stream) {
+
+// The `_ex` entries' box arguments -> (box, bf), checked; `nm` names the entry.  Box form l1 reads none of eps / linear / the coder (they
+// may be anything, the pointers NULL): the entries without `_ex` forward here with it.
+static const BoxForm BOX_FORM_L1 = {{0.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, 0.f, 0.f, 0};
+static int box_form_args(const char* nm, int focal_form, int box_form, const float* bbox_pred, float eps, int linear, const float* means4,
+                         const float* stds4, float wh_ratio_clip, BoxForm& bf) {
+  AOD_CHECK_ARG(focal_form == FORM_EDL || focal_form == FORM_SIGMOID, "%s: focal form must be 0 (edl) or 1 (sigmoid), got %d", nm, focal_form);
+  AOD_CHECK_ARG(box_form >= BOX_L1 && box_form <= BOX_GIOU, "%s: box form must be 0 (l1), 1 (iou) or 2 (giou), got %d", nm, box_form);
+  bf = BOX_FORM_L1;
+  if (box_form == BOX_L1) return 0;
+  AOD_CHECK_ARG(bbox_pred, "%s: box form %s needs bbox_pred", nm, box_form == BOX_IOU ? "iou" : "giou");
+  AOD_CHECK_ARG(means4 && stds4, "%s: box form %s needs the coder's means and stds", nm, box_form == BOX_IOU ? "iou" : "giou");
+  AOD_CHECK_ARG(fabsf(eps) <= 3.4028234e38f, "%s: eps must be finite (got %g)", nm, (double)eps);
+  for (int j = 0; j < 4; ++j) {
+    AOD_CHECK_ARG(fabsf(means4[j]) <= 3.4028234e38f && fabsf(stds4[j]) <= 3.4028234e38f, "%s: the coder's means and stds must be finite", nm);
+    AOD_CHECK_ARG(stds4[j] > 0.f, "%s: the coder's stds must be > 0 (got %g)", nm, (double)stds4[j]);
+    bf.mean[j] = means4[j]; bf.std[j] = stds4[j];
+  }
+  AOD_CHECK_ARG(wh_ratio_clip > 0.f && wh_ratio_clip <= 3.4028234e38f, "%s: wh_ratio_clip must be finite and > 0 (got %g)", nm, (double)wh_ratio_clip);
+  bf.max_ratio = (float)fabs(log((double)wh_ratio_clip));      // |ln(wh_ratio_clip)| of delta2bbox, rounded once
+  bf.eps = eps;
+  bf.linear = linear != 0;
+  return 0;
+}
+
+static int focal_l1_fwd(int form, int box, const BoxForm& bf, const char* nm, const float* cls, const int64_t* labels, const float* label_w,
+                        const float* bbox_pred, const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
+                        float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
   AOD_CHECK_ARG(nrows >= 0, "%s: negative row count", nm);
   if (nrows == 0) return 0;
   AOD_CHECK_ARG(cls && labels && label_w && loss_noR && sums3 && partials, "%s: null pointer", nm);
@@ -267,13 +399,23 @@ static int focal_l1_fwd(int form, const char* nm, const float* cls, const int64_
 extern "C" int aod_edl_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                     const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
                                     float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
-  return focal_l1_fwd(FORM_EDL, "edl_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR, sums3, partials, stream);
+  return focal_l1_fwd(FORM_EDL, BOX_L1, BOX_FORM_L1, "edl_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR, sums3,
+                      partials, stream);
+}
+extern "C" int aod_focal_box_fwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                    float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, float* loss_noR,
+                                    float* sums3, float* partials, aod_stream_t stream) {
+  BoxForm bf;
+  if (int e = box_form_args("focal_box_fwd_ex", focal_form, box_form, bbox_pred, box_eps, box_linear, means4, stds4, wh_ratio_clip, bf)) return e;
+  return focal_l1_fwd(focal_form, box_form, bf, "focal_box_fwd_ex", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR,
+                      sums3, partials, stream);
 }
 extern "C" int aod_sigmoid_focal_l1_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                         const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
                                         float* loss_noR, float* sums3, float* partials, aod_stream_t stream) {
-  return focal_l1_fwd(FORM_SIGMOID, "sigmoid_focal_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, loss_noR, sums3,
-                      partials, stream);
+  return focal_l1_fwd(FORM_SIGMOID, BOX_L1, BOX_FORM_L1, "sigmoid_focal_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha,
+                      loss_noR, sums3, partials, stream);
 }
 
 extern "C" size_t aod_loss_levels_partials_len(int nlevels, const int64_t* level_rows) {
@@ -286,7 +428,7 @@ static bool level_rows_ok(int nlevels, const int64_t* level_rows) {
   for (int l = 0; l < nlevels; ++l) if (level_rows[l] < 0) return false;
   return true;
 }
-static int focal_l1_levels_fwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+static int focal_l1_levels_fwd(int form, int box, const BoxForm& bf, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
                                float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images, float* divisors,
                                float* num_total, aod_stream_t stream) {
@@ -306,32 +448,44 @@ static int focal_l1_levels_fwd(int form, const char* nm, const float* cls, const
   return 0;
 }
 #undef AOD_FOCAL_FWD
+#undef AOD_FOCAL_FWD_B
 #undef AOD_FOCAL_FWD_
 extern "C" int aod_edl_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                            const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
                                            float alpha, float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
                                            float* divisors, float* num_total, aod_stream_t stream) {
-  return focal_l1_levels_fwd(FORM_EDL, "edl_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma, alpha, loss_noR,
-                             sums, partials, num_pos, num_images, divisors, num_total, stream);
+  return focal_l1_levels_fwd(FORM_EDL, BOX_L1, BOX_FORM_L1, "edl_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
+                             alpha, loss_noR, sums, partials, num_pos, num_images, divisors, num_total, stream);
+}
+extern "C" int aod_focal_box_levels_fwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                           float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                                           const float* bbox_pred, const float* bbox_tgt, const float* bbox_w, int nlevels,
+                                           const int64_t* level_rows, int C, float gamma, float alpha, float* loss_noR, float* sums, float* partials,
+                                           const int32_t* num_pos, int num_images, float* divisors, float* num_total, aod_stream_t stream) {
+  BoxForm bf;
+  if (int e = box_form_args("focal_box_levels_fwd_ex", focal_form, box_form, bbox_pred, box_eps, box_linear, means4, stds4, wh_ratio_clip, bf)) return e;
+  return focal_l1_levels_fwd(focal_form, box_form, bf, "focal_box_levels_fwd_ex", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C,
+                             gamma, alpha, loss_noR, sums, partials, num_pos, num_images, divisors, num_total, stream);
 }
 extern "C" int aod_sigmoid_focal_l1_levels_fwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                                const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
                                                float alpha, float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
                                                float* divisors, float* num_total, aod_stream_t stream) {
-  return focal_l1_levels_fwd(FORM_SIGMOID, "sigmoid_focal_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
-                             alpha, loss_noR, sums, partials, num_pos, num_images, divisors, num_total, stream);
+  return focal_l1_levels_fwd(FORM_SIGMOID, BOX_L1, BOX_FORM_L1, "sigmoid_focal_levels_fwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels,
+                             level_rows, C, gamma, alpha, loss_noR, sums, partials, num_pos, num_images, divisors, num_total, stream);
 }
 
 // backward.  Output element (row r, class c) lives at (r / A) * pitch + (r % A) * C + c so that the
 // gradient lands directly in the conv's [pixels, A*C (padded)] dZ layout, bf16 or fp32.
-template <int FORM, bool OUT_BF16, int CT, int LPR>
+template <int FORM, int BOX, bool OUT_BF16, int CT, int LPR>
 __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict__ cls, const long long* __restrict__ labels,
                                                         const float* __restrict__ lw, const float* __restrict__ bp,
                                                         const float* __restrict__ bt, const float* __restrict__ bw, const LossLevels lv, int C,
                                                         float gamma, float alpha, const float* __restrict__ g_cls,
                                                         const float* __restrict__ g_bbox, const float* __restrict__ g_noR, float g_noR_s, int g_noR_bcast,
                                                         void* __restrict__ grad_cls, void* __restrict__ grad_bbox, int A, int pitch_cls,
-                                                        int pitch_box, int g_lstride, const float* __restrict__ g_div, int nlv) {
+                                                        int pitch_box, int g_lstride, const float* __restrict__ g_div, int nlv,
+                                                        const BoxForm bf) {
   extern __shared__ __attribute__((aligned(16))) float srow[];
   constexpr int RB = LB / LPR;
   const int P = C | 1;
@@ -410,12 +564,28 @@ __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict_
     if (live && part == 0 && bp && grad_bbox) {
       const float gb = g_div ? g_bbox[gl] / g_div[nlv + gl] : g_bbox[gl];
       const long long bb = (r / A) * pitch_box + (r % A) * 4;
-      for (int j = 0; j < 4; ++j) {
-        const float d = bp[r * 4 + j] - bt[r * 4 + j];
-        const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        const float gx = sgn * bw[r * 4 + j] * gb;
-        if (OUT_BF16) ((bf16_t*)grad_bbox)[bb + j] = (bf16_t)gx;
-        else ((float*)grad_bbox)[bb + j] = gx;
+      if constexpr (BOX == BOX_L1) {
+        for (int j = 0; j < 4; ++j) {
+          const float d = bp[r * 4 + j] - bt[r * 4 + j];
+          const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+          const float gx = sgn * bw[r * 4 + j] * gb;
+          if (OUT_BF16) ((bf16_t*)grad_bbox)[bb + j] = (bf16_t)gx;
+          else ((float*)grad_bbox)[bb + j] = gx;
+        }
+      } else {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(bw + r * 4);
+        const float wm = (((w[0] + w[1]) + w[2]) + w[3]) * 0.25f;
+        float g4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (wm != 0.f) {
+          box_row<BOX, true>(*reinterpret_cast<const f32x4*>(bp + r * 4), *reinterpret_cast<const f32x4*>(bt + r * 4), bf, g4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) g4[j] = gb * wm * g4[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (OUT_BF16) ((bf16_t*)grad_bbox)[bb + j] = (bf16_t)g4[j];
+          else ((float*)grad_bbox)[bb + j] = g4[j];
+        }
       }
     }
   }
@@ -434,20 +604,25 @@ __global__ __launch_bounds__(LB) void edl_l1_bwd_kernel(const float* __restrict_
   }
 }
 
-#define AOD_FOCAL_BWD_(FORM_, BF, LPR_)                                                                                                    \
-  hipLaunchKernelGGL((edl_l1_bwd_kernel<FORM_, BF, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
+#define AOD_FOCAL_BWD_(FORM_, BOX_, BF, LPR_)                                                                                              \
+  hipLaunchKernelGGL((edl_l1_bwd_kernel<FORM_, BOX_, BF, 24, LPR_>), dim3((unsigned)nb), dim3(LB), (size_t)(LB / LPR_) * (C | 1) * 4, (hipStream_t)stream, cls, \
                      (const long long*)labels, label_w, bbox_pred, bbox_tgt, bbox_w, lv, C, gamma, alpha, g_cls, g_bbox, g_noR, \
-                     g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, A, pitch_cls, pitch_box, g_lstride, g_div, nlv_)
+                     g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, A, pitch_cls, pitch_box, g_lstride, g_div, nlv_, bf)
+#define AOD_FOCAL_BWD_B(FORM_, BOX_)                                                                                                       \
+  do {                                                                                                                                     \
+    if (out_bf16) { if (C <= 24) AOD_FOCAL_BWD_(FORM_, BOX_, true, 1); else AOD_FOCAL_BWD_(FORM_, BOX_, true, 4); }                        \
+    else { if (C <= 24) AOD_FOCAL_BWD_(FORM_, BOX_, false, 1); else AOD_FOCAL_BWD_(FORM_, BOX_, false, 4); }                               \
+  } while (0)
 #define AOD_FOCAL_BWD_F(FORM_)                                                                                                             \
   do {                                                                                                                                     \
-    if (out_bf16) { if (C <= 24) AOD_FOCAL_BWD_(FORM_, true, 1); else AOD_FOCAL_BWD_(FORM_, true, 4); }                                    \
-    else { if (C <= 24) AOD_FOCAL_BWD_(FORM_, false, 1); else AOD_FOCAL_BWD_(FORM_, false, 4); }                                           \
+    if (box == BOX_GIOU) AOD_FOCAL_BWD_B(FORM_, BOX_GIOU); else if (box == BOX_IOU) AOD_FOCAL_BWD_B(FORM_, BOX_IOU);                       \
+    else AOD_FOCAL_BWD_B(FORM_, BOX_L1);                                                                                                   \
   } while (0)
 #define AOD_FOCAL_BWD()                                                                                                                    \
   do {                                                                                                                                     \
     if (form == FORM_SIGMOID) AOD_FOCAL_BWD_F(FORM_SIGMOID); else AOD_FOCAL_BWD_F(FORM_EDL);                                               \
   } while (0)
-static int focal_l1_bwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+static int focal_l1_bwd(int form, int box, const BoxForm& bf, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                         const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, const float* g_cls,
                         const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar, void* grad_cls, void* grad_bbox,
                         int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
@@ -468,21 +643,31 @@ extern "C" int aod_edl_focal_l1_bwd(const float* cls, const int64_t* labels, con
                                     const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
                                     const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
                                     void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
-  return focal_l1_bwd(FORM_EDL, "edl_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR, g_noR_scalar,
-                      g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+  return focal_l1_bwd(FORM_EDL, BOX_L1, BOX_FORM_L1, "edl_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR,
+                      g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+}
+extern "C" int aod_focal_box_bwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                    float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+                                    const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha, const float* g_cls,
+                                    const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar, void* grad_cls,
+                                    void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
+  BoxForm bf;
+  if (int e = box_form_args("focal_box_bwd_ex", focal_form, box_form, bbox_pred, box_eps, box_linear, means4, stds4, wh_ratio_clip, bf)) return e;
+  return focal_l1_bwd(focal_form, box_form, bf, "focal_box_bwd_ex", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox,
+                      g_noR, g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 extern "C" int aod_sigmoid_focal_l1_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                         const float* bbox_tgt, const float* bbox_w, int64_t nrows, int C, float gamma, float alpha,
                                         const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
                                         void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
-  return focal_l1_bwd(FORM_SIGMOID, "sigmoid_focal_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR,
+  return focal_l1_bwd(FORM_SIGMOID, BOX_L1, BOX_FORM_L1, "sigmoid_focal_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nrows, C, gamma, alpha, g_cls, g_bbox, g_noR,
                       g_noR_scalar, g_noR_is_scalar, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 
 // g_sums[3][nlevels] = the gradients of aod_edl_focal_l1_levels_fwd's sums (row 0: classification sums, row 1: box sums, row 2: row sums) --
 // of the DIVIDED sums when `divisors` (the forward's) is given: the kernel forms g / divisor itself;
 // g_noR_rows (optional): a gradient per anchor row of loss_noR, replaces row 2.
-static int focal_l1_levels_bwd(int form, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
+static int focal_l1_levels_bwd(int form, int box, const BoxForm& bf, const char* nm, const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
                                const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox, int out_bf16,
                                int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
@@ -504,19 +689,31 @@ static int focal_l1_levels_bwd(int form, const char* nm, const float* cls, const
 }
 #undef AOD_FOCAL_BWD
 #undef AOD_FOCAL_BWD_F
+#undef AOD_FOCAL_BWD_B
 #undef AOD_FOCAL_BWD_
 extern "C" int aod_edl_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                            const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
                                            float alpha, const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls,
                                            void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
-  return focal_l1_levels_bwd(FORM_EDL, "edl_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma, alpha, g_sums,
-                             divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+  return focal_l1_levels_bwd(FORM_EDL, BOX_L1, BOX_FORM_L1, "edl_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
+                             alpha, g_sums, divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
+}
+extern "C" int aod_focal_box_levels_bwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                           float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                                           const float* bbox_pred, const float* bbox_tgt, const float* bbox_w, int nlevels,
+                                           const int64_t* level_rows, int C, float gamma, float alpha, const float* g_sums, const float* divisors,
+                                           const float* g_noR_rows, void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls,
+                                           int pitch_box, aod_stream_t stream) {
+  BoxForm bf;
+  if (int e = box_form_args("focal_box_levels_bwd_ex", focal_form, box_form, bbox_pred, box_eps, box_linear, means4, stds4, wh_ratio_clip, bf)) return e;
+  return focal_l1_levels_bwd(focal_form, box_form, bf, "focal_box_levels_bwd_ex", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C,
+                             gamma, alpha, g_sums, divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 extern "C" int aod_sigmoid_focal_l1_levels_bwd(const float* cls, const int64_t* labels, const float* label_w, const float* bbox_pred,
                                                const float* bbox_tgt, const float* bbox_w, int nlevels, const int64_t* level_rows, int C, float gamma,
                                                float alpha, const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls,
                                                void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream) {
-  return focal_l1_levels_bwd(FORM_SIGMOID, "sigmoid_focal_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
+  return focal_l1_levels_bwd(FORM_SIGMOID, BOX_L1, BOX_FORM_L1, "sigmoid_focal_levels_bwd", cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, nlevels, level_rows, C, gamma,
                              alpha, g_sums, divisors, g_noR_rows, grad_cls, grad_bbox, out_bf16, A, pitch_cls, pitch_box, stream);
 }
 

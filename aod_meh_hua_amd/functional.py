@@ -1321,10 +1321,12 @@ class RetinaLossFn(Function):
     device scalar so that no host sync is needed)."""
 
     @staticmethod
-    def forward(ctx, cls_score, bbox_pred, labels, label_w, bbox_t, bbox_w, gamma, alpha, num_classes, arena=None, level=0, form='edl'):
-        """form: 'edl' (softmax -> logit -> focal) or 'sigmoid' (the focal term on the raw logits, MyRetinaHead.py:91-109), hipops.FOCAL_FORMS"""
+    def forward(ctx, cls_score, bbox_pred, labels, label_w, bbox_t, bbox_w, gamma, alpha, num_classes, arena=None, level=0, form='edl', box=None):
+        """form: 'edl' (softmax -> logit -> focal) or 'sigmoid' (the focal term on the raw logits, MyRetinaHead.py:91-109), hipops.FOCAL_FORMS
+        box: None (L1 on the deltas) or box_kwargs(...) -- the IoU / GIoU term on the decoded boxes, hipops.BOX_FORMS"""
         B, AC, H, W = cls_score.shape
         ctx.arena, ctx.level, ctx.form = arena, level, form
+        ctx.box = box = dict(box or {})
         # (an output nobody differentiates -- the loss_noR rows, which train_step detaches -- arrives as None in backward instead of a
         # zero-filled tensor of its size that backward would then add the row-sum gradient to: two launches per level)
         ctx.set_materialize_grads(False)
@@ -1335,7 +1337,7 @@ class RetinaLossFn(Function):
         label_w = label_w.reshape(-1).contiguous()
         bbox_t = bbox_t.reshape(-1, 4).contiguous()
         bbox_w = bbox_w.reshape(-1, 4).contiguous()
-        noR, sums = ho.edl_focal_l1_fwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, gamma, alpha, form=form)
+        noR, sums = ho.edl_focal_l1_fwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, gamma, alpha, form=form, **box)
         ctx.save_for_backward(cls_rows, box_rows, labels, label_w, bbox_t, bbox_w)
         ctx.cfg = (gamma, alpha, cls_score.shape, bbox_pred.shape)
         return sums[0], sums[1], noR, sums[2]      # sums[2] = sum(noR): lets the caller form mean(loss_noR) without a pass over the rows
@@ -1360,9 +1362,17 @@ class RetinaLossFn(Function):
             dst_c = ctx.arena.slice('cls', ctx.level, B * H * W, AC, dev).view(-1, cls_rows.shape[1])
             dst_b = ctx.arena.slice('box', ctx.level, B * H * W, bshape[1], dev).view(-1, 4)
         gc, gb = ho.edl_focal_l1_bwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, g_cls, g_box, g_noR_t, 0.0, gamma, alpha,
-                                     g_noR_is_scalar=scalar, grad_cls=dst_c, grad_bbox=dst_b, form=ctx.form)
+                                     g_noR_is_scalar=scalar, grad_cls=dst_c, grad_bbox=dst_b, form=ctx.form, **ctx.box)
         return (as_nchw(gc.view(B * H * W, AC), B, H, W), as_nchw(gb.view(B * H * W, bshape[1]), B, H, W),
-                None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
+def box_kwargs(box_form='l1', eps=1e-6, linear=False, coder=None):
+    """The box-form arguments of the fused loss launches (hipops.edl_focal_l1_*) as RetinaLossFn / RetinaLossLevelsFn carry them: None for
+    the L1 term (the launches then run exactly what they ran before the box forms existed), a dict otherwise."""
+    if box_form == 'l1':
+        return None
+    return dict(box_form=box_form, box_eps=float(eps), box_linear=bool(linear), coder=coder)
 
 
 def dense_concat(tensors):
@@ -1400,18 +1410,19 @@ class RetinaLossLevelsFn(Function):
     [all rows]).  Same blocks, same summation orders as the per-level launches: identical bits (tests/test_gpu_kernels.py)."""
 
     @staticmethod
-    def forward(ctx, cls_rows, box_rows, labels, label_w, bbox_t, bbox_w, gamma, alpha, level_rows, shapes, num_pos=None, form='edl'):
+    def forward(ctx, cls_rows, box_rows, labels, label_w, bbox_t, bbox_w, gamma, alpha, level_rows, shapes, num_pos=None, form='edl', box=None):
         """num_pos (int32 [B], the assigner's per-image positive counts): the sums come back divided -- rows 0, 1 by num_total_samples =
         sum_b max(num_pos[b], 1), row 2 by the level's row count (L_anchor_head.py:266-288,300-303; SSL_Lambda.py:136-141) -- and
         num_total_samples as a third output; the clamp / sum / cast / cat / divide launches of the tensor form are inside the reduction."""
         ctx.set_materialize_grads(False)
         ctx.form = form
+        ctx.box = box = dict(box or {})      # (None: the L1 term; functional.box_kwargs)
         div = nt = None
         if num_pos is None:
-            noR, sums = ho.edl_focal_l1_levels_fwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, level_rows, gamma, alpha, form=form)
+            noR, sums = ho.edl_focal_l1_levels_fwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, level_rows, gamma, alpha, form=form, **box)
         else:
             noR, sums, div, nt = ho.edl_focal_l1_levels_fwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, level_rows, gamma, alpha, num_pos,
-                                                            form=form)
+                                                            form=form, **box)
         ctx.save_for_backward(cls_rows, box_rows, labels, label_w, bbox_t, bbox_w, div)
         ctx.cfg = (gamma, alpha, tuple(level_rows), shapes)
         if nt is None:
@@ -1436,8 +1447,8 @@ class RetinaLossLevelsFn(Function):
         gc = torch.empty(cls_rows.shape[0] // A, AC, dtype=torch.float32, device=dev)
         gb = torch.empty(cls_rows.shape[0] // A, A4, dtype=torch.float32, device=dev)
         ho.edl_focal_l1_levels_bwd(cls_rows, labels, label_w, box_rows, bbox_t, bbox_w, level_rows, g_sums, g_rows, gc, gb, A, gamma, alpha, divisors=div,
-                                   form=ctx.form)
-        return gc.view(cls_rows.shape), gb.view(box_rows.shape), None, None, None, None, None, None, None, None, None, None
+                                   form=ctx.form, **ctx.box)
+        return gc.view(cls_rows.shape), gb.view(box_rows.shape), None, None, None, None, None, None, None, None, None, None, None
 
 
 _LEVEL_ROWS_DEV = {}

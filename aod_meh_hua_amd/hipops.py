@@ -774,10 +774,32 @@ def act_bwd(g, a=None, z=None, scale=None, mean=None, invstd=None, relu=True, wa
 # the focal forms of the fused loss kernels: 'edl' = softmax -> logit -> focal (EDL_Softmax_FocalLoss), 'sigmoid' = the focal term on the raw
 # logits (FocalLoss of the plain RetinaNet baseline, focal_loss.py:85).  Same arguments, same layouts, one entry family each.
 FOCAL_FORMS = {'edl': 'aod_edl_focal', 'sigmoid': 'aod_sigmoid_focal'}
+# the box forms of the same kernels: 'l1' on the encoded deltas (L1Loss), 'iou' / 'giou' on the boxes decoded from the prediction
+# and the target deltas in the anchor-normalised frame (IoULoss / GIoULoss with reg_decoded_bbox=True).  'l1' runs the entries it always ran;
+# the other two go through aod_focal_box_*_ex.
+BOX_FORMS = {'l1': 0, 'iou': 1, 'giou': 2}
+FOCAL_FORM_IDS = {'edl': 0, 'sigmoid': 1}
 
 
-def edl_focal_l1_fwd(cls, labels, label_w, bbox_pred=None, bbox_tgt=None, bbox_w=None, gamma=2.0, alpha=0.25, sums=None, form='edl'):
-    """cls [rows, C] fp32.  Returns (loss_noR [rows], sums[3] = (sum l*w, sum |d|*bw, sum noR))."""
+def _box_entry(form, box_form, box_eps, box_linear, coder, suffix, args):
+    """Runs aod_{edl,sigmoid}_focal_l1_<suffix>(*args) for box_form 'l1', aod_focal_box_<suffix>_ex(forms, eps, linear, coder, *args) otherwise.
+    coder = (means, stds, wh_ratio_clip) of the head's DeltaXYWHBBoxCoder; None = (0, 0, 0, 0), (1, 1, 1, 1), 16 / 1000."""
+    if box_form not in BOX_FORMS:
+        raise ValueError(f"unknown box form {box_form!r} (expected 'l1', 'iou' or 'giou')")
+    if box_form == 'l1':
+        return call(FOCAL_FORMS[form] + '_l1_' + suffix, *args)
+    means, stds, clip = coder if coder is not None else ((0., 0., 0., 0.), (1., 1., 1., 1.), 16 / 1000)
+    means, stds = tuple(float(v) for v in means), tuple(float(v) for v in stds)
+    if len(means) != 4 or len(stds) != 4:
+        raise ValueError('the coder must hold four means and four stds')
+    return call('aod_focal_box_' + suffix + '_ex', FOCAL_FORM_IDS[form], BOX_FORMS[box_form], float(box_eps), int(bool(box_linear)), _F4(*means),
+                _F4(*stds), float(clip), *args)
+
+
+def edl_focal_l1_fwd(cls, labels, label_w, bbox_pred=None, bbox_tgt=None, bbox_w=None, gamma=2.0, alpha=0.25, sums=None, form='edl',
+                     box_form='l1', box_eps=1e-6, box_linear=False, coder=None):
+    """cls [rows, C] fp32.  Returns (loss_noR [rows], sums[3] = (sum l*w, sum |d|*bw, sum noR)); sums[1] is the sum of the IoU / GIoU row
+    terms for box_form 'iou' / 'giou' (BOX_FORMS)."""
     rows, Cc = cls.shape
     loss_noR = torch.empty(rows, dtype=torch.float32, device=cls.device)
     if sums is None:
@@ -785,14 +807,15 @@ def edl_focal_l1_fwd(cls, labels, label_w, bbox_pred=None, bbox_tgt=None, bbox_w
     part = torch.empty(max(int(_C.lib.aod_loss_partials_len(rows)), 1), dtype=torch.float32, device=cls.device)
     # algorithmic bytes per anchor row: logits + label (int64) + label weight + 3 box vectors in, loss_noR out
     prof_bytes(form + '_l1_fwd', rows * (Cc * 4 + 8 + 4 + (48 if bbox_pred is not None else 0) + 4),
-               lambda: call(FOCAL_FORMS[form] + '_l1_fwd', ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), rows, Cc,
-                            gamma, alpha, ptr(loss_noR), ptr(sums), ptr(part), stream()))
+               lambda: _box_entry(form, box_form, box_eps, box_linear, coder, 'fwd',
+                                  (ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), rows, Cc,
+                                   gamma, alpha, ptr(loss_noR), ptr(sums), ptr(part), stream())))
     return loss_noR, sums
 
 
 def edl_focal_l1_bwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, g_cls, g_bbox, g_noR=None, g_noR_scalar=0.0,
                      gamma=2.0, alpha=0.25, g_noR_is_scalar=False, out_bf16=False, A=1, pitch_cls=None, pitch_box=None, grad_cls=None, grad_bbox=None,
-                     form='edl'):
+                     form='edl', box_form='l1', box_eps=1e-6, box_linear=False, coder=None):
     rows, Cc = cls.shape
     pitch_cls = pitch_cls or A * Cc
     pitch_box = pitch_box or A * 4
@@ -805,9 +828,10 @@ def edl_focal_l1_bwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, g_cls, g
         grad_bbox = alloc(pitch_box, A * 4)
     esz = 2 if out_bf16 else 4
     prof_bytes(form + '_l1_bwd', rows * (Cc * 4 + 8 + 4 + (4 if (g_noR is not None and not g_noR_is_scalar) else 0) + Cc * esz + ((48 + 4 * esz) if bbox_pred is not None else 0)),
-               lambda: call(FOCAL_FORMS[form] + '_l1_bwd', ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), rows, Cc,
-                            gamma, alpha, ptr(g_cls), ptr(g_bbox), ptr(g_noR), float(g_noR_scalar), int(bool(g_noR_is_scalar)), ptr(grad_cls), ptr(grad_bbox), int(out_bf16), A,
-                            pitch_cls, pitch_box, stream()))
+               lambda: _box_entry(form, box_form, box_eps, box_linear, coder, 'bwd',
+                                  (ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), rows, Cc,
+                                   gamma, alpha, ptr(g_cls), ptr(g_bbox), ptr(g_noR), float(g_noR_scalar), int(bool(g_noR_is_scalar)), ptr(grad_cls),
+                                   ptr(grad_bbox), int(out_bf16), A, pitch_cls, pitch_box, stream())))
     return grad_cls, grad_bbox
 
 
@@ -843,7 +867,8 @@ def _level_rows(rows):
     return (C.c_int64 * len(rows))(*[int(r) for r in rows])
 
 
-def edl_focal_l1_levels_fwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, level_rows, gamma=2.0, alpha=0.25, num_pos=None, form='edl'):
+def edl_focal_l1_levels_fwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, level_rows, gamma=2.0, alpha=0.25, num_pos=None, form='edl',
+                            box_form='l1', box_eps=1e-6, box_linear=False, coder=None):
     """All pyramid levels in one launch: cls [rows, C] fp32 with level l = rows [sum(level_rows[:l]), +level_rows[l]).  Returns
     (loss_noR [rows], sums [3, L]) -- bit-identical to L calls of edl_focal_l1_fwd on the level slices.  With num_pos (int32 [B], the
     assigner's per-image positive counts): (loss_noR, sums / divisors, divisors [3, L], num_total_samples [1])."""
@@ -860,22 +885,24 @@ def edl_focal_l1_levels_fwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, l
         nt = torch.empty(1, dtype=torch.float32, device=cls.device)
     part = torch.empty(max(int(_C.lib.aod_loss_levels_partials_len(L, lr)), 1), dtype=torch.float32, device=cls.device)
     prof_bytes(form + '_l1_fwd', rows * (Cc * 4 + 8 + 4 + (48 if bbox_pred is not None else 0) + 4),
-               lambda: call(FOCAL_FORMS[form] + '_l1_levels_fwd', ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), L, lr, Cc,
-                            gamma, alpha, ptr(loss_noR), ptr(sums), ptr(part), ptr(num_pos), 0 if num_pos is None else int(num_pos.numel()), ptr(div),
-                            ptr(nt), stream()))
+               lambda: _box_entry(form, box_form, box_eps, box_linear, coder, 'levels_fwd',
+                                  (ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), L, lr, Cc,
+                                   gamma, alpha, ptr(loss_noR), ptr(sums), ptr(part), ptr(num_pos), 0 if num_pos is None else int(num_pos.numel()),
+                                   ptr(div), ptr(nt), stream())))
     return (loss_noR, sums) if num_pos is None else (loss_noR, sums, div, nt)
 
 
 def edl_focal_l1_levels_bwd(cls, labels, label_w, bbox_pred, bbox_tgt, bbox_w, level_rows, g_sums, g_noR_rows, grad_cls, grad_bbox, A,
-                            gamma=2.0, alpha=0.25, divisors=None, form='edl'):
+                            gamma=2.0, alpha=0.25, divisors=None, form='edl', box_form='l1', box_eps=1e-6, box_linear=False, coder=None):
     """g_sums [3, L] fp32 contiguous; gradients are written into grad_cls [rows / A, A * C] / grad_bbox [rows / A, A * 4] (fp32, unpadded)."""
     rows, Cc = cls.shape
     L = len(level_rows)
     lr = _level_rows(level_rows)
     assert g_sums.shape == (3, L) and g_sums.is_contiguous() and g_sums.dtype == torch.float32
     prof_bytes(form + '_l1_bwd', rows * (Cc * 4 + 8 + 4 + (4 if g_noR_rows is not None else 0) + Cc * 4 + ((48 + 16) if bbox_pred is not None else 0)),
-               lambda: call(FOCAL_FORMS[form] + '_l1_levels_bwd', ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), L, lr, Cc,
-                            gamma, alpha, ptr(g_sums), ptr(divisors), ptr(g_noR_rows), ptr(grad_cls), ptr(grad_bbox), 0, A, A * Cc, A * 4, stream()))
+               lambda: _box_entry(form, box_form, box_eps, box_linear, coder, 'levels_bwd',
+                                  (ptr(cls), ptr(labels), ptr(label_w), ptr(bbox_pred), ptr(bbox_tgt), ptr(bbox_w), L, lr, Cc,
+                                   gamma, alpha, ptr(g_sums), ptr(divisors), ptr(g_noR_rows), ptr(grad_cls), ptr(grad_bbox), 0, A, A * Cc, A * 4, stream())))
     return grad_cls, grad_bbox
 
 

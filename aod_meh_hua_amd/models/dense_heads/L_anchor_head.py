@@ -19,6 +19,9 @@ _NO_SAMPLING = ['EDL_Loss', 'EDL_Loss_2', 'EDL_Loss_3', 'EDL_Loss_BCE', 'FocalLo
                 'EDL_Softmax_SL_FocalLoss', 'SSL_EDL_Softmax_FocalLoss']
 
 
+_DECODED_BOX_LOSSES = ('IoULoss', 'GIoULoss')      # box losses on decoded (x1, y1, x2, y2) boxes: reg_decoded_bbox=True
+
+
 class PackedGT(tuple):
     """(gts [B,Gmax,4] f32, counts [B] int32, labels [B,Gmax] int64) already on the device: what pack_gts produces.  Passed as
     `gt_bboxes` (with gt_labels=None) by callers that keep static input buffers (graphs.GraphedTrainStep)."""
@@ -70,11 +73,19 @@ class L_AnchorHead(BaseModule):
             self.cls_out_channels = num_classes + 1
         if self.cls_out_channels <= 0:
             raise ValueError(f'num_classes={num_classes} is too small')
-        self.reg_decoded_bbox = reg_decoded_bbox
-        assert not reg_decoded_bbox
+        self.reg_decoded_bbox = bool(reg_decoded_bbox)
         self.bbox_coder = build_bbox_coder(bbox_coder)
         self.loss_cls = build_loss(loss_cls)
         self.loss_bbox = build_loss(loss_bbox)
+        # the box loss and the space it is taken in go together (anchor_head.py:354-359): IoULoss / GIoULoss read decoded boxes, every other
+        # box loss reads the encoded deltas.  The targets stay encoded either way; the fused loss launches decode both rows.
+        bbox_type = type(self.loss_bbox).__name__
+        if self.reg_decoded_bbox != (bbox_type in _DECODED_BOX_LOSSES):
+            raise ValueError(f'reg_decoded_bbox={self.reg_decoded_bbox} does not go with loss_bbox={bbox_type}: reg_decoded_bbox=True is for '
+                             f'loss_bbox in {sorted(_DECODED_BOX_LOSSES)} and for nothing else')
+        if self.reg_decoded_bbox and type(self.bbox_coder).__name__ != 'DeltaXYWHBBoxCoder':
+            raise ValueError(f'reg_decoded_bbox=True with loss_bbox={bbox_type} needs bbox_coder=DeltaXYWHBBoxCoder '
+                             f'(got {type(self.bbox_coder).__name__})')
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         if self.train_cfg:
             self.assigner = build_assigner(self.train_cfg.assigner)
@@ -162,6 +173,19 @@ class L_AnchorHead(BaseModule):
         with torch.no_grad():
             ho.class_difficulty_update(self._class_difficulty_acc, self.class_difficulty, self.class_difficulty_cfg['momentum'])
         self._class_difficulty_due = False
+
+    def _box_loss_form(self):
+        """loss_bbox as the box form of the fused loss launches (functional.box_kwargs): None for L1Loss -- the launches as they always
+        were --, the 'iou' / 'giou' form with the loss's eps / linear and this head's coder for IoULoss / GIoULoss (decode's wh_ratio_clip
+        is its default, as in anchor_head.py:358).  Any other box loss has no fused form."""
+        t = type(self.loss_bbox).__name__
+        if t == 'L1Loss':
+            return None
+        if t not in _DECODED_BOX_LOSSES:
+            raise ValueError(f'{type(self).__name__} is built for loss_bbox=L1Loss, IoULoss or GIoULoss (got {t})')
+        from ... import functional as AF
+        coder = (tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds), 16 / 1000)
+        return AF.box_kwargs('giou' if t == 'GIoULoss' else 'iou', self.loss_bbox.eps, getattr(self.loss_bbox, 'linear', False), coder)
 
     def _init_layers(self):
         self.conv_cls = Conv2d(self.in_channels, self.num_anchors * self.cls_out_channels, 1)

@@ -22,6 +22,9 @@ from ..builder import HEADS
 from .L_anchor_head import L_AnchorHead
 
 
+_FUSED_BOX_LOSSES = ('L1Loss', 'IoULoss', 'GIoULoss')      # the box forms of the fused loss launches (L_AnchorHead._box_loss_form)
+
+
 @HEADS.register_module()
 class Lambda_L2Net(L_AnchorHead):
     def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None, norm_cfg=None,
@@ -61,12 +64,13 @@ class Lambda_L2Net(L_AnchorHead):
     def _sparse_fwd_prepare(self, x, img_metas, gt_bboxes, gt_labels, **kwargs):
         """-> (the assigner's targets, [m0, F_n, ..., F_1]) or (None, None): the dense path.  F_k = where the output of tower layer k is needed
         (hipops.fwd_row_maps).  Taken only in the live training branch whose readers of bbox_preds / L_scores all multiply by bbox_weights
-        (DESIGN 3a): L1 box loss, an MEH form of hipops.MEH_FORMS, the MEH tower riding in the paired launches."""
+        (DESIGN 3a): L1 box loss -- or the IoU / GIoU forms, which do not multiply but SKIP the rows whose weights are zero --, an
+        MEH form of hipops.MEH_FORMS, the MEH tower riding in the paired launches."""
         from ... import hipops as ho
         x = list(x)
         n = len(self.reg_convs)
         ok = (ho.sparse_fwd() and torch.is_grad_enabled() and self.training and kwargs.get('Labeled', True) and not kwargs.get('Pseudo', False)
-              and type(self.loss_bbox).__name__ == 'L1Loss' and self._meh_form in ('l2', 'l1', 'msle') and self._rides(x)
+              and type(self.loss_bbox).__name__ in _FUSED_BOX_LOSSES and self._meh_form in ('l2', 'l1', 'msle') and self._rides(x)
               and 1 <= n == len(self.cls_convs) <= 7 and all(m.with_activation for m in list(self.cls_convs) + list(self.reg_convs))
               and all(m.conv.weight.shape[2:] == (3, 3) and m.conv.padding == (1, 1) and m.conv.dilation == (1, 1) and m.conv.stride == (1, 1)
                       for m in list(self.reg_convs) + list(self.L_convs))
@@ -173,10 +177,12 @@ class Lambda_L2Net(L_AnchorHead):
         entered by the AL driver (SURVEY 3.2 iv) and is not built."""
         if not (kwargs.get('Labeled', True) and not kwargs.get('Pseudo', False)):
             raise NotImplementedError('pseudo-label branch (Lambda_L2.py:122-232) is dead code in the reference driver')
-        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == self._loss_cls_type
+        assert type(self.loss_bbox).__name__ in _FUSED_BOX_LOSSES and type(self.loss_cls).__name__ == self._loss_cls_type
+        # (reg_decoded_bbox: the reference's Lambda_L2.loss_single (:118-121) lacks the decode line of anchor_head.py:354-359 / MyRetinaHead.py:104-106
+        # and so compares deltas with boxes; here the setting means what it means there -- the loss on the decoded boxes, DESIGN 3r)
         sum_cls, sum_box, loss_noR, sum_noR = AF.RetinaLossFn.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
                                                                     float(self.loss_cls.gamma), float(self.loss_cls.alpha), self.cls_out_channels,
-                                                                    kwargs.get('grad_arena'), int(sIdx), self._focal_form)
+                                                                    kwargs.get('grad_arena'), int(sIdx), self._focal_form, self._box_loss_form())
         if self.class_difficulty_cfg is not None and self.training:      # (the operands as RetinaLossFn.forward hands them to the launch)
             C = self.cls_out_channels
             self._track_class_difficulty(AF.as_rows(cls_score.detach()).view(-1, C), labels.reshape(-1).contiguous(),
@@ -199,7 +205,7 @@ class Lambda_L2Net(L_AnchorHead):
             raise NotImplementedError('pseudo-label branch (Lambda_L2.py:122-232) is dead code in the reference driver')
         if self.loss_cls.loss_weight != 1.0 or self.loss_bbox.loss_weight != 1.0:
             return None
-        assert type(self.loss_bbox).__name__ == 'L1Loss' and type(self.loss_cls).__name__ == self._loss_cls_type
+        assert type(self.loss_bbox).__name__ in _FUSED_BOX_LOSSES and type(self.loss_cls).__name__ == self._loss_cls_type
         C = self.cls_out_channels
         cls_d, box_d = AF.dense_levels(cls_scores), AF.dense_levels(bbox_preds)
         flat = [AF.dense_concat([t.reshape(-1, *t.shape[2:]) for t in ts]) for ts in (labels_list, lw_list, bt_list, bw_list)]
@@ -209,7 +215,7 @@ class Lambda_L2Net(L_AnchorHead):
         level_rows = [c.shape[0] * c.shape[2] * c.shape[3] * A for c in cls_scores]
         out = AF.RetinaLossLevelsFn.apply(cls_d.view(-1, C), box_d.view(-1, 4), flat[0], flat[1], flat[2], flat[3],
                                           float(self.loss_cls.gamma), float(self.loss_cls.alpha), level_rows,
-                                          (A, cls_d.shape[1], box_d.shape[1]), num_pos, self._focal_form)
+                                          (A, cls_d.shape[1], box_d.shape[1]), num_pos, self._focal_form, self._box_loss_form())
         if self.class_difficulty_cfg is not None:
             self._track_class_difficulty(cls_d.view(-1, C), flat[0], flat[1], box_d.view(-1, 4), flat[2])
         return (out[0], list(out[1].split(level_rows))) + tuple(out[2:])

@@ -29,9 +29,11 @@ class MyRetinaHead(L_AnchorHead):
                                override=dict(type='Normal', name='retina_cls', std=0.01, bias_prob=0.01)), **kwargs):
         self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
         super().__init__(num_classes, in_channels, anchor_generator=anchor_generator, init_cfg=init_cfg, **kwargs)
-        if self.last_activation != 'sigmoid' or type(self.loss_cls).__name__ != 'FocalLoss' or type(self.loss_bbox).__name__ != 'L1Loss':
-            raise ValueError("MyRetinaHead is built for loss_cls=FocalLoss(last_activation='sigmoid') + loss_bbox=L1Loss "
-                             f'(got {type(self.loss_cls).__name__}/{self.last_activation} + {type(self.loss_bbox).__name__})')
+        if (self.last_activation != 'sigmoid' or type(self.loss_cls).__name__ != 'FocalLoss'
+                or type(self.loss_bbox).__name__ not in ('L1Loss', 'IoULoss', 'GIoULoss')):
+            raise ValueError("MyRetinaHead is built for loss_cls=FocalLoss(last_activation='sigmoid') + loss_bbox=L1Loss, or IoULoss / GIoULoss "
+                             f'with reg_decoded_bbox=True (got {type(self.loss_cls).__name__}/{self.last_activation} + '
+                             f'{type(self.loss_bbox).__name__})')
 
     def _init_layers(self):
         """MyRetinaHead.py:47-78 (same attribute names -> same state_dict keys)."""

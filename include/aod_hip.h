@@ -476,6 +476,42 @@ int aod_sigmoid_focal_l1_levels_bwd(const float* cls, const int64_t* labels, con
                                     int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
                                     const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox,
                                     int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream);
+/* The eight passes above with the focal form AND the box form as arguments; the entries above are box_form 0 and return the
+ * same bits through these.  focal_form 0 = EDL softmax-focal, 1 = sigmoid focal.  The box term of a row (what enters sums row 1):
+ *   box_form 0  l1    sum_j |pred_j - tgt_j| * bw_j on the encoded deltas; box_eps / box_linear / the coder are not read (may be NULL)
+ *   box_form 1  iou   w * -log(max(IoU, box_eps)), or w * (1 - max(IoU, box_eps)) when box_linear   (mmdet IoULoss, iou_loss.py:14-36)
+ *   box_form 2  giou  w * (1 - (IoU - (E - U) / E)), U = max(U, box_eps), E = max(E, box_eps)        (mmdet GIoULoss, iou_loss.py:87-102)
+ * with w = (bw_0 + bw_1 + bw_2 + bw_3) / 4.  A row with w == 0 is not evaluated: it adds exactly 0 and its four gradients are +0, whatever
+ * bbox_pred / bbox_tgt hold there (NaN and inf included).  Forms 1, 2 decode bbox_pred[r] and bbox_tgt[r] -- both encoded deltas, as for
+ * form 0 -- in the anchor-normalised frame: t = delta * stds4 + means4 (HOST float[4] each, stds > 0), centre (t0, t1), size
+ * (exp(clamp(t2)), exp(clamp(t3))), clamp to +-|ln(wh_ratio_clip)|, corners centre -+ size / 2; bbox_overlaps(is_aligned=True) of
+ * iou2d_calculator.py:212-260 on the two boxes.  IoU, and (E - U) / E, do not change under the per-axis scaling and translation that takes
+ * this frame to pixels, so no anchor is read.  Gradients: autograd's, through the decode; a tie of torch.max(a, b) / torch.min(a, b) hands
+ * each side half, clamp(min=m) passes where x >= m, the size clamp passes on [-|ln clip|, |ln clip|].  Needs bbox_pred (non-NULL) and
+ * 16-B aligned bbox_* for forms 1, 2. */
+int aod_focal_box_fwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                         float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                         const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                         int64_t nrows, int C, float gamma, float alpha,
+                         float* loss_noR, float* sums3, float* partials, aod_stream_t stream);
+int aod_focal_box_bwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                         float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                         const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                         int64_t nrows, int C, float gamma, float alpha,
+                         const float* g_cls, const float* g_bbox, const float* g_noR, float g_noR_scalar, int g_noR_is_scalar,
+                         void* grad_cls, void* grad_bbox, int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream);
+int aod_focal_box_levels_fwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                                const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                                int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                                float* loss_noR, float* sums, float* partials, const int32_t* num_pos, int num_images,
+                                float* divisors, float* num_total, aod_stream_t stream);
+int aod_focal_box_levels_bwd_ex(int focal_form, int box_form, float box_eps, int box_linear, const float* means4, const float* stds4,
+                                float wh_ratio_clip, const float* cls, const int64_t* labels, const float* label_w,
+                                const float* bbox_pred, const float* bbox_tgt, const float* bbox_w,
+                                int nlevels, const int64_t* level_rows, int C, float gamma, float alpha,
+                                const float* g_sums, const float* divisors, const float* g_noR_rows, void* grad_cls, void* grad_bbox,
+                                int out_bf16, int A, int pitch_cls, int pitch_box, aod_stream_t stream);
 /* FocalLoss.forward(reduction='none') (focal_loss.py:85): out[r][c] = l_c, or with grad_out the gradient grad_out[r][c] * d l_c / d x_c */
 int aod_sigmoid_focal_elem(const float* cls, const int64_t* labels, int64_t nrows, int C, float gamma, float alpha,
                            const float* grad_out, float* out, aod_stream_t stream);

@@ -71,6 +71,11 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                    help="track PPAL's per-class difficulty EMA while training (config key model.bbox_head.class_difficulty = dict(xi=0.6, "
                         'momentum=0.99, alpha=0.3, beta=0.2)); the Entropy / Margin / LeastConf / CCMS pools then weight every detection by its '
                         "class (class_weighted).  RetinaNet heads; each rank's EMA follows its own batches, rank 0's is used for the pool pass")
+    p.add_argument('--loss-bbox', choices=['L1', 'IoU', 'GIoU'], default=None,
+                   help='box regression loss of the RetinaNet heads: L1 on the encoded deltas, or IoU / GIoU on the decoded boxes (config keys '
+                        'model.bbox_head.loss_bbox and model.bbox_head.reg_decoded_bbox, set together); default: what the config says')
+    p.add_argument('--loss-bbox-weight', type=float, default=None,
+                   help='loss_weight of --loss-bbox (default: 1.0, or what the config says when --loss-bbox is not given)')
     p.add_argument('--candidate-factor', type=float, default=4.0,
                    help='CCMS pool: the candidate set holds ceil(factor x budget) of the most uncertain unlabelled images (default: 4)')
     p.add_argument('--max-objects', type=int, default=32,
@@ -166,6 +171,18 @@ def init_dist(launcher, backend='nccl', **kwargs):
     dist.init_process_group(backend=backend, **kwargs)
 
 
+def set_loss_bbox(cfg, loss_bbox, loss_weight=None):
+    """--loss-bbox / --loss-bbox-weight: the box loss and the space it is taken in are one choice -- L1 reads the encoded deltas,
+    IoU / GIoU the decoded boxes -- so model.bbox_head.loss_bbox and model.bbox_head.reg_decoded_bbox are written together."""
+    head = cfg.model.bbox_head
+    if loss_bbox:
+        head.loss_bbox = dict(type=loss_bbox + 'Loss', loss_weight=1.0 if loss_weight is None else float(loss_weight))
+        head.reg_decoded_bbox = loss_bbox != 'L1'
+    elif loss_weight is not None:
+        head.loss_bbox.loss_weight = float(loss_weight)
+    return cfg
+
+
 def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
     args = parse_args(default_config, default_size)
     cfg = Config.fromfile(args.config)
@@ -174,6 +191,7 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
     cfg.seed, cfg.onlyEval = seed, onlyEval
     if args.bbox_head:
         cfg.model.bbox_head.type = args.bbox_head
+    set_loss_bbox(cfg, args.loss_bbox, args.loss_bbox_weight)
     if args.uncertainty_pool == 'PPAL' or args.class_difficulty:
         cfg.model.bbox_head.class_difficulty = dict(CLASS_DIFFICULTY)
     str2unc = {'SACA': 'scaleAvg_classAvg', 'SSCS': 'scaleSum_classSum', 'SACS': 'scaleAvg_classSum', 'SSCA': 'scaleSum_classAvg'}
