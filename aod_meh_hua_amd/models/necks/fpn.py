@@ -49,10 +49,17 @@ class FPN(BaseModule):
         # (shared_input: a backbone stage output also feeds the next stage -- and C5 the first extra conv --: functional.GradAcc)
         laterals = [lc(inputs[i + self.start_level], shared_input=True) for i, lc in enumerate(self.lateral_convs)]
         n = len(laterals)
+        # ('on_lateral': the top lateral is a third time an input, of the first extra conv -- every consumer gets a handle of ONE fork)
+        on_lateral, lat_src = self.add_extra_convs == 'on_lateral' and self.num_outs > n, None
         for i in range(n - 1, 0, -1):
             # (a merged lateral feeds its own output conv AND the level below: AF.fork -- a no-op handle in the bf16 mode)
-            laterals[i], top = AF.fork(laterals[i], 2)
+            if on_lateral and i == n - 1:
+                laterals[i], top, lat_src = AF.fork(laterals[i], 3)
+            else:
+                laterals[i], top = AF.fork(laterals[i], 2)
             laterals[i - 1] = AF.upsample_add(laterals[i - 1], top)
+        if on_lateral and n == 1:                                 # (a single level: no level below)
+            laterals[0], lat_src = AF.fork(laterals[0], 2)
         # all output levels live in ONE pyramid buffer so that the head's level-batched convs read them in place
         from ...hipops import out_hw
         shapes = [(l.shape[0], l.shape[2], l.shape[3]) for l in laterals]
@@ -69,9 +76,9 @@ class FPN(BaseModule):
             if self.add_extra_convs == 'on_input':
                 src = inputs[self.backbone_end_level - 1]
             elif self.add_extra_convs == 'on_lateral':
-                src = laterals[-1]
+                src = lat_src
             else:
-                src = outs[-1]
+                outs[-1], src = AF.fork(outs[-1], 2)              # (the last backbone level's output: an output of the neck and the first extra conv's input)
             outs.append(self.fpn_convs[n](src, out=slots[n], shared_input=self.add_extra_convs == 'on_input'))
             for i in range(n + 1, self.num_outs):
                 outs[-1], src = AF.fork(outs[-1], 2)              # (an extra level is an output of the neck and the next extra conv's input)
