@@ -14,15 +14,20 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.cpp')))
 
 
+def headers():
+    """Every header a source can include: csrc/*.h plus the C-ABI header.  The one list behind the digest and the rebuild check, so a new
+    header cannot be missing from either."""
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + [os.path.join(HERE, '..', 'include', 'aod_hip.h')]
+
+
 def source_digest():
-    """sha256[:16] over the kernel sources + the C-ABI header: the tag that ties a committed PMC summary (profiles/pmc_*.json, written by
+    """sha256[:16] over the kernel sources + headers: the tag that ties a committed PMC summary (profiles/pmc_*.json, written by
     tools/profile/pmc_passes.sh) to the build it was measured on -- bench.py merges such a file into its line only when the tags agree."""
     import hashlib
     h = hashlib.sha256()
-    for f in sources() + [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pointwise.h'), os.path.join(CSRC, 'conv_x3p.h'), os.path.join(CSRC, 'conv_params.h'), os.path.join(HERE, '..', 'include', 'aod_hip.h')]:
-        if os.path.exists(f):
-            h.update(os.path.basename(f).encode())
-            h.update(open(f, 'rb').read())
+    for f in sources() + headers():
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, 'rb').read())
     return h.hexdigest()[:16]
 
 
@@ -30,9 +35,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pointwise.h'), os.path.join(CSRC, 'conv_x3p.h'), os.path.join(CSRC, 'conv_params.h'),
-                        os.path.join(HERE, '..', 'include', 'aod_hip.h')]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in sources() + headers())
 
 
 def build(force=False, verbose=True):

@@ -18,7 +18,7 @@
 // dead t1 region once conv2 is done; rounded to bf16 as the separate launch would store it -> the residual registers: identical bits, one launch
 // and 134 MB of residual traffic less (the twin of bottleneck_x3.hip's DS form).
 // LDS images use the 128-B-row XOR swizzle of conv.hip (slot s of row r holds 16-B chunk s ^ ((r >> 1) & 7)).
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -55,41 +55,22 @@ __device__ unsigned long long* g_bn_stamps = nullptr;
 #define BSTAMP(k) do {} while (0)
 #endif
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-// filter images: the paired-block row permutation (wrow) makes the 16 lanes of a fragment read rows {0-3, 8-11, 16-19, 24-27} (+4): rows r and
-// r + 16 share (r >> 1) & 7 and lie 2048 B apart -- the same banks.  One more row bit in the XOR key separates them (PMC before: 35 % of
-// the LDS cycles of the kernel were bank conflicts).
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-// Which output channel sits in MFMA row `lr` of 16-row block j.  The blocks are PAIRED: rows 4q .. 4q + 3 of block 2p are channels
-// 32p + 8q + 0..3 and of block 2p + 1 channels 32p + 8q + 4..7, so that in the transposed accumulators lane group q holds the 8
-// CONSECUTIVE channels 32p + 8q .. + 7 across the pair: intermediates, residual and output move in 16-B pieces.
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
-
 template <bool DS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void bottleneck64_fwd_kernel(const BnkArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   const int t = threadIdx.x, lane = t & 63;
   BSTAMP(0);
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int ty0 = (tt / p.tiles_x) * TH, tx0 = (tt % p.tiles_x) * TW;
   const long long img0 = (long long)b * p.H * p.W;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)((long long)p.B * p.H * p.W * p.Cin * 2), 0x00020000);
-  const auto rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, 64 * p.Cin * 2, 0x00020000);
-  const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, 64 * 576 * 2, 0x00020000);
-  const auto rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, 256 * 64 * 2, 0x00020000);
-  constexpr unsigned OOB = 0xf0000000u;
+  const auto rsrc_x = buf_rsrc(p.x, (int)((long long)p.B * p.H * p.W * p.Cin * 2));
+  const auto rsrc_w1 = buf_rsrc(p.w1, 64 * p.Cin * 2);
+  const auto rsrc_w2 = buf_rsrc(p.w2, 64 * 576 * 2);
+  const auto rsrc_w3 = buf_rsrc(p.w3, 256 * 64 * 2);
   // LDS-DMA lane roles: one wave-instruction fills 8 rows x 8 chunks; lane -> row (lane >> 3) of the group, slot lane & 7, source chunk
   // slot ^ ((row >> 1) & 7) -- the row groups a wave serves are 8 apart, so that chunk is the same for all of them
   const int drow = lane >> 3;
@@ -120,7 +101,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   const float* const vs1 = vec, * const vb1 = vec + 64, * const vs2 = vec + 128, * const vb2 = vec + 192, * const vs3 = vec + 256, * const vb3 = vec + 512;
   const float* const vsd = vec + 768, * const vbd = vec + 1024;
-  const auto rsrc_wd = __builtin_amdgcn_make_buffer_rsrc((void*)p.wd, 0, DS ? 256 * 64 * 2 : 0, 0x00020000);
+  const auto rsrc_wd = buf_rsrc(p.wd, DS ? 256 * 64 * 2 : 0);
 
   // ------------------------------------------------------------------ phase 1: t1 = relu(bn1(conv1(x))) on the halo
   unsigned xoff[6];
@@ -128,7 +109,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 6; ++i) {
     const int h = 8 * (uw + 8 * i) + drow;
     int y, x;
-    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * p.Cin + kc * 8) * 2) : OOB;
+    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * p.Cin + kc * 8) * 2) : BUF_OOB;
   }
   unsigned w1off = (unsigned)(((8 * uw + drow) * p.Cin + kcw * 8) * 2);
   const int nk1 = p.Cin >> 6;
@@ -201,18 +182,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // (branch-free: pixels outside the image get an out-of-range buffer offset -- a conditional load makes hipcc wait for each value
   // where the two paths merge, 32 serial L2 round trips per tile)
   const unsigned y_bytes = (unsigned)((long long)p.B * p.H * p.W * 256 * 2);
-  const auto rsrc_res = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, (int)y_bytes, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)y_bytes, 0x00020000);
+  const auto rsrc_res = buf_rsrc(p.res, (int)y_bytes);
+  const auto rsrc_y = buf_rsrc(p.y, (int)y_bytes);
   unsigned prow[2];         // byte offset of the lane's pixel row in [B*H*W][256] bf16
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int y = ty0 + 2 * uw + i, x = tx0 + lr;
-    prow[i] = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * 512) : OOB;
+    prow[i] = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * 512) : BUF_OOB;
   }
   // the residual tile (16-B pieces: 2 halves x 2 pixel rows x 4 channel groups per lane) is requested a few pieces per conv2 tap, so
   // that the address processing of these row-strided loads runs under the MFMAs instead of stalling the wave in one burst
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  u32x4_t rv[2][2][4];
+  u32x4 rv[2][2][4];
   BSTAMP(8);
   {
     char* t1 = smem + OFF_T1;
@@ -276,7 +256,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   BSTAMP(4);
   // DS: t1 is dead as well -- the downsample filter takes its place (it lands under the t2 epilogue; the barrier behind it drains the queue),
   // and the wave's 2 x 16 pixels of x are requested as fragments (lane = pixel lr, k-chunk lq)
-  u32x4_t xfr[2][2];
+  u32x4 xfr[2][2];
   if constexpr (DS) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -286,7 +266,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int y = ty0 + 2 * uw + i, x = tx0 + lr;
-      const unsigned xrow = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * 128) : OOB;
+      const unsigned xrow = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * 128) : BUF_OOB;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) xfr[i][ks] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)(xrow + (unsigned)((ks * 4 + lq) * 16)), 0, 0);
     }
@@ -344,7 +324,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[4 * h2 + r] = (bf16_t)(accd[i][2 * jp + h2][r] * sc[r] + sh[r]);
           }
-          rv[half][i][jp] = __builtin_bit_cast(u32x4_t, o);
+          rv[half][i][jp] = __builtin_bit_cast(u32x4, o);
         }
     }
     f32x4 acc3[2][8];
@@ -371,7 +351,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int jp = 0; jp < 4; ++jp) {
         const int c = half * 128 + jp * 32 + lq * 8;
-        const u32x4_t q = rv[half][i][jp];
+        const u32x4 q = rv[half][i][jp];
         bf16x8 o;
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
@@ -384,7 +364,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[4 * h2 + r] = (bf16_t)fmaxf(v[r], 0.f);
         }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
       }
   }
   BSTAMP(6);

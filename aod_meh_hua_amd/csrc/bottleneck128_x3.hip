@@ -18,10 +18,10 @@
 //            tail stores.
 // Optional outputs t1 / t2 (interior pixels, X rows): with them the launch is the forward of a training step -- the three convs are then
 // recorded as autograd nodes around its outputs (functional.conv_bn_act(pre=...)) and the backward pass is unchanged.
-// Products are computed transposed (filter fragment = the MFMA's A operand) with the paired-block row permutation of bottleneck.hip, so a
+// Products are computed transposed (filter fragment = the MFMA's A operand) with the paired-block row permutation (wrow, tile_prims.h), so a
 // lane holds 8 consecutive channels of one pixel and every intermediate / residual / output piece is 16 B.  Same products in the same order
 // per accumulator, same fp32 epilogue arithmetic and the same head / tail roundings as the three conv_igemm_kernel<X3> launches: identical bits.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -53,7 +53,6 @@ constexpr int OFF_VEC = OFF_T1 + 4 * T1SUB;                              // 157 
 constexpr int LDS_BYTES = OFF_VEC + (4 * P + 2 * 4 * P) * 4;             // 163 840 = all of the CU's LDS
 constexpr int NS2 = 36, NS = NS2 + 16;                                   // ring steps: conv2, then conv3
 static_assert(3 * STG1 <= OFF_VEC && 4 * T2SUB <= 4 * T1SUB && LDS_BYTES <= 160 * 1024, "LDS map");
-constexpr unsigned OOB = 0xf0000000u;
 
 #ifdef AOD_TILE_TIMING
 // debug build only (tools/dbg/b128x3_timing.py): per-workgroup wall-clock stamps (100 MHz) at the phase boundaries
@@ -66,30 +65,6 @@ __device__ unsigned long long* g_bw3_stamps = nullptr;
 #define TICK() 0ull
 #define TACC(acc, a, b) do {} while (0)
 #endif
-
-#define AOD_VMCASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-__device__ __forceinline__ void wait_vm_dyn(int n) {      // n is wave-uniform
-  switch (n) {
-    AOD_VMCASE(0) AOD_VMCASE(4) AOD_VMCASE(5) AOD_VMCASE(6) AOD_VMCASE(8) AOD_VMCASE(12) AOD_VMCASE(16) AOD_VMCASE(18) AOD_VMCASE(20) AOD_VMCASE(22) AOD_VMCASE(24)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-#undef AOD_VMCASE
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& l) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { h[j] = (bf16_t)v[j]; l[j] = (bf16_t)(v[j] - (float)h[j]); }
-}
 
 // Vector-memory operations of one wave in phases 2 / 3, in issue order (S = a ring slice, 2 instructions; the optional outputs are ALWAYS
 // issued -- through an empty descriptor when the tensor is not wanted -- so the counts hold for every launch):
@@ -112,25 +87,6 @@ __device__ __forceinline__ int wait_of(int s) {
   return kg == 0 ? 12 : (kg == 3 ? 4 + R : 12 + R);
 }
 
-// bit j of the result: element j of the 16-B piece (8 bf16 heads) is > 0 -- the ReLU mask of 8 channels in 8 bits
-__device__ __forceinline__ unsigned pos_bits(const u32x4_t q) {
-  unsigned m = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    m |= (__uint_as_float(q[w] << 16) > 0.f ? 1u : 0u) << (2 * w);
-    m |= (__uint_as_float(q[w] & 0xffff0000u) > 0.f ? 1u : 0u) << (2 * w + 1);
-  }
-  return m;
-}
-// sum over the 16 lanes that share lq (one DPP row): four rotate-and-add steps on the vector ALU, every lane ends up with the total
-template <int N> __device__ __forceinline__ float row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum_lr(float v) {
-  v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v);
-  return v;
-}
-
 // BWD: the same three products are the block's DGRAD chain (csrc/conv.hip dgrad epilogue semantics: result = mask > 0 ? acc (+ res) : 0,
 // fp32 column sums of the results): x = the finished gradient G of the block output, w1 / w2 / w3 = the scale-folded X dgrad filters of
 // conv3 / conv2 / conv1, t1 / t2 / y = the gradients of forward t2 / t1 / x, residual = G (the skip branch).
@@ -142,20 +98,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int lr = lane & 15, lq = lane >> 4;
   const int wp = uw >> 1, wc = uw & 1;                    // wave grid: 4 (pixel row pairs) x 2 (output-channel halves)
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int ty0 = (tt / p.tiles_x) * TH, tx0 = (tt % p.tiles_x) * TW;
   const long long img0 = (long long)b * p.H * p.W;
   const long long npix = (long long)p.B * p.H * p.W;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(npix * XC * 2), 0x00020000);
-  const auto rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, P * XC * 2, 0x00020000);
-  const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, P * 9 * XP * 2, 0x00020000);
-  const auto rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, 4 * P * XP * 2, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)(npix * XC * 2), 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)(npix * XC * 2));
+  const auto rsrc_w1 = buf_rsrc(p.w1, P * XC * 2);
+  const auto rsrc_w2 = buf_rsrc(p.w2, P * 9 * XP * 2);
+  const auto rsrc_w3 = buf_rsrc(p.w3, 4 * P * XP * 2);
+  const auto rsrc_y = buf_rsrc(p.y, (int)(npix * XC * 2));
   // the optional outputs through descriptors that are EMPTY when the tensor is not wanted: the stores are always issued (the counted waits
   // rely on that) and dropped by the range check
-  const auto rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, p.t1 ? (int)(npix * XP * 2) : 0, 0x00020000);
-  const auto rsrc_t2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, p.t2 ? (int)(npix * XP * 2) : 0, 0x00020000);
+  const auto rsrc_t1 = buf_rsrc(p.t1, p.t1 ? (int)(npix * XP * 2) : 0);
+  const auto rsrc_t2 = buf_rsrc(p.t2, p.t2 ? (int)(npix * XP * 2) : 0);
 
   // LDS-DMA lane roles (bottleneck.hip): one wave-instruction fills 8 rows x 8 slots; lane -> row (lane >> 3) of its group, slot lane & 7,
   // source chunk slot ^ key(row); a wave serves row groups uw + 8 i, for which the keys are the same
@@ -188,16 +144,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   WSTAMP(0);
   // ------------------------------------------------------------------ phase 1: t1 = relu(bn1(conv1(x))) on the halo
-  const auto rsrc_m1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m1, 0, BWD ? (int)(npix * XP * 2) : 0, 0x00020000);
-  const auto rsrc_m2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m2, 0, BWD ? (int)(npix * XP * 2) : 0, 0x00020000);
-  const auto rsrc_m3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m3, 0, BWD ? (int)(npix * XC * 2) : 0, 0x00020000);
-  u32x4_t mk1[3][2];                               // BWD: head pieces of the masks of this lane's halo pixels (out-of-image pixels read 0 = masked)
+  const auto rsrc_m1 = buf_rsrc(p.m1, BWD ? (int)(npix * XP * 2) : 0);
+  const auto rsrc_m2 = buf_rsrc(p.m2, BWD ? (int)(npix * XP * 2) : 0);
+  const auto rsrc_m3 = buf_rsrc(p.m3, BWD ? (int)(npix * XC * 2) : 0);
+  u32x4 mk1[3][2];                               // BWD: head pieces of the masks of this lane's halo pixels (out-of-image pixels read 0 = masked)
   if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int h = (3 * wp + i) * 16 + lr;
       int y, x;
-      const unsigned hrow = halo_pix(h, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : OOB;
+      const unsigned hrow = halo_pix(h, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : BUF_OOB;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) mk1[i][jp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m1, (int)(hrow + (unsigned)((2 * wc + jp) * 128 + lq * 16)), 0, 0);
     }
@@ -207,7 +163,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 3; ++i) {
     const int h = 8 * (uw + 8 * i) + drow;
     int y, x;
-    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * XC + kc * 8) * 2) : OOB;
+    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * XC + kc * 8) * 2) : BUF_OOB;
   }
   unsigned w1off[2];
 #pragma unroll
@@ -220,7 +176,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     char* xs = smem + buf * STG1;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      const unsigned off = xoff[i];               // (an OOB row stays out of range)
+      const unsigned off = xoff[i];               // (an BUF_OOB row stays out of range)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(xs + (uw + 8 * i) * 1024), 16, off, kt * 128, 0, 0);
     }
 #pragma unroll
@@ -346,7 +302,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   issue_slice(3);
   __builtin_amdgcn_sched_barrier(0);
   // epilogue 1: t1 -> LDS (zero outside the image) and, for the tile's own pixels, -> global (training forward)
-  u32x4_t mk2[2][2];                              // BWD: mask pieces of the second epilogue (forward t1 at the tile's own pixels)
+  u32x4 mk2[2][2];                              // BWD: mask pieces of the second epilogue (forward t1 at the tile's own pixels)
   {
     char* t1 = smem + OFF_T1;
     float cs1v[2][8] = {};
@@ -357,7 +313,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const bool ok = halo_pix(h, y, x);
       const int hy = h / HW_, hx = h - hy * HW_;
       const bool inner = ok && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW;
-      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : OOB;
+      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : BUF_OOB;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         const int c = 64 * wc + 32 * jp + lq * 8;
@@ -386,15 +342,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           *reinterpret_cast<bf16x8*>(t1 + (2 * wc + jp) * T1SUB + swz(h, 4 + lq)) = ol;
         }
         const unsigned col = (unsigned)((2 * wc + jp) * 128 + lq * 16);      // byte offset of the 8 heads of channel group 2 wc + jp in an X row
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, oh), rsrc_t1, (int)(grow + col), 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ol), rsrc_t1, (int)(grow + col + 64u), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oh), rsrc_t1, (int)(grow + col), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ol), rsrc_t1, (int)(grow + col + 64u), 0, 0);
       }
     }
     if constexpr (BWD) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int y = ty0 + 2 * wp + i, x = tx0 + lr;
-        const unsigned r2 = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : OOB;
+        const unsigned r2 = (y < p.H && x < p.W) ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : BUF_OOB;
 #pragma unroll
         for (int jp = 0; jp < 2; ++jp) mk2[i][jp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m2, (int)(r2 + (unsigned)((2 * wc + jp) * 128 + lq * 16)), 0, 0);
       }
@@ -489,8 +445,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 2; ++i) {
       const int y = ty0 + 2 * wp + i, x = tx0 + lr;
       const bool ok = y < p.H && x < p.W;
-      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (XC * 2)) : OOB;
-      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : OOB;
+      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (XC * 2)) : BUF_OOB;
+      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (XP * 2)) : BUF_OOB;
       const int o_ = (2 * wp + i) * 16 + lr;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
@@ -518,8 +474,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         *reinterpret_cast<bf16x8*>(t2 + (2 * wc + jp) * T2SUB + swz(o_, lq)) = oh;
         *reinterpret_cast<bf16x8*>(t2 + (2 * wc + jp) * T2SUB + swz(o_, 4 + lq)) = ol;
         const unsigned col = (unsigned)((2 * wc + jp) * 128 + lq * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, oh), rsrc_t2, (int)(grow + col), 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ol), rsrc_t2, (int)(grow + col + 64u), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oh), rsrc_t2, (int)(grow + col), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ol), rsrc_t2, (int)(grow + col + 64u), 0, 0);
       }
     }
     if constexpr (BWD) {
@@ -554,7 +510,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc3[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4_t rh[2][2], rl[2][2], mk3[2][2];
+    u32x4 rh[2][2], rl[2][2], mk3[2][2];
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
       const int s = NS2 + n3 * 4 + kg;
@@ -595,7 +551,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         const int c = n3 * 128 + 64 * wc + 32 * jp + lq * 8;
-        const u32x4_t qh = rh[i][jp], ql = rl[i][jp];
+        const u32x4 qh = rh[i][jp], ql = rl[i][jp];
         float v[8];
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
@@ -623,8 +579,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         bf16x8 oh, ol;
         split8(v, oh, ol);
         const unsigned col = (unsigned)((n3 * 4 + 2 * wc + jp) * 128 + lq * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, oh), rsrc_y, (int)(prow[i] + col), 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ol), rsrc_y, (int)(prow[i] + col + 64u), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oh), rsrc_y, (int)(prow[i] + col), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ol), rsrc_y, (int)(prow[i] + col + 64u), 0, 0);
       }
     if constexpr (BWD) {
 #pragma unroll

@@ -11,11 +11,11 @@
 //            5-slot ring (4 in flight, counted s_waitcnt vmcnt + one raw s_barrier per step); t2 = relu(bn2(.)) -> LDS;
 //   phase 3  conv3 in four chunks of 128 output channels, K = 128 from t2 in LDS, 32-KB filter chunks through a 3-slot ring;
 //            epilogue in registers: + residual (requested before the first chunk), ReLU, 16-B stores.
-// All products are computed transposed with the paired-block row permutation of bottleneck.hip: a lane holds 8 consecutive channels of
+// All products are computed transposed with the paired-block row permutation (wrow, tile_prims.h): a lane holds 8 consecutive channels of
 // one pixel.  Optional outputs t1 / t2 (the block's two intermediates, interior pixels only): with them the kernel is the FORWARD of a
 // training step as well (the backward pass reads them); without (null) nothing but y leaves the CU.
 // Same bf16 rounding points and the same K order per output element as the three-launch block.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -51,7 +51,6 @@ constexpr int W2SLOT = P * 128, W2R = 5;                                 // phas
 constexpr int OFF_T2 = 0, T2SUB = TH * TW * 128;                         // t2 [2][128][128 B] = 32 768 over the dead ring
 constexpr int OFF_W3 = 2 * T2SUB, W3SLOT = 2 * P * 128, W3R = 3;         // 32 768 .. 131 072: three 32-KB conv3 filter chunks
 static_assert(W2R * W2SLOT <= OFF_T1 && OFF_W3 + W3R * W3SLOT <= OFF_VEC && LDS_BYTES <= 160 * 1024, "LDS map");
-constexpr unsigned OOB = 0xf0000000u;
 
 #ifdef AOD_TILE_TIMING
 // debug build only (tools/dbg/wide_timing.py): per-workgroup wall-clock stamps (100 MHz) at the phase boundaries
@@ -60,48 +59,6 @@ __device__ unsigned long long* g_bnw_stamps = nullptr;
 #else
 #define WSTAMP(k) do {} while (0)
 #endif
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define AOD_VMCASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-__device__ __forceinline__ void wait_vm_dyn(int n) {      // n is wave-uniform
-  switch (n) {
-    AOD_VMCASE(0) AOD_VMCASE(1) AOD_VMCASE(2) AOD_VMCASE(3) AOD_VMCASE(4) AOD_VMCASE(5) AOD_VMCASE(6) AOD_VMCASE(7) AOD_VMCASE(8)
-    AOD_VMCASE(9) AOD_VMCASE(10) AOD_VMCASE(11) AOD_VMCASE(12) AOD_VMCASE(13) AOD_VMCASE(14) AOD_VMCASE(15) AOD_VMCASE(16)
-    AOD_VMCASE(17) AOD_VMCASE(18) AOD_VMCASE(19) AOD_VMCASE(20) AOD_VMCASE(21) AOD_VMCASE(22) AOD_VMCASE(23) AOD_VMCASE(24)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-#undef AOD_VMCASE
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// bit j of the result: element j of the 16-B piece (8 bf16) is > 0 -- the ReLU mask of 8 channels in 8 bits
-__device__ __forceinline__ unsigned pos_bits(const u32x4_t q) {
-  unsigned m = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    m |= (__uint_as_float(q[w] << 16) > 0.f ? 1u : 0u) << (2 * w);
-    m |= (__uint_as_float(q[w] & 0xffff0000u) > 0.f ? 1u : 0u) << (2 * w + 1);
-  }
-  return m;
-}
-// sum over the 16 lanes that share lq (the lanes of one pixel block that hold the same 8 channels) = one DPP row: four rotate-and-add steps
-// on the vector ALU, every lane ends up with the total (__shfl_xor would be four ds_bpermute round trips through the LDS pipe per value)
-template <int N> __device__ __forceinline__ float row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum_lr(float v) {
-  v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v);
-  return v;
-}
 
 // BWD: the same three products are the block's DGRAD chain (csrc/conv.hip dgrad epilogue semantics: result = mask > 0 ? acc (+ res) : 0,
 // fp32 column sums of the results): x = the finished gradient G of the block output, w1 / w2 / w3 = the scale-folded dgrad filters of
@@ -114,20 +71,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int lr = lane & 15, lq = lane >> 4;
   const int wp = uw >> 1, wc = uw & 1;                    // wave grid: 4 (pixel rows) x 2 (output channels)
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int ty0 = (tt / p.tiles_x) * TH, tx0 = (tt % p.tiles_x) * TW;
   const long long img0 = (long long)b * p.H * p.W;
   const long long npix = (long long)p.B * p.H * p.W;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(npix * CIN * 2), 0x00020000);
-  const auto rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, P * CIN * 2, 0x00020000);
-  const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, P * 9 * P * 2, 0x00020000);
-  const auto rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, CIN * P * 2, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)(npix * CIN * 2), 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)(npix * CIN * 2));
+  const auto rsrc_w1 = buf_rsrc(p.w1, P * CIN * 2);
+  const auto rsrc_w2 = buf_rsrc(p.w2, P * 9 * P * 2);
+  const auto rsrc_w3 = buf_rsrc(p.w3, CIN * P * 2);
+  const auto rsrc_y = buf_rsrc(p.y, (int)(npix * CIN * 2));
   // the optional outputs through descriptors that are EMPTY when the tensor is not wanted: the stores are always issued (the counted waits
   // below rely on that) and dropped by the range check
-  const auto rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, p.t1 ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_t2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, p.t2 ? (int)(npix * P * 2) : 0, 0x00020000);
+  const auto rsrc_t1 = buf_rsrc(p.t1, p.t1 ? (int)(npix * P * 2) : 0);
+  const auto rsrc_t2 = buf_rsrc(p.t2, p.t2 ? (int)(npix * P * 2) : 0);
 
   // LDS-DMA lane roles: one wave-instruction fills 8 rows x 8 slots; lane -> row (lane >> 3) of its group, slot lane & 7, source chunk
   // slot ^ key(row); a wave serves row groups uw + 8 i, for which the keys are the same
@@ -162,16 +119,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   WSTAMP(0);
 
   // ------------------------------------------------------------------ phase 1: t1 = relu(bn1(conv1(x))) on the halo
-  const auto rsrc_m1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m1, 0, BWD ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_m2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m2, 0, BWD ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_m3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m3, 0, BWD ? (int)(npix * CIN * 2) : 0, 0x00020000);
-  u32x4_t mk1[3][2];                               // BWD: mask pieces of this lane's halo pixels (out-of-image pixels read 0 = masked)
+  const auto rsrc_m1 = buf_rsrc(p.m1, BWD ? (int)(npix * P * 2) : 0);
+  const auto rsrc_m2 = buf_rsrc(p.m2, BWD ? (int)(npix * P * 2) : 0);
+  const auto rsrc_m3 = buf_rsrc(p.m3, BWD ? (int)(npix * CIN * 2) : 0);
+  u32x4 mk1[3][2];                               // BWD: mask pieces of this lane's halo pixels (out-of-image pixels read 0 = masked)
   if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int h = (3 * wp + i) * 16 + lr;
       int y, x;
-      const unsigned hrow = halo_pix(h, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      const unsigned hrow = halo_pix(h, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) mk1[i][jp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m1, (int)(hrow + (unsigned)((64 * wc + 32 * jp + lq * 8) * 2)), 0, 0);
     }
@@ -181,7 +138,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 3; ++i) {
     const int h = 8 * (uw + 8 * i) + drow;
     int y, x;
-    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * CIN + kc * 8) * 2) : OOB;
+    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * CIN + kc * 8) * 2) : BUF_OOB;
   }
   unsigned w1off[2];
 #pragma unroll
@@ -192,7 +149,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 3; ++i) {
       const unsigned off = xoff[i];
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(xs + (uw + 8 * i) * 1024), 16, off, 0, 0, 0);
-      xoff[i] += 128;                                  // (an OOB row stays out of range)
+      xoff[i] += 128;                                  // (an BUF_OOB row stays out of range)
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -245,7 +202,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const bool ok = halo_pix(h, y, x);
       const int hy = h / HW_, hx = h - hy * HW_;
       const bool inner = ok && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW;
-      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         const int c = 64 * wc + 32 * jp + lq * 8;
@@ -269,7 +226,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         }
         *reinterpret_cast<bf16x8*>(t1 + wc * T1SUB + swz(h, jp * 4 + lq)) = o;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_t1, (int)(grow + (unsigned)(c * 2)), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_t1, (int)(grow + (unsigned)(c * 2)), 0, 0);
       }
     }
     if constexpr (BWD) {
@@ -286,14 +243,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   WSTAMP(2);
   // BWD: the masks of the two later epilogues, requested ahead of the filter ring (older than every ring load: in-order return has them
   // in registers by the first counted wait); the third one (forward x, 16 pieces) is boiled down to a bit per element after the loop
-  u32x4_t mk2[2][2], mk3[2][4][2];
+  u32x4 mk2[2][2], mk3[2][4][2];
   if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int y = ty0 + 2 * wp + i, x = tx0 + lr;
       const bool ok = y < p.H && x < p.W;
       const long long pix = img0 + (long long)y * p.W + x;
-      const unsigned r2 = ok ? (unsigned)(pix * (P * 2)) : OOB, r3 = ok ? (unsigned)(pix * (CIN * 2)) : OOB;
+      const unsigned r2 = ok ? (unsigned)(pix * (P * 2)) : BUF_OOB, r3 = ok ? (unsigned)(pix * (CIN * 2)) : BUF_OOB;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         mk2[i][jp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m2, (int)(r2 + (unsigned)((64 * wc + 32 * jp + lq * 8) * 2)), 0, 0);
@@ -372,8 +329,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 2; ++i) {
       const int y = ty0 + 2 * wp + i, x = tx0 + lr;
       const bool ok = y < p.H && x < p.W;
-      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (CIN * 2)) : OOB;
-      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (CIN * 2)) : BUF_OOB;
+      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
       const int o_ = (2 * wp + i) * 16 + lr;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
@@ -398,7 +355,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         }
         *reinterpret_cast<bf16x8*>(t2 + wc * T2SUB + swz(o_, jp * 4 + lq)) = o;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_t2, (int)(grow + (unsigned)(c * 2)), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_t2, (int)(grow + (unsigned)(c * 2)), 0, 0);
       }
     }
     if constexpr (BWD) {
@@ -416,7 +373,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   WSTAMP(4);
   // ------------------------------------------------------------------ phase 3: y = relu(bn3(conv3(t2)) + x), 4 chunks of 128 output channels
   // residual pieces of the whole tile row pair (16 B each: [pixel row i][chunk][channel pair jp]), requested ahead of the filter chunks
-  u32x4_t rv[2][4][2];
+  u32x4 rv[2][4][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -469,7 +426,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         const int c = n3 * 128 + 64 * wc + 32 * jp + lq * 8;
-        const u32x4_t q = rv[i][n3][jp];
+        const u32x4 q = rv[i][n3][jp];
         bf16x8 o;
         if constexpr (BWD) {
           const unsigned mb = mb3[i][jp] >> (8 * n3);
@@ -499,7 +456,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[4 * h2 + r] = (bf16_t)fmaxf(v[r], 0.f);
         }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
       }
     if constexpr (BWD) {
 #pragma unroll
@@ -553,18 +510,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int ty0 = (tt / p.tiles_x) * TH, tx0 = (tt % p.tiles_x) * TW;
   const long long img0 = (long long)b * p.H * p.W;
   const long long npix = (long long)p.B * p.H * p.W;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(npix * CIN * 2), 0x00020000);
-  const auto rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, P * CIN * 2, 0x00020000);
-  const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, P * 9 * P * 2, 0x00020000);
-  const auto rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, CIN * P * 2, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)(npix * CIN * 2), 0x00020000);
-  const auto rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, p.t1 ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_t2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, p.t2 ? (int)(npix * P * 2) : 0, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)(npix * CIN * 2));
+  const auto rsrc_w1 = buf_rsrc(p.w1, P * CIN * 2);
+  const auto rsrc_w2 = buf_rsrc(p.w2, P * 9 * P * 2);
+  const auto rsrc_w3 = buf_rsrc(p.w3, CIN * P * 2);
+  const auto rsrc_y = buf_rsrc(p.y, (int)(npix * CIN * 2));
+  const auto rsrc_t1 = buf_rsrc(p.t1, p.t1 ? (int)(npix * P * 2) : 0);
+  const auto rsrc_t2 = buf_rsrc(p.t2, p.t2 ? (int)(npix * P * 2) : 0);
   const int drow = lane >> 3;
   const int kc = (lane & 7) ^ ((4 * (uw & 1) + (lane >> 4)) & 7);
   const int kcw = kc ^ (((uw >> 1) & 1) << 1);
@@ -583,15 +540,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // ------------------------------------------------------------------ phase 1
   const int cw = 32 * uw + lq * 8;                 // this lane's 8 consecutive channels (within P, and within a 256-channel conv3 chunk)
-  const auto rsrc_m1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m1, 0, BWD ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_m2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m2, 0, BWD ? (int)(npix * P * 2) : 0, 0x00020000);
-  const auto rsrc_m3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.m3, 0, BWD ? (int)(npix * CIN * 2) : 0, 0x00020000);
-  u32x4_t mk1[7];
+  const auto rsrc_m1 = buf_rsrc(p.m1, BWD ? (int)(npix * P * 2) : 0);
+  const auto rsrc_m2 = buf_rsrc(p.m2, BWD ? (int)(npix * P * 2) : 0);
+  const auto rsrc_m3 = buf_rsrc(p.m3, BWD ? (int)(npix * CIN * 2) : 0);
+  u32x4 mk1[7];
   if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       int y, x;
-      const unsigned hrow = halo_pix(i * 16 + lr, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      const unsigned hrow = halo_pix(i * 16 + lr, y, x) ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
       mk1[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m1, (int)(hrow + (unsigned)(cw * 2)), 0, 0);
     }
   }
@@ -600,7 +557,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 2; ++i) {
     const int h = 8 * (uw + 8 * i) + drow;
     int y, x;
-    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * CIN + kc * 8) * 2) : OOB;
+    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * CIN + kc * 8) * 2) : BUF_OOB;
   }
   unsigned w1off[4];
 #pragma unroll
@@ -663,7 +620,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const bool ok = halo_pix(h, y, x);
       const int hy = h / HW_, hx = h - hy * HW_;
       const bool inner = ok && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW;
-      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      const unsigned grow = inner ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
       bf16x8 o;
       if constexpr (BWD) {
         const unsigned mb = pos_bits(mk1[i]);
@@ -684,7 +641,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       }
       *reinterpret_cast<bf16x8*>(t1 + (uw >> 1) * T1SUB + swz(h, (uw & 1) * 4 + lq)) = o;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_t1, (int)(grow + (unsigned)(cw * 2)), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_t1, (int)(grow + (unsigned)(cw * 2)), 0, 0);
     }
     if constexpr (BWD) {
 #pragma unroll
@@ -696,14 +653,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   __syncthreads();
   WSTAMP(2);
-  u32x4_t mk2[4], mk3[4][4];                       // BWD: masks of the two later epilogues, requested ahead of the filter ring
+  u32x4 mk2[4], mk3[4][4];                       // BWD: masks of the two later epilogues, requested ahead of the filter ring
   if constexpr (BWD) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int y = ty0 + i, x = tx0 + lr;
       const bool ok = y < p.H && x < p.W;
       const long long pix = img0 + (long long)y * p.W + x;
-      const unsigned r2 = ok ? (unsigned)(pix * (P * 2)) : OOB, r3 = ok ? (unsigned)(pix * (CIN * 2)) : OOB;
+      const unsigned r2 = ok ? (unsigned)(pix * (P * 2)) : BUF_OOB, r3 = ok ? (unsigned)(pix * (CIN * 2)) : BUF_OOB;
       mk2[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m2, (int)(r2 + (unsigned)(cw * 2)), 0, 0);
 #pragma unroll
       for (int n3 = 0; n3 < 4; ++n3) mk3[i][n3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m3, (int)(r3 + (unsigned)((n3 * 256 + cw) * 2)), 0, 0);
@@ -775,8 +732,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 4; ++i) {
       const int y = ty0 + i, x = tx0 + lr;
       const bool ok = y < p.H && x < p.W;
-      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (CIN * 2)) : OOB;
-      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : OOB;
+      prow[i] = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (CIN * 2)) : BUF_OOB;
+      const unsigned grow = ok ? (unsigned)((img0 + (long long)y * p.W + x) * (P * 2)) : BUF_OOB;
       bf16x8 o;
       if constexpr (BWD) {
         const unsigned mb = pos_bits(mk2[i]);
@@ -797,7 +754,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       }
       *reinterpret_cast<bf16x8*>(t2 + (uw >> 1) * T2SUB + swz(i * 16 + lr, (uw & 1) * 4 + lq)) = o;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_t2, (int)(grow + (unsigned)(cw * 2)), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_t2, (int)(grow + (unsigned)(cw * 2)), 0, 0);
     }
     if constexpr (BWD) {
 #pragma unroll
@@ -817,7 +774,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   WSTAMP(4);
   // ------------------------------------------------------------------ phase 3: 4 chunks of 256 output channels x 4 K quarters
   const float* const vs3 = reinterpret_cast<const float*>(smem + OFF_VEC3), * const vb3 = vs3 + 1024;
-  u32x4_t rv[4][4];
+  u32x4 rv[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -872,7 +829,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int c = n3 * 256 + cw;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const u32x4_t q = rv[i][n3];
+          const u32x4 q = rv[i][n3];
           bf16x8 o;
           if constexpr (BWD) {
             const unsigned mb = mb3[i] >> (8 * n3);
@@ -902,7 +859,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[4 * h2 + r] = (bf16_t)fmaxf(v[r], 0.f);
           }
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_y, (int)(prow[i] + (unsigned)(c * 2)), 0, 0);
         }
       }
       slot = slot == WR - 1 ? 0 : slot + 1;

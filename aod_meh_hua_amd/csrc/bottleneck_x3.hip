@@ -17,9 +17,9 @@
 // as well instead of being written (268 MB at 16 x 128 x 128) by a launch of its own and read back: per half of 128 output channels, the
 // wave's 16 pixels of x (fragments straight from global memory: L2 hits, the halo tile was just read) against half of the X filter [256][128]
 // staged in a 32 KB LDS region of its own; BN, rounding to head + tail as the separate launch would store it -> the residual registers.
-// Products are computed transposed (filter fragment = the MFMA's A operand) with the paired-block row permutation of bottleneck.hip, so a
+// Products are computed transposed (filter fragment = the MFMA's A operand) with the paired-block row permutation (wrow, tile_prims.h), so a
 // lane holds 8 consecutive channels of one pixel and every intermediate / residual / output piece is 16 B.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -50,7 +50,6 @@ constexpr int SLOT = 8192;                             // conv2 filter ring: 8 s
 constexpr int W3SUB = 256 * 128;                       // conv3 filter: 2 sub-images [256][128 B] over the ring
 static_assert(OFF_W1 + 2 * 8192 <= OFF_T1 && 8 * SLOT <= OFF_T1 && 2 * W3SUB <= OFF_T1 && 2 * T2SUB <= 2 * T1SUB && LDS_BYTES_DS <= 160 * 1024, "LDS map");
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 #ifdef AOD_TILE_TIMING
 __device__ unsigned long long* g_b64_stamps = nullptr;      // debug build (tools/dbg/b64x3_timing.py): phase stamps of every tile, 100 MHz wall clock
 #define BSTAMP(k) do { if (g_b64_stamps && threadIdx.x == 0) g_b64_stamps[(size_t)blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
@@ -58,42 +57,26 @@ __device__ unsigned long long* g_b64_stamps = nullptr;      // debug build (tool
 #define BSTAMP(k) do {} while (0)
 #endif
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
-
-// v[8] -> head and tail pieces
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& l) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { h[j] = (bf16_t)v[j]; l[j] = (bf16_t)(v[j] - (float)h[j]); }
-}
-
 template <bool DS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void bottleneck64x3_fwd_kernel(const Bnx3Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   const int t = threadIdx.x, lane = t & 63;
   BSTAMP(0);
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int ty0 = (tt / p.tiles_x) * TH, tx0 = (tt % p.tiles_x) * TW;
   const long long img0 = (long long)b * p.H * p.W;
   const long long npix = (long long)p.B * p.H * p.W;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(npix * p.CP * 2), 0x00020000);
-  const auto rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, 64 * p.CP * 2, 0x00020000);
-  const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, 64 * 9 * 128 * 2, 0x00020000);
-  const auto rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, 256 * 128 * 2, 0x00020000);
-  const auto rsrc_res = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.x : p.res), 0, DS ? (int)(npix * p.CP * 2) : (int)(npix * 1024), 0x00020000);
-  const auto rsrc_wd = __builtin_amdgcn_make_buffer_rsrc((void*)p.wd, 0, DS ? 256 * 128 * 2 : 0, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)(npix * 1024), 0x00020000);
-  constexpr unsigned OOB = 0xf0000000u;
+  const auto rsrc_x = buf_rsrc(p.x, (int)(npix * p.CP * 2));
+  const auto rsrc_w1 = buf_rsrc(p.w1, 64 * p.CP * 2);
+  const auto rsrc_w2 = buf_rsrc(p.w2, 64 * 9 * 128 * 2);
+  const auto rsrc_w3 = buf_rsrc(p.w3, 256 * 128 * 2);
+  const auto rsrc_res = buf_rsrc(DS ? p.x : p.res, DS ? (int)(npix * p.CP * 2) : (int)(npix * 1024));
+  const auto rsrc_wd = buf_rsrc(p.wd, DS ? 256 * 128 * 2 : 0);
+  const auto rsrc_y = buf_rsrc(p.y, (int)(npix * 1024));
   // LDS-DMA lane roles (bottleneck.hip): one wave-instruction fills 8 rows x 8 chunks; lane -> row (lane >> 3) of the group, slot lane & 7
   const int drow = lane >> 3;
   const int kc = (lane & 7) ^ ((4 * (uw & 1) + (lane >> 4)) & 7);
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 3; ++i) {
     const int h = 8 * (uw + 8 * i) + drow;
     int y, x;
-    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * p.CP + kc * 8) * 2) : OOB;
+    xoff[i] = halo_pix(h, y, x) ? (unsigned)(((img0 + (long long)y * p.W + x) * p.CP + kc * 8) * 2) : BUF_OOB;
   }
   unsigned w1off = (unsigned)(((8 * uw + drow) * p.CP + kcw * 8) * 2);
   const int nk1 = p.CP >> 6;
@@ -315,8 +298,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   // residual pieces of the first half (x was just read by this XCD: L2 hits); 16-B heads and tails of the lane's 8 channels
   const int oy = ty0 + uw, ox = tx0 + lr;
-  const unsigned prow = (oy < p.H && ox < p.W) ? (unsigned)((img0 + (long long)oy * p.W + ox) * 1024) : OOB;
-  u32x4_t rh[4], rl[4];
+  const unsigned prow = (oy < p.H && ox < p.W) ? (unsigned)((img0 + (long long)oy * p.W + ox) * 1024) : BUF_OOB;
+  u32x4 rh[4], rl[4];
   auto load_res = [&](int half) {
 #pragma unroll
     for (int jp = 0; jp < 4; ++jp) {
@@ -327,9 +310,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   };
   // DS: the wave's 16 pixels of x as MFMA fragments (lane = pixel lr, k-chunk lq): heads and tails of the two 32-channel groups
-  u32x4_t xf[4];
+  u32x4 xf[4];
   auto load_xf = [&]() {
-    const unsigned xrow = (oy < p.H && ox < p.W) ? (unsigned)((img0 + (long long)oy * p.W + ox) * 256) : OOB;
+    const unsigned xrow = (oy < p.H && ox < p.W) ? (unsigned)((img0 + (long long)oy * p.W + ox) * 256) : BUF_OOB;
 #pragma unroll
     for (int q = 0; q < 4; ++q) xf[q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_res, (int)(xrow + (unsigned)(q * 64 + lq * 16)), 0, 0);
   };
@@ -363,7 +346,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       bf16x8 oh, ol;
       split8(v, oh, ol);
-      rh[jp] = __builtin_bit_cast(u32x4_t, oh); rl[jp] = __builtin_bit_cast(u32x4_t, ol);
+      rh[jp] = __builtin_bit_cast(u32x4, oh); rl[jp] = __builtin_bit_cast(u32x4, ol);
     }
   };
   wait_vm<0>();                                   // the conv3 filter has landed (this wave's part; DS: and half 0 of the downsample filter)
@@ -413,7 +396,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int jp = 0; jp < 4; ++jp) {
       const int c = half * 128 + jp * 32 + lq * 8;
-      const u32x4_t qh = rh[jp], ql = rl[jp];
+      const u32x4 qh = rh[jp], ql = rl[jp];
       float v[8];
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
@@ -430,8 +413,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       bf16x8 oh, ol;
       split8(v, oh, ol);
       const unsigned col = (unsigned)((((c >> 5) << 6) + (c & 31)) * 2);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, oh), rsrc_y, (int)(prow + col), 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ol), rsrc_y, (int)(prow + col + 64u), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oh), rsrc_y, (int)(prow + col), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ol), rsrc_y, (int)(prow + col + 64u), 0, 0);
     }
     if (half == 0) { if constexpr (DS) { __builtin_amdgcn_sched_barrier(0); load_xf(); } else load_res(1); }
     BSTAMP(5 + half);

@@ -22,14 +22,6 @@ extern "C" int aod_dbg_set_tile_stamps(void* buf) { return (int)hipMemcpyToSymbo
 #define TSTAMP(k) do {} while (0)
 #endif
 
-// n / d for n < 2^22 (the float product is within 1 of the quotient; one correction step makes it exact)
-__device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d) {
-  unsigned q = (unsigned)((float)n * __builtin_amdgcn_rcpf((float)d));
-  const int r = (int)(n - q * d);
-  q = r < 0 ? q - 1 : ((unsigned)r >= d ? q + 1 : q);
-  return q;
-}
-
 // block -> (tile, member) of a grouped launch of `ngroups` members of `nwg` tiles each; a bijection of [0, nwg * ngroups).
 // mapped = 0 (no member carries a row-activity map): member-major over xcd_swizzle -- every XCD a contiguous range of tiles.
 // mapped = 1: a member's LIVE tiles cluster (the positives sit on the coarse levels, the last quarter of the tile range), and a contiguous
@@ -199,8 +191,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
   const int prow = lane >> 3;                       // row inside the wave's 8-row group
   const int kc = (lane & 7) ^ ((4 * uw + (lane >> 4)) & 7);   // k-chunk this lane fetches (same for every pass)
   const int C8 = p.C >> 3;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)g_x, 0, (int)p.x_bytes, 0x00020000);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)g_w, 0, (int)p.w_bytes, 0x00020000);
+  const auto rsrc_x = buf_rsrc(g_x, (int)p.x_bytes);
+  const auto rsrc_w = buf_rsrc(g_w, (int)p.w_bytes);
   constexpr unsigned OOB = 0xfffffff0u;
 
   unsigned rbase[A_IT];                             // byte offset of pixel (b, 0, 0) of the row's source block
@@ -290,16 +282,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
 
   // A-operand byte offsets are kept incrementally: inside one filter tap consecutive K-steps only advance the
   // channel offset by BK elements (and the validity of the tap does not change), so the full coordinate / bounds
-  // computation runs once per tap instead of once per K-step.  Invalid rows park at OOB_BASE, which stays out of
-  // range under the increments (x_bytes < OOB_BASE is checked on the host).
-  constexpr unsigned OOB_BASE = 0xf0000000u;
+  // computation runs once per tap instead of once per K-step.  Invalid rows park at BUF_OOB, which stays out of
+  // range under the increments (x_bytes < BUF_OOB is checked on the host).
   const bool fast_tap = (C8 % CPR) == 0;          // then every lane of the block changes tap at the same K-step
   unsigned aoff[A_IT];
   unsigned woff[B_IT];
 #pragma unroll
-  for (int i = 0; i < A_IT; ++i) aoff[i] = OOB_BASE;
+  for (int i = 0; i < A_IT; ++i) aoff[i] = BUF_OOB;
 #pragma unroll
-  for (int i = 0; i < B_IT; ++i) woff[i] = wbase[i] == OOB ? OOB_BASE : wbase[i];
+  for (int i = 0; i < B_IT; ++i) woff[i] = wbase[i] == OOB ? BUF_OOB : wbase[i];
   const int steps_per_tap = fast_tap ? C8 / CPR : 1;
   // taps that can reach this tile at all (class-major dgrad of a stride-2 conv: tap (r, s) only hits destination pixels with
   // y = r * dil - pad and x = s * dil - pad modulo 2); the others are skipped whole -- 5 to 8 of the 9 taps of a 3x3, 3 of 4 tiles
@@ -343,7 +334,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
           const int d = (dy * rW[i] + dx) * p.C * 2;
-          const unsigned off = ((tvm[i] >> tp_tap) & 1u) ? tbase[i] + (unsigned)(p.transposed ? -d : d) + (unsigned)tp_cc * (BK * 2) : OOB_BASE;
+          const unsigned off = ((tvm[i] >> tp_tap) & 1u) ? tbase[i] + (unsigned)(p.transposed ? -d : d) + (unsigned)tp_cc * (BK * 2) : BUF_OOB;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(sa + (RPP * i + 8 * uw) * ROWB), 16, off, 0, 0, 0);
         }
         return;
@@ -362,7 +353,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
           else { ok = ok && ((ty | tx) >= 0) && (ty % p.stride == 0) && (tx % p.stride == 0); y = ty / p.stride; x = tx / p.stride; }
         } else { y = ry0[i] + dy; x = rx0[i] + dx; }
         ok = ok && (unsigned)y < (unsigned)rH[i] && (unsigned)x < (unsigned)rW[i];
-        aoff[i] = ok ? rbase[i] + (unsigned)(((y * rW[i] + x) * p.C + c8 * 8) * 2) : OOB_BASE;
+        aoff[i] = ok ? rbase[i] + (unsigned)(((y * rW[i] + x) * p.C + c8 * 8) * 2) : BUF_OOB;
       }
       new_tap = false;
     }
@@ -379,7 +370,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
         const unsigned kofs = (unsigned)((tp_tap * p.C + tp_cc * BK) * 2);
 #pragma unroll
         for (int i = 0; i < B_IT; ++i) {
-          const unsigned off = wb0[i] == OOB ? OOB_BASE : wb0[i] + kofs;
+          const unsigned off = wb0[i] == OOB ? BUF_OOB : wb0[i] + kofs;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(sb + (RPP * i + 8 * uw) * ROWB), 16, off, 0, 0, 0);
         }
         return;
@@ -388,7 +379,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
     const bool kok = (kt_ld * BK + kc * 8) < p.K;
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
-      const unsigned off = kok ? woff[i] : OOB_BASE;
+      const unsigned off = kok ? woff[i] : BUF_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(sb + (RPP * i + 8 * uw) * ROWB), 16, off, 0, 0, 0);
     }
   };
@@ -466,9 +457,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM >= 192 ? 
       {
         // bias through a buffer descriptor that is EMPTY when there is no bias: the range check then returns zeros and the load needs
         // no branch (a branch would make the compiler wait for the loaded values where the two paths merge, i.e. right here)
-        const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)g_shift, 0, g_shift ? p.N * 4 : 0, 0x00020000);
-        const auto rsrc_s = __builtin_amdgcn_make_buffer_rsrc((void*)p.pre_scale, 0, p.pre_scale ? p.N * 4 : 0, 0x00020000);
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const auto rsrc_b = buf_rsrc(g_shift, g_shift ? p.N * 4 : 0);
+        const auto rsrc_s = buf_rsrc(p.pre_scale, p.pre_scale ? p.N * 4 : 0);
         const u32x4 b0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, n * 4, 0, 0), b1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, n * 4 + 16, 0, 0);
         const u32x4 s0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_s, n * 4, 0, 0), s1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_s, n * 4 + 16, 0, 0);
 #pragma unroll
@@ -2216,17 +2206,16 @@ extern "C" int aod_param_prep(const void* items_dev, int nitems, int total_block
 }
 extern "C" int aod_param_prep_item_bytes(void) { return (int)sizeof(PrepItem); }
 
-static inline int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 extern "C" int aod_pack_weight_fwd(const float* w, void* o, int O, int I, int R, int S, int Ipad, aod_stream_t stream) {
   AOD_CHECK_ARG(w && o && Ipad >= I && Ipad % 8 == 0, "pack_weight_fwd: bad args");
-  hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(grid_for((long long)O * R * S * Ipad)), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)o, O, I, R * S, Ipad);
+  hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(grid_for<4096>((long long)O * R * S * Ipad)), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)o, O, I, R * S, Ipad);
   AOD_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int aod_pack_weight_dgrad(const float* w, void* o, int O, int I, int R, int S, int Opad, const float* scale, aod_stream_t stream) {
   AOD_CHECK_ARG(w && o && Opad >= O && Opad % 8 == 0, "pack_weight_dgrad: Opad must be a multiple of 8 and >= O");
-  hipLaunchKernelGGL(pack_w_dgrad_kernel, dim3(grid_for((long long)Opad * R * S * I)), dim3(256), 0, (hipStream_t)stream, w, scale, (bf16_t*)o, O, I, R * S, Opad);
+  hipLaunchKernelGGL(pack_w_dgrad_kernel, dim3(grid_for<4096>((long long)Opad * R * S * I)), dim3(256), 0, (hipStream_t)stream, w, scale, (bf16_t*)o, O, I, R * S, Opad);
   AOD_LAUNCH_CHECK();
   return 0;
 }

@@ -1,7 +1,8 @@
 // What the two halves of the convolution share: conv.hip (forward / dgrad) and conv_wgrad.hip (weight gradient) both turn an aod_conv_desc_t
-// into ConvKParams with fill_params(), read the environment switches of the dispatch from ConvKnobs and place workgroups with xcd_swizzle().
+// into ConvKParams with fill_params(), read the environment switches of the dispatch from ConvKnobs and place workgroups with xcd_swizzle()
+// (tile_prims.h).
 #pragma once
-#include "common.h"
+#include "tile_prims.h"
 
 constexpr int WG_MAXG = 4;      // members of a grouped weight-gradient launch (conv_wgrad.hip) and of its grouped unpack (conv.hip)
 
@@ -47,12 +48,6 @@ struct ConvKParams {
   long long seg_src0[8], seg_dst0[8];
   int seg_mend[8];
 };
-
-__host__ __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
-  // bijective remap: blocks that share an XCD (bid % 8) get a contiguous range of tiles
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
 
 static inline int fill_params(const aod_conv_desc_t* d, ConvKParams& p) {
   AOD_CHECK_ARG(d->nseg >= 1 && d->nseg <= 8, "conv: nseg %d out of range", d->nseg);

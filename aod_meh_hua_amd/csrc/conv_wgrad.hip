@@ -130,11 +130,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
   const int nbt = (p.M + 63) >> 6;
   const bool deal = SPARSE && p.zmap && nbt <= 65535 && (nbt + p.splits - 1) / p.splits <= SLIST_CAP;
   if (deal) { ms = 0; me = p.M; }
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, (int)p.z_bytes, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)p.x_bytes);
+  const auto rsrc_z = buf_rsrc(p.dz, (int)p.z_bytes);
   const int prow = lane >> 4;                                  // pixel row inside the wave's 4-row group
   const int ch = (lane & 15) ^ ((prow << 2) | (uw & 3));       // source chunk of this lane (fixed)
-  constexpr unsigned OOB_BASE = 0xf0000000u;
 
   // per-lane constants of each sub-image: dZ column, and for X the byte offset of the lane's (tap, channel chunk) relative to a pixel's
   // top-left tap, its row offset and its mask bit
@@ -162,7 +161,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
   // Row records reach the lanes through LDS: waves 0 and 1 fetch the 64 records of a step with ONE LDS-DMA instruction each (two steps
   // ahead, into a two-slot ring behind the operand stages), every lane then picks its four with ds_read.  Fetching them into VGPRs
   // (global_load) beside the LDS-DMA operand loads made every K-step drain the whole vector-memory queue: 27 % of the kernel.
-  const auto rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void*)p.tab, 0, (int)p.tab_bytes, 0x00020000);
+  const auto rsrc_t = buf_rsrc(p.tab, (int)p.tab_bytes);
   char* const stab = smem + 2 * STAGE;                        // [2][64] records
   auto tdma = [&](int mbase, int slot) {
     if (uw < 2) {
@@ -186,12 +185,12 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
       const RowRec r = rec[i];
 #pragma unroll
       for (int h = 0; h < TN; ++h) {
-        const unsigned zoff = (mok && zok[h]) ? r.zoff + zcol[h] : OOB_BASE;
+        const unsigned zoff = (mok && zok[h]) ? r.zoff + zcol[h] : BUF_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_z, (__attribute__((address_space(3))) void*)(sz + h * IMG + (RPW * i + 4 * uw) * 256), 16, zoff, 0, 0, 0);
       }
 #pragma unroll
       for (int h = 0; h < TK; ++h) {
-        const unsigned xoff = (mok && (r.mask & tbit[h])) ? r.xrow + (unsigned)dy[h] * r.wc2 + cdx[h] : OOB_BASE;
+        const unsigned xoff = (mok && (r.mask & tbit[h])) ? r.xrow + (unsigned)dy[h] * r.wc2 + cdx[h] : BUF_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(sx + h * IMG + (RPW * i + 4 * uw) * 256), 16, xoff, 0, 0, 0);
       }
     }
@@ -245,9 +244,8 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
   // every step -- i.e. for the LDS-DMA of the NEXT stage issued just above -- which serialises load and compute inside each wave (the
   // plain ds_read_b128 of the forward kernel does not get that wait).  The asm reads are invisible to the compiler's counters; frag_wait()
   // is their s_waitcnt and makes every destination opaque, so no MFMA is scheduled above it.
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  u32x2_t alo[NI], ahi[NI], blo[NJ], bhi[NJ];
-  auto tr_read = [&](u32x2_t& dst, const char* ptr) {
+  u32x2 alo[NI], ahi[NI], blo[NJ], bhi[NJ];
+  auto tr_read = [&](u32x2& dst, const char* ptr) {
     const unsigned a = (unsigned)(unsigned long long)ptr;       // (the low half of a shared-aperture address is the LDS byte address)
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(a) : "memory");
   };
@@ -277,11 +275,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradParams& p, int bid_in) {
     for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(alo[i]), "+v"(ahi[i]));
 #pragma unroll
     for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(blo[j]), "+v"(bhi[j]));
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
-    for (int i = 0; i < NI; ++i) af[i] = __builtin_bit_cast(bf16x8, (u32x4_t){alo[i][0], alo[i][1], ahi[i][0], ahi[i][1]});
+    for (int i = 0; i < NI; ++i) af[i] = __builtin_bit_cast(bf16x8, (u32x4){alo[i][0], alo[i][1], ahi[i][0], ahi[i][1]});
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4_t){blo[j][0], blo[j][1], bhi[j][0], bhi[j][1]});
+    for (int j = 0; j < NJ; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4){blo[j][0], blo[j][1], bhi[j][0], bhi[j][1]});
   };
   auto mfma_block = [&]() {
 #pragma unroll
@@ -401,12 +398,11 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
   const int nbt = (p.M + 63) >> 6;                             // 64-row blocks of the whole pixel axis
   const bool deal = SPARSE && p.zmap && nbt <= 65535 && (nbt + p.splits - 1) / p.splits <= SLIST_CAP;
   if (deal) { ms = 0; me = p.M; }                              // the workgroup's rows come from all over the axis
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const auto rsrc_z = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, (int)p.z_bytes, 0x00020000);
-  const auto rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void*)p.tab, 0, (int)p.tab_bytes, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)p.x_bytes);
+  const auto rsrc_z = buf_rsrc(p.dz, (int)p.z_bytes);
+  const auto rsrc_t = buf_rsrc(p.tab, (int)p.tab_bytes);
   const int prow = lane >> 4;                                  // pixel row inside the wave's 4-row group
   const int ch = (lane & 15) ^ ((prow << 2) | (uw & 3));       // source chunk of this lane (fixed; tr_off's key of row RPW * i + 4 * uw + prow)
-  constexpr unsigned OOB_BASE = 0xf0000000u;
   unsigned zcol[TN];
   bool zok[TN];
 #pragma unroll
@@ -451,12 +447,12 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
       const RowRec r = rec[i];
 #pragma unroll
       for (int h = 0; h < TN; ++h) {
-        const unsigned zoff = (mok && zok[h]) ? r.zoff + zcol[h] : OOB_BASE;
+        const unsigned zoff = (mok && zok[h]) ? r.zoff + zcol[h] : BUF_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_z, (__attribute__((address_space(3))) void*)(sz + h * IMG + (RPW * i + 4 * uw) * 256), 16, zoff, 0, 0, 0);
       }
 #pragma unroll
       for (int h = 0; h < TK; ++h) {
-        const unsigned xoff = (mok && (r.mask & tbit[h])) ? r.xrow + (unsigned)dy[h] * r.wc2 + cdx[h] : OOB_BASE;
+        const unsigned xoff = (mok && (r.mask & tbit[h])) ? r.xrow + (unsigned)dy[h] * r.wc2 + cdx[h] : BUF_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(sx + h * IMG + (RPW * i + 4 * uw) * 256), 16, xoff, 0, 0, 0);
       }
     }
@@ -505,20 +501,18 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
     __syncthreads();
   }
   const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  auto tr_read = [&](u32x2_t& dst, const char* ptr) {
+  auto tr_read = [&](u32x2& dst, const char* ptr) {
     const unsigned a = (unsigned)(unsigned long long)ptr;
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(a) : "memory");
   };
   // fragment of the 16 physical columns [col, col + 16) of an operand stage: pixel rows 8g + q (+4), 4 columns per lane
-  auto frag = [&](u32x2_t& lo, u32x2_t& hi, const char* base, int col) {
+  auto frag = [&](u32x2& lo, u32x2& hi, const char* base, int col) {
     const char* im = base + (col >> 7) * IMG;
     const int c = (col & 127) + pp * 4;
     tr_read(lo, im + tr_off(8 * g + q, c >> 3) + (c & 7) * 2);
     tr_read(hi, im + tr_off(8 * g + q + 4, c >> 3) + (c & 7) * 2);
   };
-  u32x2_t alo[NI], ahi[NI], bhlo[NJ], bhhi[NJ], bllo[NJ], blhi[NJ];
+  u32x2 alo[NI], ahi[NI], bhlo[NJ], bhhi[NJ], bllo[NJ], blhi[NJ];
   bf16x8 af[NI], bh[NJ], bl[NJ];
   for (int stp = 0; stp < nsteps; ++stp) {
     const int cur = stp & 1;
@@ -540,15 +534,15 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < NI; ++i) { asm volatile("" : "+v"(alo[i]), "+v"(ahi[i])); af[i] = __builtin_bit_cast(bf16x8, (u32x4_t){alo[i][0], alo[i][1], ahi[i][0], ahi[i][1]}); }
+    for (int i = 0; i < NI; ++i) { asm volatile("" : "+v"(alo[i]), "+v"(ahi[i])); af[i] = __builtin_bit_cast(bf16x8, (u32x4){alo[i][0], alo[i][1], ahi[i][0], ahi[i][1]}); }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       asm volatile("" : "+v"(bhlo[j]), "+v"(bhhi[j]), "+v"(bllo[j]), "+v"(blhi[j]));
-      bh[j] = __builtin_bit_cast(bf16x8, (u32x4_t){bhlo[j][0], bhlo[j][1], bhhi[j][0], bhhi[j][1]});
-      bl[j] = __builtin_bit_cast(bf16x8, (u32x4_t){bllo[j][0], bllo[j][1], blhi[j][0], blhi[j][1]});
+      bh[j] = __builtin_bit_cast(bf16x8, (u32x4){bhlo[j][0], bhlo[j][1], bhhi[j][0], bhhi[j][1]});
+      bl[j] = __builtin_bit_cast(bf16x8, (u32x4){bllo[j][0], bllo[j][1], blhi[j][0], blhi[j][1]});
     }
     // tails of dZ requested now, consumed after the two head products
-    u32x2_t tlo[NI], thi[NI];
+    u32x2 tlo[NI], thi[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) { const int nl = wm * WML + i * 16; frag(tlo[i], thi[i], sz, ((nl >> 5) << 6) + (nl & 31) + 32); }
 #pragma unroll
@@ -560,7 +554,7 @@ __device__ __forceinline__ void wgrad_tile_x3w(const WgradParams& p, int bid_in)
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < NI; ++i) { asm volatile("" : "+v"(tlo[i]), "+v"(thi[i])); af[i] = __builtin_bit_cast(bf16x8, (u32x4_t){tlo[i][0], tlo[i][1], thi[i][0], thi[i][1]}); }
+    for (int i = 0; i < NI; ++i) { asm volatile("" : "+v"(tlo[i]), "+v"(thi[i])); af[i] = __builtin_bit_cast(bf16x8, (u32x4){tlo[i][0], tlo[i][1], thi[i][0], thi[i][1]}); }
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll

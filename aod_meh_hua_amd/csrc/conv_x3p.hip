@@ -27,23 +27,11 @@
 // otherwise; xh*wh, xl*wh, xh*wl per step) and the same fp32 epilogue arithmetic: IDENTICAL BITS (tests/test_gpu_x3p.py); only the fp32
 // atomics of the optional column sums arrive in another order.
 #include "conv_x3p.h"
+#include "tile_prims.h"
 
 namespace {
 
 constexpr int XP_XBYTES = 16384;
-constexpr unsigned XP_OOB = 0xf0000000u;
-
-__device__ __forceinline__ unsigned xp_udiv(unsigned n, unsigned d) {      // n / d for n < 2^22 (conv.hip udiv_small)
-  unsigned q = (unsigned)((float)n * __builtin_amdgcn_rcpf((float)d));
-  const int r = (int)(n - q * d);
-  q = r < 0 ? q - 1 : ((unsigned)r >= d ? q + 1 : q);
-  return q;
-}
-
-__device__ __forceinline__ int xp_swizzle(int bid, int nwg) {      // bijective: blocks that share an XCD (bid % 8) take a contiguous tile range
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
 
 template <class T>
 __device__ __forceinline__ T xp_sel8(const T* a, int sg) {      // a[sg] of a by-value argument array with constant indices only (sg is wave-uniform)
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     const int base = j * G, left = ntiles - base;
-    return base + xp_swizzle(bid, left < G ? left : G);
+    return base + xcd_swizzle(bid, left < G ? left : G);
   };
   // K-steps of a tile: taps x chunks; in the class-major form the class (tile / tiles per class) decides the taps: 1, 2, 2, 4
   auto taps_of = [&](int tile) {
@@ -161,8 +149,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int tm = tl / p.tiles_n, tn = tl - tm * p.tiles_n;
       const int m0 = tm * XP_BM, n0 = tn * BN;
       // (p.rot bits 8 / 9, timing experiments only: a zero-record descriptor drops every load of that operand at the range check)
-      const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)XP_GSEL(x), 0, (p.rot & 256) ? 0 : (int)p.x_bytes, 0x00020000);
-      const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)XP_GSEL(w), 0, (p.rot & 512) ? 0 : (int)p.w_bytes, 0x00020000);
+      const auto rsrc_x = buf_rsrc(XP_GSEL(x), (p.rot & 256) ? 0 : (int)p.x_bytes);
+      const auto rsrc_w = buf_rsrc(XP_GSEL(w), (p.rot & 512) ? 0 : (int)p.w_bytes);
       // the tile lies inside ONE segment (launcher): workgroup-uniform geometry
       const int sg = LAT == 1 ? 0 : seg_of(m0);
       const unsigned mstart = sg ? (unsigned)xp_sel8(p.seg_mend, sg - 1) : 0u;
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int m = m0 + 8 * w + 32 * i + prow;
         const bool live = m < mlim;
         const unsigned ml = (unsigned)m - mstart;
-        const unsigned b = xp_udiv(ml, rhw), rem = ml - b * rhw, oy = xp_udiv(rem, RW), ox = rem - oy * RW;
+        const unsigned b = udiv_small(ml, rhw), rem = ml - b * rhw, oy = udiv_small(rem, RW), ox = rem - oy * RW;
         const unsigned base = src0b + b * imgb + (unsigned)(kc * 16);
         if constexpr (LAT == 1) {
           // destination pixel (2 oy + py, 2 ox + px) of a 3x3 / stride-2 / pad-1 conv's input gradient: tap (r, s) reaches it from dZ pixel
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int ri = px ? tq >> 1 : tq, si = px ? tq & 1 : 0;            // tap tq of the class = (ri-th row tap, si-th column tap)
             const int sy = (int)oy + ((py && ri == 0) ? 1 : 0), sx = (int)ox + ((px && si == 0) ? 1 : 0);
             const bool ok = live && tq < ntap && (unsigned)sy < H && (unsigned)sx < W;
-            vo[tq][i] = ok ? base + (unsigned)(sy * (int)W + sx) * rowb : XP_OOB;
+            vo[tq][i] = ok ? base + (unsigned)(sy * (int)W + sx) * rowb : BUF_OOB;
           }
         } else {
           const int y0 = p.transposed ? (int)oy + p.pad : (int)oy * p.stride - p.pad;
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int s_ = 0; s_ < RR; ++s_) {
               const int x = x0 + sgn * s_ * p.dil;
               const bool ok = yok && (unsigned)x < W;
-              vo[r * RR + s_][i] = ok ? base + (unsigned)(y * (int)W + x) * rowb : XP_OOB;
+              vo[r * RR + s_][i] = ok ? base + (unsigned)(y * (int)W + x) * rowb : BUF_OOB;
             }
           }
         }
@@ -271,8 +259,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int oh = (lq ^ sw) << 4, ol = ((4 + lq) ^ sw) << 4;          // 16-B slot of this lane's head / tail k-chunk inside a 128-B tile row
   const int xoff = (wm * 64 + lr) * 128, woff = XP_XBYTES + (wn * 16 * NBW + lr) * 128;
   const int NP = ((p.N + 31) >> 5) << 6;                             // destination row pitch (X-layout, elements)
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-  const auto rsrc_s = __builtin_amdgcn_make_buffer_rsrc((void*)p.pre_scale, 0, p.pre_scale ? p.N * 4 : 0, 0x00020000);     // empty descriptor -> zeros
+  const auto rsrc_s = buf_rsrc(p.pre_scale, p.pre_scale ? p.N * 4 : 0);     // empty descriptor -> zeros
 
   XSTAMP(0);
   __builtin_amdgcn_s_barrier();                                      // stage 0 is resident
@@ -323,7 +310,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if constexpr (LAT == 0) prow_[mb] = (drow0 + mc) * NP;
         else {
           // lattice destinations: row (image, y, x) of the tile's row space lands at (2y + py, 2x + px) of the full-resolution map
-          const unsigned b = xp_udiv((unsigned)mc, erhw), rem = (unsigned)mc - b * erhw, oy = xp_udiv(rem, eRW), ox = rem - oy * eRW;
+          const unsigned b = udiv_small((unsigned)mc, erhw), rem = (unsigned)mc - b * erhw, oy = udiv_small(rem, eRW), ox = rem - oy * eRW;
           const long long drow = LAT == 1 ? ((long long)b * eOH + 2 * oy + (unsigned)(cls >> 1)) * eOW + 2 * ox + (unsigned)(cls & 1)
                                           : (long long)b * p.up_hw + (long long)(2 * oy) * p.up_w + 2 * ox;
           prow_[mb] = (xp_sel8(p.seg_dst0, 0) + drow) * NP;
@@ -387,7 +374,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bf16_t* const gmask = XP_GSEL(mask);
     float* const gcs = XP_GSEL(colsum);
     const float* const gshift = XP_GSEL(shift);
-    const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)gshift, 0, gshift ? p.N * 4 : 0, 0x00020000);
+    const auto rsrc_b = buf_rsrc(gshift, gshift ? p.N * 4 : 0);
     if constexpr (PRE == 0) row_addresses();
     // PG block pairs (32 channels each) at a time: all their operands are requested before the first is used.  Two pairs with 64 accumulator
     // registers; one with 128 (the 256-column tile), where a second pair's 48 operand registers would spill
@@ -400,11 +387,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int aa = 0; aa < PG; ++aa) {
         const int cb = n0 + wn * 16 * NBW + 32 * (pg * PG + aa) + 8 * lq;
         const int col = 2 * (cb - 8 * lq) + 8 * lq;
-        const u32x4_t b0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, cb * 4, 0, 0), b1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, cb * 4 + 16, 0, 0);
+        const u32x4 b0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, cb * 4, 0, 0), b1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, cb * 4 + 16, 0, 0);
         // (the scale vector only where there is one: a load whose result is never used is never waited for either, and the registers it
         // targets stay 'pending' into the next tile's K loop -- whose first fragment reads then wait for EVERY older memory operation of the
         // wave, i.e. for the previous tile's stores to drain)
-        u32x4_t s0 = {0u, 0u, 0u, 0u}, s1 = {0u, 0u, 0u, 0u};
+        u32x4 s0 = {0u, 0u, 0u, 0u}, s1 = {0u, 0u, 0u, 0u};
         if (p.pre_scale) { s0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_s, cb * 4, 0, 0); s1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc_s, cb * 4 + 16, 0, 0); }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

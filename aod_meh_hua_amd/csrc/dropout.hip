@@ -8,18 +8,10 @@
 // word c & 3 of the block, u = u01(word) in (0, 1], factor = u > rate ? 1 / (1 - rate) : 0  (fp32; rate = 0: u > 0 always, factor 1).
 // The tag keeps the stream apart from the HUA sampler's, whose key is (seed_lo, seed_hi) itself.  A factor is a function of (seed, sample,
 // image id, site, channel) only: not of the batch, the image's position in it, the rank or eager / replayed execution.
-#include "common.h"
+#include "tile_prims.h"
 
 #define DROP_KEY_TAG 0x44524F50u        // 'DROP'
 #define DROP_MAX_SEG 8
-
-static inline int grid_for(long long nvec) {
-  long long b = (nvec + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
-// X-layout (x3_ops.hip): physical column of logical octet q -- 8 logical channels = a 16-B head piece and the 16-B tail piece 64 B behind it
-__device__ __forceinline__ int xoct(int q) { return ((q >> 2) << 6) + ((q & 3) << 3); }
 
 // ---------------------------------------------------------------- the factor table of one forward
 // grid (1, n_sites, B), one wave per (site, image): lane t produces the quads t, t + 64, ... of the site -- one Philox call = four channels
@@ -150,10 +142,10 @@ extern "C" int aod_dropout2d_apply_multi(void* x, const float* table, int64_t ro
   const int CP = x3 ? 2 * Cp : C;                 // physical row width (bf16 columns)
   const long long items = sg.cum[nseg] * P;
   if (x3)
-    hipLaunchKernelGGL(dropout2d_apply_kernel<true>, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, table,
+    hipLaunchKernelGGL(dropout2d_apply_kernel<true>, dim3(grid_for<2048>(items)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, table,
                        (long long)row_stride_T, sg, C, P, CP);
   else
-    hipLaunchKernelGGL(dropout2d_apply_kernel<false>, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, table,
+    hipLaunchKernelGGL(dropout2d_apply_kernel<false>, dim3(grid_for<2048>(items)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, table,
                        (long long)row_stride_T, sg, C, P, CP);
   AOD_LAUNCH_CHECK();
   return 0;

@@ -1,10 +1,5 @@
 // HBM-bound elementwise / reduction kernels around the conv stack (NHWC bf16, 16-B lanes).
-#include "common.h"
-
-static inline int grid_for(long long nvec) {
-  long long b = (nvec + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
+#include "tile_prims.h"
 
 // ---------------------------------------------------------------- NCHW fp32 -> NHWC bf16 (padded C)
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int B, int C, int HW, int Cpad) {
@@ -24,7 +19,7 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, bf16_t* __res
 }
 extern "C" int aod_nchw_f32_to_nhwc_bf16(const float* src, void* dst, int B, int C, int H, int W, int Cpad, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && Cpad >= C, "nchw_to_nhwc: bad args");
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H * W, Cpad);
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for<2048>((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H * W, Cpad);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -59,7 +54,7 @@ __global__ void nchw_to_s2d_kernel(const float* __restrict__ src, bf16_t* __rest
 }
 extern "C" int aod_nchw_f32_to_s2d_bf16(const float* src, void* dst, int B, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C >= 1 && C <= 4 && H % 2 == 0 && W % 2 == 0, "nchw_to_s2d: C <= 4 and even H, W required (C %d, %d x %d)", C, H, W);
-  hipLaunchKernelGGL(nchw_to_s2d_kernel, dim3(grid_for((long long)B * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H, W);
+  hipLaunchKernelGGL(nchw_to_s2d_kernel, dim3(grid_for<2048>((long long)B * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -94,7 +89,7 @@ __global__ void maxpool_kernel(const bf16_t* __restrict__ src, bf16_t* __restric
 extern "C" int aod_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C % 8 == 0, "maxpool: C must be a multiple of 8");
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for<2048>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, (bf16_t*)dst, B, H, W, C / 8, OH, OW);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -119,7 +114,7 @@ __global__ void upsample_add_kernel(const bf16_t* __restrict__ src, const bf16_t
 }
 extern "C" int aod_upsample2x_add(const void* src, void* dst, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C % 8 == 0, "upsample_add: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, (const bf16_t*)dst, (bf16_t*)dst, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -128,7 +123,7 @@ extern "C" int aod_upsample2x_add(const void* src, void* dst, int B, int h, int 
 // lateral conv's output): one pass less over the level
 extern "C" int aod_upsample2x_add_to(const void* top, const void* lateral, void* out, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(top && lateral && out && C % 8 == 0, "upsample_add_to: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)top, (const bf16_t*)lateral, (bf16_t*)out, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -162,7 +157,7 @@ __global__ void upsample_add_bwd_kernel(const bf16_t* __restrict__ gd, bf16_t* _
 }
 extern "C" int aod_upsample2x_add_bwd(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(g_dst && g_src && C % 8 == 0, "upsample_add_bwd: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_bwd_kernel<true>, dim3(grid_for((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_bwd_kernel<true>, dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)g_dst, (bf16_t*)g_src, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -170,7 +165,7 @@ extern "C" int aod_upsample2x_add_bwd(const void* g_dst, void* g_src, int B, int
 // ... writing g_src instead of accumulating into it (no zero fill of the destination needed)
 extern "C" int aod_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(g_dst && g_src && C % 8 == 0, "upsample_add_bwd_set: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_bwd_kernel<false>, dim3(grid_for((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_bwd_kernel<false>, dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)g_dst, (bf16_t*)g_src, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -188,7 +183,7 @@ __global__ void add_relu_kernel(const bf16_t* __restrict__ a, const bf16_t* __re
 }
 extern "C" int aod_add_relu(const void* a, const void* b, void* out, int64_t n, aod_stream_t stream) {
   AOD_CHECK_ARG(a && b && out && n % 8 == 0, "add_relu: n must be a multiple of 8");
-  hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)(n / 8));
+  hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for<2048>(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)(n / 8));
   AOD_LAUNCH_CHECK();
   return 0;
 }

@@ -10,11 +10,11 @@
 //   * K-steps run chunk-major, (64-channel chunk, tap): the pixel operand of a step is read straight from the halo chunk at the tap's offset
 //     (row (i + r) * 18 + x + s), only the [N][64] filter slice of the step is streamed (three-slot ring, LDS-DMA, counted s_waitcnt vmcnt(N) +
 //     one raw s_barrier per step -- a __syncthreads() would drain the ring);
-//   * products are computed transposed (filter fragment = MFMA A operand): a lane ends up with 4 (8 with the paired-block row permutation of
-//     bottleneck.hip) consecutive output channels of ONE pixel, so fp32 / bf16 results leave in 16-B pieces straight from the accumulators:
+//   * products are computed transposed (filter fragment = MFMA A operand): a lane ends up with 4 (8 with the paired-block row permutation,
+//     wrow in tile_prims.h) consecutive output channels of ONE pixel, so fp32 / bf16 results leave in 16-B pieces straight from the accumulators:
 //     no fp32 LDS image, no epilogue barrier;  bias, ReLU, the producer's ReLU mask and the bias-gradient column sums are fused like in conv.hip.
 // dgrad = the same kernel on the dgrad-packed filter with the taps mirrored (flip).
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -34,24 +34,6 @@ struct HaloArgs {
 constexpr int TH = 8, TW = 16, PW_ = TW + 2, PPIX = (TH + 2) * PW_;      // 180 halo pixels
 constexpr int PROWS = 184;                                                // 23 groups of 8 rows (waves 0-6 move 3 LDS-DMA pieces per chunk, wave 7 two)
 constexpr int PSLOT = PROWS * 128;                                        // one 64-channel chunk of the halo
-constexpr unsigned OOB = 0xf0000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-
-#define AOD_VMCASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-__device__ __forceinline__ void wait_vm_dyn(int n) {      // n is wave-uniform
-  switch (n) {
-    AOD_VMCASE(0) AOD_VMCASE(1) AOD_VMCASE(2) AOD_VMCASE(3) AOD_VMCASE(4) AOD_VMCASE(5) AOD_VMCASE(6) AOD_VMCASE(7) AOD_VMCASE(8)
-    AOD_VMCASE(9) AOD_VMCASE(10) AOD_VMCASE(11) AOD_VMCASE(12) AOD_VMCASE(13) AOD_VMCASE(14) AOD_VMCASE(15) AOD_VMCASE(16)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-#undef AOD_VMCASE
 
 // NB: 16-channel output blocks per PASS (the kernel makes ceil(N / 16 NB) passes over the K loop; the halo is re-streamed per pass, from L2);
 // WPX x (8 / WPX) waves over (pixel rows, channel blocks); R: slots of the filter ring (R - 1 filter slices in flight: a K-step of a narrow
@@ -73,7 +55,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int wp = uw / WCH, wc = uw % WCH;
-  const int wg = xcd_remap(blockIdx.x, p.ntiles);
+  const int wg = xcd_swizzle(blockIdx.x, p.ntiles);
   // (constant indices only: a run-time index into the by-value argument struct would move it to scratch memory)
   int sH = 1, sW = 1, stx = 1, stpi = 1, st0 = 0;
   long long ssrc = 0, sdst = 0;
@@ -86,10 +68,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
   const int local = wg - st0;
   const int b = local / stpi, rem = local - b * stpi;
   const int ty0 = (rem / stx) * TH, tx0 = (rem % stx) * TW;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)p.w_bytes, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)p.x_bytes);
+  const auto rsrc_w = buf_rsrc(p.w, (int)p.w_bytes);
   // the ReLU mask through a descriptor that is EMPTY when there is no mask (zeros come back, no branch around the loads)
-  const auto rsrc_m = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask, 0, p.mask ? (int)(p.y_rows * p.N * 2) : 0, 0x00020000);
+  const auto rsrc_m = buf_rsrc(p.mask, p.mask ? (int)(p.y_rows * p.N * 2) : 0);
 
   // bias vector -> LDS (an ordinary global load beside LDS-DMA makes hipcc drain the DMA queue where the value is used: do it first)
   float* const vec = reinterpret_cast<float*>(smem + OFF_VEC);
@@ -114,7 +96,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
     const int hy = row / PW_, hx = row - hy * PW_;
     const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
     const bool ok = row < PPIX && (unsigned)y < (unsigned)sH && (unsigned)x < (unsigned)sW;
-    poff[i] = ok ? (unsigned)((ssrc + ((long long)b * sH + y) * sW + x) * (long long)p.C * 2) : OOB;
+    poff[i] = ok ? (unsigned)((ssrc + ((long long)b * sH + y) * sW + x) * (long long)p.C * 2) : BUF_OOB;
   }
   auto issue_patch = [&](int kc, int slot) {
     const int ch = kc * 8 + kcl;
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
 #pragma unroll
     for (int i = 0; i < NPI; ++i) {
       if (uw + 8 * i < PPIECES) {
-        const unsigned off = (cok && poff[i] != OOB) ? poff[i] + (unsigned)(ch * 16) : OOB;
+        const unsigned off = (cok && poff[i] != BUF_OOB) ? poff[i] + (unsigned)(ch * 16) : BUF_OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(smem + slot * PSLOT + (uw + 8 * i) * 1024), 16, off, 0, 0, 0);
       }
     }
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
 #pragma unroll
     for (int i = 0; i < NWI; ++i) {
       const int n = nb0 * 16 + 8 * (uw + 8 * i) + drow;
-      wbase[i] = n < p.N ? (unsigned)((long long)n * 9 * p.C * 2) : OOB;
+      wbase[i] = n < p.N ? (unsigned)((long long)n * 9 * p.C * 2) : BUF_OOB;
     }
     auto issue_w = [&](int s, int slot) {
       const int kc = s / 9, tap = s - kc * 9;
@@ -158,24 +140,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB >= 8 ? 2
 #pragma unroll
       for (int i = 0; i < NWI; ++i) {
         if (uw + 8 * i < WPIECES) {
-          const unsigned off = (cok && wbase[i] != OOB) ? wbase[i] + koff : OOB;
+          const unsigned off = (cok && wbase[i] != BUF_OOB) ? wbase[i] + koff : BUF_OOB;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(smem + OFF_W + slot * WSLOT + (uw + 8 * i) * 1024), 16, off, 0, 0, 0);
         }
       }
     };
     // the producer's ReLU mask rows of this pass: requested ahead of the K loop, consumed after it
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    u32x4_t mreg[NPW][NU];
+    u32x4 mreg[NPW][NU];
 #pragma unroll
     for (int i = 0; i < NPW; ++i)
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
         const int jg0 = nb0 + wc * NBW + (PAIR ? 2 * u : u);
         const int ch0 = PAIR ? ((jg0 >> 1) * 32 + lq * 8) : jg0 * 16 + lq * 4;
-        const unsigned off = (pok[i] && mvec && ch0 + CW <= p.N) ? (unsigned)((orow[i] * p.N + ch0) * 2) : OOB;
+        const unsigned off = (pok[i] && mvec && ch0 + CW <= p.N) ? (unsigned)((orow[i] * p.N + ch0) * 2) : BUF_OOB;
         if (PAIR) mreg[i][u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_m, (int)off, 0, 0);
-        else { const u32x2_t m2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc_m, (int)off, 0, 0); mreg[i][u] = (u32x4_t){m2[0], m2[1], 0u, 0u}; }
+        else { const u32x2 m2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc_m, (int)off, 0, 0); mreg[i][u] = (u32x4){m2[0], m2[1], 0u, 0u}; }
       }
 
     f32x4 acc[NPW][NBW];

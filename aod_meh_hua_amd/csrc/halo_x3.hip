@@ -9,7 +9,7 @@
 // these layers in (C >= 256 columns: taps innermost) -- identical bits.  Wave w = output pixel row w of the tile; products are computed transposed
 // (filter fragment = the MFMA's A operand), so a lane ends up with 4 consecutive output channels of one pixel: 16-B fp32 stores straight from
 // the accumulators, bias and ReLU fused.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -27,24 +27,6 @@ struct Hx3Args {
 constexpr int TH = 8, TW = 16, PW_ = TW + 2, PPIX = (TH + 2) * PW_;      // 180 halo pixels
 constexpr int PROWS = 184, PPIECES = PROWS / 8;                            // 23 LDS-DMA pieces of 8 rows (waves 0-6 move three, wave 7 two)
 constexpr int PSLOT = PROWS * 128;                                        // one 32-channel chunk of the halo: 23 552 B
-constexpr unsigned OOB = 0xf0000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-#define AOD_VMCASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-__device__ __forceinline__ void wait_vm_dyn(int n) {      // n is wave-uniform
-  switch (n) {
-    AOD_VMCASE(0) AOD_VMCASE(1) AOD_VMCASE(2) AOD_VMCASE(3) AOD_VMCASE(4) AOD_VMCASE(5) AOD_VMCASE(6) AOD_VMCASE(7) AOD_VMCASE(8)
-    AOD_VMCASE(9) AOD_VMCASE(10) AOD_VMCASE(11) AOD_VMCASE(12) AOD_VMCASE(13) AOD_VMCASE(14) AOD_VMCASE(15) AOD_VMCASE(16)
-    AOD_VMCASE(17) AOD_VMCASE(18) AOD_VMCASE(19) AOD_VMCASE(20) AOD_VMCASE(21) AOD_VMCASE(22) AOD_VMCASE(23) AOD_VMCASE(24)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-#undef AOD_VMCASE
 
 // NB: 16-channel output blocks (N <= 16 NB); S: stages (chunks resident / in flight).  One output pixel row per wave: every wave reads all of
 // a chunk's filter fragments for its row -- 72 ds_read_b128 per 81 MFMAs at NB = 3.  What bounds the kernel is the arrival of its chunks (77 KB
@@ -62,7 +44,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   const int t = threadIdx.x, lane = t & 63;
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
-  const int wg = xcd_remap(blockIdx.x, p.ntiles);
+  const int wg = xcd_swizzle(blockIdx.x, p.ntiles);
   // (constant indices only: a run-time index into the by-value argument struct would move it to scratch memory)
   int sH = 1, sW = 1, stx = 1, stpi = 1, st0 = 0;
   long long ssrc = 0, sdst = 0;
@@ -75,8 +57,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   const int local = wg - st0;
   const int b = local / stpi, rem = local - b * stpi;
   const int ty0 = (rem / stx) * TH, tx0 = (rem % stx) * TW;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)p.w_bytes, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)p.x_bytes);
+  const auto rsrc_w = buf_rsrc(p.w, (int)p.w_bytes);
 
   // bias vector -> LDS (an ordinary global load beside LDS-DMA makes hipcc drain the DMA queue where the value is used: do it first)
   float* const vec = reinterpret_cast<float*>(smem + OFF_VEC);
@@ -99,13 +81,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const int hy = row / PW_, hx = row - hy * PW_;
     const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
     const bool ok = row < PPIX && (unsigned)y < (unsigned)sH && (unsigned)x < (unsigned)sW;
-    poff[i] = ok ? (unsigned)((ssrc + ((long long)b * sH + y) * sW + x) * (long long)p.C * 2 + kcl * 16) : OOB;
+    poff[i] = ok ? (unsigned)((ssrc + ((long long)b * sH + y) * sW + x) * (long long)p.C * 2 + kcl * 16) : BUF_OOB;
   }
 #pragma unroll
   for (int i = 0; i < NWI; ++i) {
     const int pi = uw + NWV * i;                                          // piece of the chunk's filter image [9][WROWS][128 B]
     const int tap = pi / (WROWS / 8), n = (pi - tap * (WROWS / 8)) * 8 + drow;
-    woff[i] = (pi < WPIECES && n < p.N) ? (unsigned)((((long long)n * 9 + tap) * p.C) * 2 + kcl * 16) : OOB;
+    woff[i] = (pi < WPIECES && n < p.N) ? (unsigned)((((long long)n * 9 + tap) * p.C) * 2 + kcl * 16) : BUF_OOB;
   }
   auto issue = [&](int kc, int slot) {                                    // chunk kc -> stage `slot`: its halo and its nine filter slices
     char* st = smem + slot * STAGE;

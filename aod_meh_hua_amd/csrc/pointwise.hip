@@ -18,78 +18,34 @@
 // memory operations may still be outstanding; stores and loads are issued unconditionally (rows past M use an out-of-range buffer
 // offset), so the counts are exact.
 #include "pointwise.h"
+#include "tile_prims.h"
 
 #include <stdlib.h>
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// wait until at most n vector memory operations of this wave are outstanding (n is wave-uniform)
-__device__ __forceinline__ void wait_vm_dyn(int n) {
+// tile_prims.h's wait_vm_dyn over the counts 0..48 of this kernel's ring (n is wave-uniform).  A switch of its own: the case set decides the
+// code the compiler makes of it, and the 0..24 table would turn every deeper wait into vmcnt(0)
+__device__ __forceinline__ void wait_vm_dyn48(int n) {
   switch (n) {
-    case 0: wait_vm<0>(); break;
-    case 1: wait_vm<1>(); break;
-    case 2: wait_vm<2>(); break;
-    case 3: wait_vm<3>(); break;
-    case 4: wait_vm<4>(); break;
-    case 5: wait_vm<5>(); break;
-    case 6: wait_vm<6>(); break;
-    case 7: wait_vm<7>(); break;
-    case 8: wait_vm<8>(); break;
-    case 9: wait_vm<9>(); break;
-    case 10: wait_vm<10>(); break;
-    case 11: wait_vm<11>(); break;
-    case 12: wait_vm<12>(); break;
-    case 13: wait_vm<13>(); break;
-    case 14: wait_vm<14>(); break;
-    case 15: wait_vm<15>(); break;
-    case 16: wait_vm<16>(); break;
-    case 17: wait_vm<17>(); break;
-    case 18: wait_vm<18>(); break;
-    case 19: wait_vm<19>(); break;
-    case 20: wait_vm<20>(); break;
-    case 21: wait_vm<21>(); break;
-    case 22: wait_vm<22>(); break;
-    case 23: wait_vm<23>(); break;
-    case 24: wait_vm<24>(); break;
-    case 25: wait_vm<25>(); break;
-    case 26: wait_vm<26>(); break;
-    case 27: wait_vm<27>(); break;
-    case 28: wait_vm<28>(); break;
-    case 29: wait_vm<29>(); break;
-    case 30: wait_vm<30>(); break;
-    case 31: wait_vm<31>(); break;
-    case 32: wait_vm<32>(); break;
-    case 33: wait_vm<33>(); break;
-    case 34: wait_vm<34>(); break;
-    case 35: wait_vm<35>(); break;
-    case 36: wait_vm<36>(); break;
-    case 37: wait_vm<37>(); break;
-    case 38: wait_vm<38>(); break;
-    case 39: wait_vm<39>(); break;
-    case 40: wait_vm<40>(); break;
-    case 41: wait_vm<41>(); break;
-    case 42: wait_vm<42>(); break;
-    case 43: wait_vm<43>(); break;
-    case 44: wait_vm<44>(); break;
-    case 45: wait_vm<45>(); break;
-    case 46: wait_vm<46>(); break;
-    case 47: wait_vm<47>(); break;
+    AOD_VMCASE(0) AOD_VMCASE(1) AOD_VMCASE(2) AOD_VMCASE(3) AOD_VMCASE(4) AOD_VMCASE(5) AOD_VMCASE(6) AOD_VMCASE(7)
+    AOD_VMCASE(8) AOD_VMCASE(9) AOD_VMCASE(10) AOD_VMCASE(11) AOD_VMCASE(12) AOD_VMCASE(13) AOD_VMCASE(14) AOD_VMCASE(15)
+    AOD_VMCASE(16) AOD_VMCASE(17) AOD_VMCASE(18) AOD_VMCASE(19) AOD_VMCASE(20) AOD_VMCASE(21) AOD_VMCASE(22) AOD_VMCASE(23)
+    AOD_VMCASE(24) AOD_VMCASE(25) AOD_VMCASE(26) AOD_VMCASE(27) AOD_VMCASE(28) AOD_VMCASE(29) AOD_VMCASE(30) AOD_VMCASE(31)
+    AOD_VMCASE(32) AOD_VMCASE(33) AOD_VMCASE(34) AOD_VMCASE(35) AOD_VMCASE(36) AOD_VMCASE(37) AOD_VMCASE(38) AOD_VMCASE(39)
+    AOD_VMCASE(40) AOD_VMCASE(41) AOD_VMCASE(42) AOD_VMCASE(43) AOD_VMCASE(44) AOD_VMCASE(45) AOD_VMCASE(46) AOD_VMCASE(47)
     default: wait_vm<48>(); break;      // (waiting for more than asked is always safe)
   }
 }
 
-// raw buffer descriptor in scalar registers for the inline-asm loads (same words as __builtin_amdgcn_make_buffer_rsrc(p, 0, bytes, 0x00020000))
-__device__ __forceinline__ u32x4_t asm_rsrc(const void* p, unsigned bytes) {
+// raw buffer descriptor in scalar registers for the inline-asm loads (same words as buf_rsrc(p, bytes))
+__device__ __forceinline__ u32x4 asm_rsrc(const void* p, unsigned bytes) {
   const unsigned long long a = (unsigned long long)p;
-  u32x4_t d;
+  u32x4 d;
   d[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
   d[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
   d[2] = __builtin_amdgcn_readfirstlane(bytes);
-  d[3] = 0x00020000u;
+  d[3] = BUF_RSRC_FLAGS;
   return d;
 }
 
@@ -132,11 +88,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   const unsigned x_bytes = (unsigned)((long long)p.M * p.K * 2), w_bytes = (unsigned)((long long)p.N * p.K * 2);
   const unsigned y_bytes = (unsigned)((long long)p.M * p.N * 2);
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)x_bytes, 0x00020000);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)w_bytes, 0x00020000);
-  const auto rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)y_bytes, 0x00020000);
-  const u32x4_t rsrc_res = asm_rsrc(p.res, has_res ? y_bytes : 0u), rsrc_mask = asm_rsrc(p.mask, has_mask ? y_bytes : 0u);
-  constexpr unsigned OOB_BASE = 0xf0000000u;      // stays out of range under the per-step increments (operands < 3.5 GiB: host check)
+  const auto rsrc_x = buf_rsrc(p.x, (int)x_bytes);
+  const auto rsrc_w = buf_rsrc(p.w, (int)w_bytes);
+  const auto rsrc_y = buf_rsrc(p.y, (int)y_bytes);
+  const u32x4 rsrc_res = asm_rsrc(p.res, has_res ? y_bytes : 0u), rsrc_mask = asm_rsrc(p.mask, has_mask ? y_bytes : 0u);
 
   // ---- loader: the flat sequence of (tile, K-step) pairs of this workgroup
   // one LDS-DMA wave-instruction fills 8 tile rows x 8 16-B chunks linearly; the XOR swizzle that makes the ds_read_b128 fragment
@@ -150,7 +105,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
       const int m = tm * BM + 64 * i + 8 * uw + prow;
-      aoff[i] = m < p.M ? (unsigned)(((long long)m * p.K + kc * 8) * 2) : OOB_BASE;
+      aoff[i] = m < p.M ? (unsigned)(((long long)m * p.K + kc * 8) * 2) : BUF_OOB;
     }
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
@@ -181,13 +136,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
 
   // ---- hidden residual / mask loads: 8 B per lane and accumulator block, the lane's 4 output channels of its pixel
-  u32x2_t rres[NP], rmsk[NP];
+  u32x2 rres[NP], rmsk[NP];
 #pragma unroll
-  for (int k = 0; k < NP; ++k) { rres[k] = (u32x2_t){0u, 0u}; rmsk[k] = (u32x2_t){0u, 0u}; }
+  for (int k = 0; k < NP; ++k) { rres[k] = (u32x2){0u, 0u}; rmsk[k] = (u32x2){0u, 0u}; }
   auto piece_off = [&](int q, int i, int j) -> unsigned {      // byte offset of the lane's piece (i, j) of tile q in [M][N] bf16
     const int tm = q / tiles_n, tn = q - tm * tiles_n;
     const int m = tm * BM + wm * WM + i * 16 + lr, n = tn * BN + wn * WN + j * 16 + lq * 4;
-    return m < p.M ? (unsigned)(((long long)m * p.N + n) * 2) : OOB_BASE;
+    return m < p.M ? (unsigned)(((long long)m * p.N + n) * 2) : BUF_OOB;
   };
   auto issue_r = [&](int q) {
     if (has_res) {
@@ -232,7 +187,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int nxt = s + 1 < total ? LPS : 0;
       const int n = one ? nxt + E * ((s >= 2 ? 1 : 0) + (s >= 1 ? 1 : 0)) + R * ((s >= 1 ? 1 : 0) + 1)
                         : nxt + E * ((end_m2 ? 1 : 0) + (end_m1 ? 1 : 0)) + (end_s ? R : 0);
-      wait_vm_dyn(n);
+      wait_vm_dyn48(n);
     }
     __builtin_amdgcn_s_barrier();      // everybody's part of stage s has landed; everybody is done reading stage s - 1
     __builtin_amdgcn_sched_barrier(0);
@@ -266,7 +221,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (end_s) {
       if (R) {
         const int n = one ? (s + 2 < total ? LPS : 0) : (s + 1 < total ? LPS : 0) + (s + 2 < total ? LPS : 0);
-        wait_vm_dyn(n);
+        wait_vm_dyn48(n);
         // (the hidden loads' destinations are opaque from here on: no consumer is scheduled above the wait)
 #pragma unroll
         for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(rres[k]), "+v"(rmsk[k]));
@@ -289,12 +244,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] * sc[r] + sh[r];
           if (has_res) {
-            const u32x2_t rv = rres[i * NI + j];
+            const u32x2 rv = rres[i * NI + j];
             v[0] += __uint_as_float(rv[0] << 16); v[1] += __uint_as_float(rv[0] & 0xffff0000u);
             v[2] += __uint_as_float(rv[1] << 16); v[3] += __uint_as_float(rv[1] & 0xffff0000u);
           }
           if (has_mask) {
-            const u32x2_t mv = rmsk[i * NI + j];
+            const u32x2 mv = rmsk[i * NI + j];
             v[0] = __uint_as_float(mv[0] << 16) > 0.f ? v[0] : 0.f; v[1] = __uint_as_float(mv[0] & 0xffff0000u) > 0.f ? v[1] : 0.f;
             v[2] = __uint_as_float(mv[1] << 16) > 0.f ? v[2] : 0.f; v[3] = __uint_as_float(mv[1] & 0xffff0000u) > 0.f ? v[3] : 0.f;
           }
@@ -307,8 +262,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           bf16x4 ov;
 #pragma unroll
           for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)v[r];
-          const unsigned off = mok ? (unsigned)(((long long)m * p.N + n) * 2) : OOB_BASE;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, ov), rsrc_y, (int)off, 0, 0);
+          const unsigned off = mok ? (unsigned)(((long long)m * p.N + n) * 2) : BUF_OOB;
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ov), rsrc_y, (int)off, 0, 0);
           acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
       }

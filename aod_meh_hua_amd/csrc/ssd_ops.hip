@@ -1,9 +1,7 @@
 // Kernels specific to the SSD300-VGG16 + MEH variant (BASELINE config 0; reference: backbones/ssd_vgg.py,
 // necks/ssd_neck.py:105-128 L2Norm, dense_heads/My_L_ssd_head.py:182-224 losses).  Small tensors (300x300 inputs):
 // simple one-thread-per-output kernels; NHWC bf16 activations, fp32 logits.
-#include "common.h"
-
-static inline int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
+#include "tile_prims.h"
 
 // ---------------------------------------------------------------- generic max-pool (k x k, stride s, pad p), NHWC bf16
 // torch semantics: windows clipped to the image, -inf padding, first maximum in (dy, dx) scan order wins the gradient.
@@ -82,7 +80,7 @@ __global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* _
 }
 extern "C" int aod_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int s, int p, aod_stream_t stream) {
   AOD_CHECK_ARG(x && y && C % 8 == 0 && k >= 1 && s >= 1, "maxpool_fwd: bad args");
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for<4096>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (bf16_t*)y, B, H, W, C / 8, OH, OW, k, s, p);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -90,7 +88,7 @@ extern "C" int aod_maxpool_fwd(const void* x, void* y, int B, int H, int W, int 
 extern "C" int aod_maxpool_bwd(const void* x, const void* g, void* gx, int B, int H, int W, int C, int OH, int OW, int k, int s, int p,
                                aod_stream_t stream) {
   AOD_CHECK_ARG(x && g && gx && C % 8 == 0, "maxpool_bwd: bad args");
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for<4096>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (const bf16_t*)g, (bf16_t*)gx, B, H, W, C / 8, OH, OW, k, s, p);
   AOD_LAUNCH_CHECK();
   return 0;

@@ -5,10 +5,10 @@
 //   1  the 20 x 36-pixel input patch (23 KB) and the 64 x 256 filter (32 KB) arrive by LDS-DMA;
 //   2  the 17 x 33 conv outputs the pool windows of the tile need (9 % recompute) are computed as 36 row blocks of 16 pixels: the im2col
 //      row of a pixel and filter row R is 4 pixels x 32 B = 128 contiguous bytes of the patch, read as fragments straight from it;
-//      accumulators transposed with the paired-block channel permutation of bottleneck.hip -> BN + ReLU -> bf16 conv tile in LDS (72 KB),
+//      accumulators transposed with the paired-block channel permutation (wrow, tile_prims.h) -> BN + ReLU -> bf16 conv tile in LDS (72 KB),
 //      zero outside the image (all values are >= 0 after the ReLU, so a zero pad equals the pool's -inf pad);
 //   3  3 x 3 / stride-2 max over the LDS tile, 16-B stores of the pooled pixels.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -32,31 +32,19 @@ constexpr int OFF_CONV = OFF_W + 4 * 8192;          // [576][128 B]
 constexpr int OFF_VEC = OFF_CONV + CBLK * 16 * 128; // scale, shift
 constexpr int LDS_BYTES = OFF_VEC + 128 * 4;        // 130560
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-// filter images: the paired-block row permutation (wrow) makes the 16 lanes of a fragment read rows {0-3, 8-11, 16-19, 24-27} (+4): rows r and
-// r + 16 share (r >> 1) & 7 and lie 2048 B apart -- the same banks.  One more row bit in the XOR key separates them (PMC before: 35 % of
-// the LDS cycles of the kernel were bank conflicts).
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
-
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_pool_kernel(const StemArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int ntile = p.tiles_y * p.tiles_x;
-  const int wg = xcd_remap(blockIdx.x, p.B * ntile);
+  const int wg = xcd_swizzle(blockIdx.x, p.B * ntile);
   const int b = wg / ntile, tt = wg - b * ntile;
   const int py0 = (tt / p.tiles_x) * PTH, px0 = (tt % p.tiles_x) * PTW;   // first pooled pixel of the tile
   const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;                          // first conv output behind it
   const int iy0 = cy0 - 2, ix0 = cx0 - 2;                                  // first input (space-to-depth) pixel of the patch
-  constexpr unsigned OOB = 0xf0000000u;
-  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)((long long)p.B * p.H2 * p.W2 * 32), 0x00020000);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, 64 * 256 * 2, 0x00020000);
+  const auto rsrc_x = buf_rsrc(p.x, (int)((long long)p.B * p.H2 * p.W2 * 32));
+  const auto rsrc_w = buf_rsrc(p.w, 64 * 256 * 2);
 
   float* const vec = reinterpret_cast<float*>(smem + OFF_VEC);
   if (t < 64) vec[t] = p.scale[t];
@@ -68,7 +56,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int px = q >> 1, pr = px / PW, pc = px - pr * PW;
     const int y = iy0 + pr, x = ix0 + pc;
     const bool ok = q < PATCH_BYTES / 16 && (unsigned)y < (unsigned)p.H2 && (unsigned)x < (unsigned)p.W2;
-    const unsigned off = ok ? (unsigned)((((long long)b * p.H2 + y) * p.W2 + x) * 32 + (q & 1) * 16) : OOB;
+    const unsigned off = ok ? (unsigned)((((long long)b * p.H2 + y) * p.W2 + x) * 32 + (q & 1) * 16) : BUF_OOB;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(smem + OFF_PATCH + k * 1024), 16, off, 0, 0, 0);
   }
   {

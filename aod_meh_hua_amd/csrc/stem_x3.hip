@@ -14,7 +14,7 @@
 //   3  BN + ReLU, the tile as fp32 in LDS over the patch / filter region (zero outside the image: every value is >= 0); 3 x 3 / stride-2
 //      max, then the roundings of the three-launch path in its order (the conv output to head + tail, the pooled value to head + tail:
 //      rounding is monotone, so it commutes with the max), head + tail stores of the pooled pixels.
-#include "common.h"
+#include "tile_prims.h"
 
 namespace {
 
@@ -39,19 +39,11 @@ constexpr int OFF_VEC = CBLK * 16 * 256;            // 147 456: scale, shift
 constexpr int LDS_BYTES = OFF_VEC + 128 * 4;        // 147 968
 static_assert(OFF_WL + 32768 <= OFF_VEC, "lds map");
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-// filter images: rows of 128 B, the key of stem.hip (fragment lanes read rows {0-3, 8-11, 16-19, 24-27} (+4): one more row bit in the XOR)
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7) ^ (((row >> 4) & 1) << 1)) << 4); }
-__device__ __forceinline__ int wrow(int j, int lr) { return (j >> 1) * 32 + (lr >> 2) * 8 + (j & 1) * 4 + (lr & 3); }
 // conv tile: rows of 256 B (64 fp32), 16-B chunks XORed with the row
 __device__ __forceinline__ int cswz(int row, int c16) { return row * 256 + ((c16 ^ (row & 15)) << 4); }
 
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_pool_x3_kernel(const StemX3Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   const int t = threadIdx.x, lane = t & 63;
   const int uw = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, lq = lane >> 4;
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // pixels are loaded into registers before the current tile's conv, so the image's memory latency is exposed once per workgroup.  (The
   // filter comes back from L2 by LDS-DMA for every tile -- the conv tile overlays it; kept in registers, 8 x 16 B per thread, the kernel spills.)
   const int q0 = (int)((long long)blockIdx.x * total / gridDim.x), q1 = (int)((long long)(blockIdx.x + 1) * total / gridDim.x);
-  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, 64 * 16 * 64 * 2, 0x00020000);
+  const auto rsrc_w = buf_rsrc(p.w, 64 * 16 * 64 * 2);
 
   float* const vec = reinterpret_cast<float*>(smem + OFF_VEC);
   if (t < 64) vec[t] = p.scale[t];

@@ -3,15 +3,7 @@
 // 2 * ceil32(C) columns [h(0..31) | l(0..31) | h(32..63) | l(32..63) | ...].  Every kernel here re-forms v = h + l in fp32, computes like its
 // bf16 twin in elementwise.hip and writes (h, l) again: nothing in this mode rounds an activation or a gradient to 8 significant bits.
 // Unit of work: one OCTET = 8 consecutive logical channels = a 16-B head piece and the 16-B tail piece 64 B behind it.
-#include "common.h"
-
-static inline int grid_for(long long nvec) {
-  long long b = (nvec + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
-// physical column (elements) of logical octet q
-__device__ __forceinline__ int xoct(int q) { return ((q >> 2) << 6) + ((q & 3) << 3); }
+#include "tile_prims.h"
 
 __device__ __forceinline__ void xload(const bf16_t* __restrict__ p, float (&v)[8]) {
   const bf16x8 h = *reinterpret_cast<const bf16x8*>(p), l = *reinterpret_cast<const bf16x8*>(p + 32);
@@ -41,7 +33,7 @@ extern "C" int aod_x3_split(const float* src, void* dst, int64_t M, int C, aod_s
   AOD_CHECK_ARG(src && dst && C >= 1, "x3_split: bad args");
   if (M == 0) return 0;
   const int Q = (C + 31) / 32 * 4;          // octets of the padded row (pad channels are written as zeros)
-  hipLaunchKernelGGL(x3_split_kernel, dim3(grid_for(M * Q)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long long)M, C, Q);
+  hipLaunchKernelGGL(x3_split_kernel, dim3(grid_for<2048>(M * Q)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long long)M, C, Q);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -60,7 +52,7 @@ extern "C" int aod_x3_merge(const void* src, float* dst, int64_t M, int C, aod_s
   AOD_CHECK_ARG(src && dst && C >= 1, "x3_merge: bad args");
   if (M == 0) return 0;
   const int Q = (C + 31) / 32 * 4;
-  hipLaunchKernelGGL(x3_merge_kernel, dim3(grid_for(M * Q)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, dst, (long long)M, C, Q);
+  hipLaunchKernelGGL(x3_merge_kernel, dim3(grid_for<2048>(M * Q)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, dst, (long long)M, C, Q);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -79,7 +71,7 @@ __global__ void x3_add_kernel(const bf16_t* __restrict__ a, const bf16_t* __rest
 extern "C" int aod_x3_add(const void* a, const void* b, void* out, int64_t n, aod_stream_t stream) {
   AOD_CHECK_ARG(a && b && out && n % 64 == 0, "x3_add: n (bf16 elements) must be a multiple of 64");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(x3_add_kernel, dim3(grid_for(n / 16)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)(n / 16));
+  hipLaunchKernelGGL(x3_add_kernel, dim3(grid_for<2048>(n / 16)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)(n / 16));
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -114,7 +106,7 @@ __global__ void x3_nchw_to_s2d_kernel(const float* __restrict__ src, bf16_t* __r
 }
 extern "C" int aod_x3_nchw_f32_to_s2d(const float* src, void* dst, int B, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C >= 1 && C <= 4 && H % 2 == 0 && W % 2 == 0, "x3_nchw_to_s2d: C <= 4 and even H, W required (C %d, %d x %d)", C, H, W);
-  hipLaunchKernelGGL(x3_nchw_to_s2d_kernel, dim3(grid_for((long long)B * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H, W);
+  hipLaunchKernelGGL(x3_nchw_to_s2d_kernel, dim3(grid_for<2048>((long long)B * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -148,7 +140,7 @@ __global__ void x3_maxpool_kernel(const bf16_t* __restrict__ src, bf16_t* __rest
 extern "C" int aod_x3_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C % 64 == 0, "x3_maxpool: the X-layout width must be a multiple of 64");
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1, Q = C / 16;
-  hipLaunchKernelGGL(x3_maxpool_kernel, dim3(grid_for((long long)B * OH * OW * Q)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst,
+  hipLaunchKernelGGL(x3_maxpool_kernel, dim3(grid_for<2048>((long long)B * OH * OW * Q)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst,
                      B, H, W, Q, OH, OW);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -175,7 +167,7 @@ __global__ void x3_upsample_add_kernel(const bf16_t* __restrict__ src, const bf1
 }
 extern "C" int aod_x3_upsample2x_add_to(const void* top, const void* lateral, void* out, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(top && lateral && out && C % 64 == 0, "x3_upsample_add_to: the X-layout width must be a multiple of 64");
-  hipLaunchKernelGGL(x3_upsample_add_kernel, dim3(grid_for((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)top,
+  hipLaunchKernelGGL(x3_upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)top,
                      (const bf16_t*)lateral, (bf16_t*)out, B, h, w, C / 16, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -205,7 +197,7 @@ __global__ void x3_upsample_add_bwd_kernel(const bf16_t* __restrict__ gd, bf16_t
 }
 extern "C" int aod_x3_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(g_dst && g_src && C % 64 == 0, "x3_upsample_add_bwd_set: the X-layout width must be a multiple of 64");
-  hipLaunchKernelGGL(x3_upsample_add_bwd_kernel, dim3(grid_for((long long)B * h * w * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g_dst,
+  hipLaunchKernelGGL(x3_upsample_add_bwd_kernel, dim3(grid_for<2048>((long long)B * h * w * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g_dst,
                      (bf16_t*)g_src, B, h, w, C / 16, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -414,7 +406,7 @@ __global__ void x3_nchw_to_nhwc_kernel(const float* __restrict__ src, bf16_t* __
 }
 extern "C" int aod_x3_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C >= 1 && C <= 32, "x3_nchw_to_nhwc: at most 32 channels (got %d)", C);
-  hipLaunchKernelGGL(x3_nchw_to_nhwc_kernel, dim3(grid_for((long long)B * H * W * 4)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H * W);
+  hipLaunchKernelGGL(x3_nchw_to_nhwc_kernel, dim3(grid_for<2048>((long long)B * H * W * 4)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H * W);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -491,7 +483,7 @@ __global__ void x3_maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t
 }
 extern "C" int aod_x3_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int s, int p, aod_stream_t stream) {
   AOD_CHECK_ARG(x && y && C % 64 == 0 && k >= 1 && s >= 1, "x3_maxpool_fwd: bad args");
-  hipLaunchKernelGGL(x3_maxpool_fwd_kernel, dim3(grid_for((long long)B * OH * OW * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+  hipLaunchKernelGGL(x3_maxpool_fwd_kernel, dim3(grid_for<2048>((long long)B * OH * OW * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (bf16_t*)y, B, H, W, C / 16, OH, OW, k, s, p);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -499,7 +491,7 @@ extern "C" int aod_x3_maxpool_fwd(const void* x, void* y, int B, int H, int W, i
 extern "C" int aod_x3_maxpool_bwd(const void* x, const void* g, void* gx, int B, int H, int W, int C, int OH, int OW, int k, int s, int p,
                                   aod_stream_t stream) {
   AOD_CHECK_ARG(x && g && gx && C % 64 == 0, "x3_maxpool_bwd: bad args");
-  hipLaunchKernelGGL(x3_maxpool_bwd_kernel, dim3(grid_for((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+  hipLaunchKernelGGL(x3_maxpool_bwd_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (const bf16_t*)g, (bf16_t*)gx, B, H, W, C / 16, OH, OW, k, s, p);
   AOD_LAUNCH_CHECK();
   return 0;
