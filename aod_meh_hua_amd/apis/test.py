@@ -100,6 +100,31 @@ class Uncertainty_fns:
         return Uncertainty_fns.CCMS(cfg, *args, **dict(kwargs, class_weighted=True))
 
     @staticmethod
+    def _enms_options(kwargs):
+        # what ENMS / DivProto read of calculate_uncertainty's kwargs: score_thr (the object gate, default 0.3) and their own options; the
+        # other HUA options have no meaning for them
+        own = {k: kwargs[k] for k in ('max_obj', 'measure', 't_enms') if kwargs.get(k) is not None}
+        if kwargs.get('class_weighted'):
+            own['class_weighted'] = True
+        return own
+
+    @staticmethod
+    def ENMS(cfg, *args, **kwargs):
+        # entropy-NMS uncertainty (Wu et al., CVPR 2022): ordinary scores, no labelled set is read
+        model, dataloader = args
+        thr = kwargs.get('score_thr')
+        return ENMS_uncertainty(cfg, model, dataloader, score_thr=0.3 if thr is None else thr, **Uncertainty_fns._enms_options(kwargs))
+
+    @staticmethod
+    def DivProto(cfg, *args, **kwargs):
+        # ENMS + the progressive diversity pick (Wu et al., CVPR 2022): needs the labelled set (it is excluded from the sweep)
+        # and selects by rank like Coreset
+        model, dataloader = args
+        own = Uncertainty_fns._enms_options(kwargs)
+        own.update({k: kwargs[k] for k in ('t_intra', 't_inter', 'alpha', 'beta', 'class_balance') if kwargs.get(k) is not None})
+        return DivProto_uncertainty(cfg, model, dataloader, **_labelled_options('DivProto', kwargs), **own)
+
+    @staticmethod
     def _loc_stability(combine, cfg, *args, **kwargs):
         # localization stability (Kao et al., ACCV 2018): reads score_thr (the object gate, default 0.3), sigmas, seed and
         # same_class; the HUA options that calculate_uncertainty's callers pass for the Entropy_* pools have no meaning for it
@@ -675,6 +700,86 @@ def CCMS_uncertainty(cfg, model, data_loader, X_L=None, budget=None, candidate_f
     ci = torch.from_numpy(cand).to(pool['unc'].device)
     dist = ccms_distance(pool['feat'][ci].contiguous(), pool['cls'][ci].contiguous(), pool['w'][ci].contiguous(), pool['cnt'][ci].contiguous())
     return _pick_scores(ci[kcenter_greedy_matrix(dist, [], budget)[0]], pool['unc'].shape[0])
+
+
+@torch.no_grad()
+def single_gpu_enms(model, data_loader, max_obj=32, score_thr=0.3, measure='entropy', t_enms=0.5, keep_objects=False, **kwargs):
+    """ENMS scores and class prototypes of the whole pool on _PoolPass's loop: single_gpu_object_descriptors' pass -- sharded,
+    prefetched, the forward (isEval=True, _padded=True, objDesc=max_obj, objUnc=True: the descriptors and the per-object measure h in
+    their slots) replayed from one captured graph while the batch shape repeats -- with scoring.enms_prototypes run per batch behind the
+    replay on the same stream, on the graph's static outputs; its rows are copied into preallocated pool tensors, which
+    parallel.gather_rows makes whole on every rank.  The object features are not kept: the prototype store takes their place.
+
+    Returns a dict of device tensors: enms [N] fp32 (the entropy-NMS score: the sum of `measure` over the objects that survive the
+    feature-similarity NMS at t_enms), kept [N] int32, proto [N, max_obj, C] fp32, pcls [N, max_obj] int32 (-1 pad), pconf [N, max_obj]
+    fp32, pcnt [N] int32, missing [N] int32 (always 0); keep_objects=True adds h, w [N, max_obj] fp32, cls [N, max_obj] int32 and cnt [N]
+    int32, the objects the scores were made of.  A row's bits depend on its image alone -- not on the batch size, the rank count, or eager /
+    replayed execution."""
+    from ..scoring import CCMS_MAX_OBJ, UNC_MEASURES, enms_prototypes
+    if measure not in UNC_MEASURES:
+        raise ValueError(f"single_gpu_enms: unknown measure {measure!r} (expected 'entropy', 'margin' or 'leastconf')")
+    max_obj, score_thr, t_enms = int(max_obj), float(score_thr), float(t_enms)
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'single_gpu_enms: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    if score_thr != score_thr or t_enms != t_enms:
+        raise ValueError('single_gpu_enms: score_thr or t_enms is NaN')
+    neck = _fpn_neck(model, 'single_gpu_enms: ENMS / DivProto object descriptors')
+    N, Cc, dev = len(data_loader.dataset), int(neck.out_channels), next(model.parameters()).device
+    f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    store = dict(enms=f32(N), kept=i32(N), proto=f32(N, max_obj, Cc), pcls=torch.full((N, max_obj), -1, dtype=torch.int32, device=dev),
+                 pconf=f32(N, max_obj), pcnt=i32(N), missing=i32(N))
+    if keep_objects:
+        store.update(h=f32(N, max_obj), w=f32(N, max_obj), cls=torch.full((N, max_obj), -1, dtype=torch.int32, device=dev), cnt=i32(N))
+    kwargs.setdefault('isUnc', False)
+    fkw = dict(kwargs, objDesc=max_obj, objUnc=True, score_thr=score_thr, unc_measure=measure, unc_aggregate='sum')
+
+    def write(out, rows):
+        feat, cls, w, cnt, missing, h = out[4:10]
+        res = enms_prototypes(feat, cls, w, h, cnt, t_enms)
+        for name, t in zip(('enms', 'kept', 'proto', 'pcls', 'pconf', 'pcnt'), res):
+            store[name][rows].copy_(t)
+        store['missing'][rows].copy_(missing)
+        if keep_objects:
+            for name, t in (('h', h), ('w', w), ('cls', cls), ('cnt', cnt)):
+                store[name][rows].copy_(t)
+    return _row_store_pass(model, data_loader, ('enms',), dict(isEval=True, _padded=True), fkw, store, write)
+
+
+def ENMS_uncertainty(cfg, model, data_loader, max_obj=32, score_thr=0.3, measure='entropy', t_enms=0.5, class_weighted=False, **kwargs):
+    """Entropy-NMS uncertainty (the first half of Wu, Chen, Huang, "Entropy-based Active Learning for Object Detection with
+    Progressive Diversity Constraint", CVPR 2022; the reference has none) in the form update_X_L takes: per image the sum of the posterior
+    `measure` over the objects that survive an NMS by feature similarity (single_gpu_enms), so that near-duplicate instances of one class
+    count once.  Returns the CPU [N] fp32 vector; these are ordinary scores, zeroRate stays on.  class_weighted as in CCMS_uncertainty."""
+    if class_weighted:
+        sync_class_difficulty(model)
+        kwargs['class_weighted'] = True
+    return single_gpu_enms(model, data_loader, max_obj=max_obj, score_thr=score_thr, measure=measure, t_enms=t_enms, **kwargs)['enms'].cpu()
+
+
+def DivProto_uncertainty(cfg, model, data_loader, X_L=None, budget=None, max_obj=32, score_thr=0.3, measure='entropy', t_enms=0.5,
+                         t_intra=0.7, t_inter=0.3, alpha=0.5, beta=0.75, class_balance=True, class_weighted=False, **kwargs):
+    """ENMS + DivProto acquisition (Wu, Chen, Huang, CVPR 2022; the reference has none) in the form update_X_L takes: the ENMS
+    score and the class prototypes of every image (single_gpu_enms), the unlabelled images ordered by that score
+    (scoring.divproto_order), then the progressive pick on the device (scoring.divproto_select): an image whose every class prototype
+    repeats one already picked (cosine above t_intra) is passed over, and with class_balance the share beta of the budget goes to images
+    that bring a class the picks hold least.  Every rank runs the pick on the same tensors and gets the same picks.  budget: default
+    cfg.X_S_size.  Returns a CPU [N] fp32 vector: the image picked at step t = 0 .. budget - 1 scores budget - t, every other image 0 --
+    with a falsy zeroRate update_X_L's arg[-X_S_size:] selects exactly the picks.  class_weighted as in CCMS_uncertainty."""
+    from ..scoring import divproto_order, divproto_select
+    if X_L is None:
+        raise TypeError('DivProto_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are excluded from the sweep')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    if class_weighted:
+        sync_class_difficulty(model)
+        kwargs['class_weighted'] = True
+    pool = single_gpu_enms(model, data_loader, max_obj=max_obj, score_thr=score_thr, measure=measure, t_enms=t_enms, **kwargs)
+    module = getattr(model, 'module', model)
+    n_cls = int(module.bbox_head.num_classes)
+    order = divproto_order(pool['enms'], X_L)
+    picks, _ = divproto_select(order, pool['proto'], pool['pcls'], pool['pconf'], pool['pcnt'], n_cls, budget, t_intra=t_intra, t_inter=t_inter,
+                               alpha=alpha, beta=beta, class_balance=class_balance)
+    return _pick_scores(picks, pool['enms'].shape[0])
 
 
 def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, class_weighted=False, **kwargs):

@@ -739,6 +739,178 @@ def ccms_candidates(unc, X_L, budget, factor=4):
     return order[:M].astype(np.int64)
 
 
+DIVPROTO_MAX_CLASSES = 128
+
+
+def divproto_chunk():
+    """sweep positions one selection launch of divproto_select handles"""
+    return int(_C.lib.aod_divproto_chunk())
+
+
+def _check_tensors(name, specs):
+    """dtype, dim and contiguity of (name, tensor, dtype, ndim) specs: ccms_distance's checks and messages under the caller's `name`"""
+    for n, t, dt, nd in specs:
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"{name}: {n} is not a {nd}-D {str(dt).replace('torch.', '')} tensor")
+        if not t.is_contiguous():
+            raise ValueError(f'{name}: {n} is not contiguous; no copy is made here')
+
+
+def _check_devices(name, ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise _cpu_refusal(name)
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError(f'{name}: the tensors live on different devices ({sorted({str(t.device) for t in ts})})')
+
+
+def _check_obj_shape(name, what, shape):
+    N, K, Cc = (int(v) for v in shape)
+    if N < 1:
+        raise ValueError(f'{name}: {what} has shape {tuple(shape)}: at least one image is needed')
+    if not 1 <= K <= CCMS_MAX_OBJ:
+        raise ValueError(f'{name}: {what} has shape {tuple(shape)}: 1..{CCMS_MAX_OBJ} objects per image are supported')
+    if Cc < 8 or Cc % 8 or Cc > CCMS_MAX_CHANNELS:
+        raise ValueError(f'{name}: {what} has shape {tuple(shape)}: the channels must be a multiple of 8 in 8..{CCMS_MAX_CHANNELS}')
+    return N, K, Cc
+
+
+def object_measure(obj_out, dets, num, obj_cand=None, max_obj=32, score_thr=0.3):
+    """The per-object posterior measure in object_descriptors' slots (aod_object_measure): h [B, max_obj] fp32 = obj_out
+    (det_uncertainty(..., want_objects=True)'s [B, max_num], the class weight included when it ran class-weighted) at the detection rows
+    j < num[b] whose score exceeds score_thr (strict), the first max_obj in row order -- object_descriptors' own slot rule, obj_cand (its
+    matched candidate rows; a row without one takes no slot) included; 0 behind them.  Device tensors, no host sync."""
+    _check_tensors('object_measure', (('obj_out', obj_out, torch.float32, 2), ('dets', dets, torch.float32, 3), ('num', num, torch.int32, 1))
+                   + ((('obj_cand', obj_cand, torch.int32, 2),) if obj_cand is not None else ()))
+    B, max_num = (int(v) for v in obj_out.shape)
+    max_obj, score_thr = int(max_obj), float(score_thr)
+    if B < 1 or not 1 <= max_num <= UNC_MAX_DET or tuple(dets.shape) != (B, max_num, 5) or tuple(num.shape) != (B,):
+        raise ValueError(f'object_measure: obj_out {tuple(obj_out.shape)}, dets {tuple(dets.shape)}, num {tuple(num.shape)}: expected (B, max_num), '
+                         f'(B, max_num, 5), (B,) with 1 <= max_num <= {UNC_MAX_DET}')
+    if obj_cand is not None and tuple(obj_cand.shape) != (B, max_num):
+        raise ValueError(f'object_measure: obj_cand has shape {tuple(obj_cand.shape)}, expected ({B}, {max_num})')
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'object_measure: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    if score_thr != score_thr:
+        raise ValueError('object_measure: score_thr is NaN')
+    _check_devices('object_measure', [obj_out, dets, num] + ([obj_cand] if obj_cand is not None else []))
+    h = torch.empty(B, max_obj, dtype=torch.float32, device=obj_out.device)
+    call('aod_object_measure', ptr(obj_out), ptr(dets), ptr(num), ptr(obj_cand), B, max_num, max_obj, score_thr, ptr(h), stream())
+    return h
+
+
+def enms_prototypes(feat, cls, w, h, cnt, t_enms=0.5, want_picks=False):
+    """ENMS score and class prototypes of every image of a batch (aod_enms_prototypes; Wu et al., CVPR 2022).
+
+    feat [B, max_obj, C] fp32, cls [B, max_obj] int32, w [B, max_obj] fp32, cnt [B] int32 as object_descriptors writes them, h [B, max_obj]
+    fp32 the per-object measure in the same slots (object_measure); rows >= cnt are not used.  max_obj <= 64, C % 8 == 0, 8 <= C <= 256.
+    ENMS: repeatedly take the alive object with the largest h (lowest slot on a tie), add its h, and drop it and every alive object of its
+    class whose cosine to it exceeds t_enms (strict; t_enms >= 1 drops nothing).  Prototypes: per class present among ALL the image's objects, ascending, the
+    (h + 2^-10)-weighted sum of its objects' features, L2-normalised, and the class's largest w.
+    Returns (enms [B] fp32, kept [B] int32, proto [B, max_obj, C] fp32, pcls [B, max_obj] int32 (-1 pad), pconf [B, max_obj] fp32 (0 pad),
+    pcnt [B] int32) on the device, no host sync; want_picks appends pick [B, max_obj] int32: the picked slots in pick order, -1 behind them.
+    An image's outputs have the same bits alone and inside any batch."""
+    name = 'enms_prototypes'
+    _check_tensors(name, (('feat', feat, torch.float32, 3), ('cls', cls, torch.int32, 2), ('w', w, torch.float32, 2), ('h', h, torch.float32, 2),
+                          ('cnt', cnt, torch.int32, 1)))
+    B, K, Cc = _check_obj_shape(name, 'feat', feat.shape)
+    for n, t in (('cls', cls), ('w', w), ('h', h)):
+        if tuple(t.shape) != (B, K):
+            raise ValueError(f'{name}: {n} has shape {tuple(t.shape)}, expected ({B}, {K})')
+    if tuple(cnt.shape) != (B,):
+        raise ValueError(f'{name}: cnt has shape {tuple(cnt.shape)}, expected ({B},)')
+    t_enms = float(t_enms)
+    if t_enms != t_enms:
+        raise ValueError(f'{name}: t_enms is NaN')
+    _check_devices(name, [feat, cls, w, h, cnt])
+    dev = feat.device
+    enms = torch.empty(B, dtype=torch.float32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    proto = torch.empty(B, K, Cc, dtype=torch.float32, device=dev)
+    pcls = torch.empty(B, K, dtype=torch.int32, device=dev)
+    pconf = torch.empty(B, K, dtype=torch.float32, device=dev)
+    pcnt = torch.empty(B, dtype=torch.int32, device=dev)
+    pick = torch.empty(B, K, dtype=torch.int32, device=dev) if want_picks else None
+    call('aod_enms_prototypes', ptr(feat), ptr(cls), ptr(w), ptr(h), ptr(cnt), B, K, Cc, t_enms, ptr(enms), ptr(kept), ptr(proto), ptr(pcls),
+         ptr(pconf), ptr(pcnt), ptr(pick), stream())
+    return (enms, kept, proto, pcls, pconf, pcnt) + ((pick,) if want_picks else ())
+
+
+def divproto_order(enms, X_L):
+    """The sweep order of the DivProto pick, on the host: the images not in X_L by `enms` descending, ties by ascending index.
+    Returns the int64 index array [M]."""
+    u = enms.detach().cpu().numpy() if torch.is_tensor(enms) else np.asarray(enms)
+    u = u.reshape(-1).astype(np.float64)
+    lab = _index_array('divproto_order', X_L, u.size, arg='X_L', distinct=False)
+    if np.isnan(u).any():
+        raise ValueError('divproto_order: the ENMS scores hold a NaN')
+    free = np.ones(u.size, bool)
+    free[lab] = False
+    idx = np.nonzero(free)[0]
+    return idx[np.argsort(-u[idx], kind='stable')].astype(np.int64)      # (idx ascends: a stable sort breaks ties by ascending index)
+
+
+def divproto_quotas(n_cls, budget, alpha=0.5, beta=0.75):
+    """the integers the selection kernel takes: (n_minor, quota, free) = (ceil(alpha n_cls), ceil(reserved / n_minor),
+    budget - reserved) with reserved = min(budget, ceil(beta budget))"""
+    n_cls, budget, alpha, beta = int(n_cls), int(budget), float(alpha), float(beta)
+    if not 1 <= n_cls <= DIVPROTO_MAX_CLASSES:
+        raise ValueError(f'divproto_select: n_cls must be in 1..{DIVPROTO_MAX_CLASSES}, got {n_cls}')
+    if budget < 1:
+        raise ValueError(f'divproto_select: budget must be at least 1, got {budget}')
+    for n, v in (('alpha', alpha), ('beta', beta)):
+        if not 0 < v <= 1:
+            raise ValueError(f'divproto_select: {n} must lie in (0, 1], got {v}')
+    n_minor = int(np.ceil(alpha * n_cls))
+    reserved = min(budget, int(np.ceil(beta * budget)))
+    return n_minor, -(-reserved // n_minor), budget - reserved
+
+
+def divproto_select(order, proto, pcls, pconf, pcnt, n_cls, budget, t_intra=0.7, t_inter=0.3, alpha=0.5, beta=0.75, class_balance=True,
+                    _chunk=None):
+    """The progressive DivProto pick (aod_divproto_select; Wu et al., CVPR 2022) over the images `order` (distinct pool indices
+    in sweep order: divproto_order) of the pool tensors proto [N, max_obj, C] fp32, pcls [N, max_obj] int32, pconf [N, max_obj] fp32,
+    pcnt [N] int32 (enms_prototypes' outputs, contiguous, on the device).
+
+    An image is skipped as redundant when every one of its classes has a prototype among the picks so far with a cosine above t_intra
+    to its own; with class_balance it is accepted when it serves a minority class (one of the ceil(alpha n_cls) classes the picks hold
+    least, present with a confidence above t_inter and below its quota) or while the free share (1 - beta) of the budget lasts,
+    else deferred.  t_intra >= 1 makes no image redundant.  A sweep that ends short is filled with the deferred, then the redundant images in sweep order.
+    Returns (picks [budget] int64, stage [budget] int32: 1 minority / no balance, 2 free share, 3 fill) on the device; all launches are
+    enqueued on the current stream, no host sync behind the upload of `order`.  _chunk: sweep positions per launch (tests; the result
+    does not depend on it)."""
+    name = 'divproto_select'
+    _check_tensors(name, (('proto', proto, torch.float32, 3), ('pcls', pcls, torch.int32, 2), ('pconf', pconf, torch.float32, 2),
+                          ('pcnt', pcnt, torch.int32, 1)))
+    N, K, Cc = _check_obj_shape(name, 'proto', proto.shape)
+    for n, t in (('pcls', pcls), ('pconf', pconf)):
+        if tuple(t.shape) != (N, K):
+            raise ValueError(f'{name}: {n} has shape {tuple(t.shape)}, expected ({N}, {K})')
+    if tuple(pcnt.shape) != (N,):
+        raise ValueError(f'{name}: pcnt has shape {tuple(pcnt.shape)}, expected ({N},)')
+    n_minor, quota, free = divproto_quotas(n_cls, budget, alpha, beta)
+    n_cls, budget = int(n_cls), int(budget)
+    t_intra, t_inter = float(t_intra), float(t_inter)
+    if t_intra != t_intra or t_inter != t_inter:
+        raise ValueError(f'{name}: a threshold is NaN (t_intra {t_intra}, t_inter {t_inter})')
+    idx = _index_array(name, order, N, arg='order')
+    M = int(idx.size)
+    if budget > M:
+        raise ValueError(f'{name}: budget {budget} exceeds the {M} images of the sweep')
+    chunk = 0 if _chunk is None else int(_chunk)
+    if chunk < 0:
+        raise ValueError(f'{name}: _chunk must be positive, got {chunk}')
+    _check_devices(name, [proto, pcls, pconf, pcnt])
+    dev = proto.device
+    order_d = torch.from_numpy(idx).to(dev)
+    picks = torch.empty(budget, dtype=torch.int64, device=dev)
+    stage = torch.empty(budget, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(_C.lib.aod_divproto_ws_len(M, n_cls, budget)) // 8 + 1, dtype=torch.int64, device=dev)
+    call('aod_divproto_select', ptr(order_d), M, N, ptr(proto), ptr(pcls), ptr(pconf), ptr(pcnt), K, Cc, n_cls, budget, t_intra, t_inter, n_minor,
+         quota, free, int(bool(class_balance)), chunk, ptr(picks), ptr(stage), ptr(ws), stream())
+    return picks, stage
+
+
 LOCSTAB_COMBINES = {'ls': 0, 'ls+c': 1}
 LOCSTAB_MAX_LEVELS = int(_C.lib.aod_loc_stability_max_levels())      # (written once, in csrc/loc_stability.hip)
 LOCSTAB_SIGMAS = (8, 16, 24, 32, 40, 48)      # Kao et al.'s noise levels, 0..255 pixel units
@@ -927,6 +1099,9 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                  with _padded=True, detPost=True -> (dets, labels, num, post [B,max,W] fp32, missing [B] int32): the same triple
                                         and det_posterior's outputs, the class-posterior row of every detection (zero rows >= num);
                                         ValueError together with objDesc or detUnc
+                 with _padded=True, objDesc=max_obj -> (dets, labels, num, unc, feat, cls, w, cnt, missing): the triple, the
+                                        posterior score and object_descriptors' outputs; objUnc=True (with objDesc only)
+                                        appends h [B,max_obj] fp32, the per-object measure in the same slots (object_measure)
                  with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
     hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / Entropy_Avg / detUnc paths.
@@ -954,6 +1129,8 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     if sigmoid:
         refuse_hua(head, **kwargs)
     _class_weight(head, None, kwargs)          # (class_weighted on a head without the option: refused before the first launch)
+    if kwargs.get('objUnc') and not kwargs.get('objDesc'):
+        raise ValueError('objUnc is offered together with objDesc only: it appends the per-object measure in the descriptors\' slots')
     if isUnc and uPool == 'Entropy_NoNMS':
         raise NotImplementedError('uncertainty_pool=Entropy_NoNMS crashes in the reference too (ComputeScaleUnc with L_scores=None)')
     lam_mode = getattr(head, '_hua_lam', 'scaled')
@@ -1015,10 +1192,20 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                 raise ValueError('objDesc needs the neck outputs: the head passes them on as _feats')
             thr = kwargs.get('score_thr')
             thr = 0.3 if thr is None else thr
-            unc, obj_cand = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation], kwargs.get('unc_measure') or 'entropy',
-                                            kwargs.get('unc_aggregate') or 'sum', thr, want_cand=True, class_w=_class_weight(head, cand, kwargs))
+            if kwargs.get('objUnc'):
+                # ENMS / DivProto (apis/test.py single_gpu_enms): the same launches, the score kernel also hands out its per-object
+                # values, and one compaction launch puts them into the descriptors' slots
+                unc, obj_out, _, obj_cand = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation],
+                                                            kwargs.get('unc_measure') or 'entropy', kwargs.get('unc_aggregate') or 'sum', thr,
+                                                            want_objects=True, want_cand=True, class_w=_class_weight(head, cand, kwargs))
+            else:
+                unc, obj_cand = det_uncertainty(cand, dets, labels, num, ACTIVATION_LAYOUT[head.last_activation],
+                                                kwargs.get('unc_measure') or 'entropy', kwargs.get('unc_aggregate') or 'sum', thr, want_cand=True,
+                                                class_w=_class_weight(head, cand, kwargs))
             desc = object_descriptors(feats, cand, dets, labels, num, obj_cand, list(na), int(kwargs['objDesc']), thr,
                                       channels=getattr(head, 'in_channels', None))
+            if kwargs.get('objUnc'):
+                return (dets, labels, num, unc) + desc + (object_measure(obj_out, dets, num, obj_cand, int(kwargs['objDesc']), thr),)
             return (dets, labels, num, unc) + desc
         return dets, labels, num
     if isUnc and not kwargs.get('isEval') and uPool in POSTERIOR_POOLS:

@@ -981,6 +981,52 @@ int aod_det_consistency(const float* dets, const int64_t* labels, const int32_t*
                         const float* ext, int B, int max_num, int W, int layout, int mode, int aggregate, float score_thr, int same_class,
                         float* unc, float* obj_out, float* iou_out, float* js_out, int32_t* match_out, aod_stream_t stream);
 
+/* ------------------------------------------------------------------ ENMS + DivProto acquisition (csrc/divproto.hip): entropy summed over
+ * the objects that survive a feature-similarity NMS, then a progressive pick that rejects images whose class prototypes repeat the picks so
+ * far and favours the classes the picks hold least (Wu, Chen, Huang, "Entropy-based Active Learning for Object Detection with Progressive
+ * Diversity Constraint", CVPR 2022).  No reference call site; the semantics are fixed in DESIGN 3s.
+ * <a, b> is one fp32 product form everywhere: 16 lanes per product, lane q owns the channels 4q + 64m (+0..3) in ascending m, four running
+ * sums (separate multiply and add), ((s0 + s1) + (s2 + s3)), an xor butterfly over the 16 lanes: bit-symmetric, a function of the two rows
+ * and C alone.
+ *   aod_object_measure: h [B][max_obj] fp32, slot-aligned with aod_object_descriptors' feat / cls / w: obj_out [B][max_num] (the per-object
+ *     measure of aod_det_uncertainty*) at the detection rows j < num[b] with dets[b][j][4] > score_thr (strict) -- a row whose
+ *     obj_cand[b][j] < 0 (nullable; expected never) takes no slot --, the first max_obj in row order; 0 behind them.
+ *   aod_enms_prototypes: feat [B][max_obj][C] fp32 (16-B aligned), cls, w, h [B][max_obj], cnt [B] (rows >= cnt[b] are never read);
+ *     1 <= max_obj <= 64, C % 8 == 0, 8 <= C <= 256.  One workgroup per image, rows resident in LDS.
+ *       ENMS: all objects alive; repeat: k* = the alive object with the largest h (lowest index on a tie), E += h_k* (fp32, pick order),
+ *         k* and every alive j with cls_j == cls_k* and <f_j, f_k*> > t_enms (strict) die.  enms [B] = E, kept [B] = picks,
+ *         pick [B][max_obj] int32 (nullable) = the picked slots in pick order, -1 behind them.
+ *       prototypes: for every class among ALL the image's objects, ascending: v = sum over its objects in ascending k of
+ *         (h_k + 2^-10) * f_k, p = v / sqrt(sum v^2) (zeros when the sum is 0), conf = max w_k.  proto [B][max_obj][C] (16-B aligned),
+ *         pcls [B][max_obj] (-1 pad), pconf [B][max_obj] (0 pad), pcnt [B].
+ *       A threshold >= 1 switches its check off (t_enms: nothing is suppressed; t_intra below: no image is redundant): a cosine cannot
+ *       exceed 1, the rounded product of a unit row with itself can.
+ *     An image's outputs are a function of its rows alone: the same bits alone, in any batch, eager or replayed.
+ *   aod_divproto_select: the progressive pick over order [M] int64 (DEVICE; distinct indices into the pool tensors proto [N][max_obj][C],
+ *     pcls, pconf [N][max_obj], pcnt [N], in sweep order).  State: S empty, n_c = 0, free_used = 0.  Per position, until `budget` images
+ *     are accepted:  m = min over the image's classes c of (max over the entries of c's list of <p_I,c, p_J,c>; 0 for an empty list);
+ *     m > t_intra (strict) and at least one class: redundant.  Otherwise, class_balance != 0: class c is minor iff fewer than n_minor
+ *     classes c' have n_c' < n_c or (n_c' == n_c and c' < c); the image serves iff it has a minor class with conf > t_inter and
+ *     n_c < quota: accepted (stage 1); else free_used < n_free: accepted (stage 2), ++free_used; else deferred.  class_balance == 0:
+ *     accepted (stage 1).  Accept: picks [t] = image, every class joins its list, ++n_c for the classes with conf > t_inter.  A sweep
+ *     that ends short is filled with the deferred positions in sweep order, then the redundant ones (stage 3).  picks [budget] int64,
+ *     stage [budget] int32.  A slot whose class lies outside [0, n_cls) is ignored.  1 <= n_cls <= 128, 1 <= budget <= M <= 2^31 - 1,
+ *     1 <= n_minor <= n_cls, 1 <= quota <= budget, 0 <= n_free <= budget.  ws: aod_divproto_ws_len(M, n_cls, budget) bytes, 8-B
+ *     aligned.  An init launch, ceil(M / chunk) launches of ONE workgroup (chunk = 0: aod_divproto_chunk() = 64 positions; a launch
+ *     that finds the budget met exits at once), one fill launch; all state in ws, so the result does not depend on chunk.  No atomics,
+ *     no cross-workgroup wait, no host sync. */
+int aod_object_measure(const float* obj_out, const float* dets, const int32_t* num, const int32_t* obj_cand, int B, int max_num, int max_obj,
+                       float score_thr, float* h, aod_stream_t stream);
+int aod_enms_prototypes(const float* feat, const int32_t* cls, const float* w, const float* h, const int32_t* cnt, int B, int max_obj, int C,
+                        float t_enms, float* enms, int32_t* kept, float* proto, int32_t* pcls, float* pconf, int32_t* pcnt, int32_t* pick,
+                        aod_stream_t stream);
+int aod_divproto_chunk(void);
+size_t aod_divproto_ws_len(int64_t M, int n_cls, int64_t budget);
+int aod_divproto_select(const int64_t* order, int64_t M, int64_t N, const float* proto, const int32_t* pcls, const float* pconf,
+                        const int32_t* pcnt, int max_obj, int C, int n_cls, int64_t budget, float t_intra, float t_inter, int n_minor,
+                        int64_t quota, int64_t n_free, int class_balance, int chunk, int64_t* picks, int32_t* stage, void* ws,
+                        aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

@@ -66,7 +66,24 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         'the summed posterior entropy, then k-center greedy under the category-conditioned matching distance between '
                         'their objects; RetinaNet detectors, zeroRate off) '
                         '| PPAL (CCMS with its first stage ranked by the difficulty-calibrated entropy: every detection times the weight of its '
-                        "class, from the class-difficulty EMA the head keeps while it trains; switches --class-difficulty on, zeroRate off)")
+                        "class, from the class-difficulty EMA the head keeps while it trains; switches --class-difficulty on, zeroRate off) "
+                        '| ENMS (entropy-NMS uncertainty, Wu et al., CVPR 2022: the posterior entropy summed over the objects that survive an '
+                        'NMS by feature similarity, --enms-thr; ordinary scores; RetinaNet detectors) '
+                        '| DivProto (ENMS + the progressive diversity pick of the same paper: sweep the images by ENMS score, pass over those '
+                        'whose class prototypes repeat a pick, --intra-thr, and give the share --minority-beta of the budget to images that '
+                        'bring one of the --minority-alpha least-held classes with a confidence above --inter-thr; RetinaNet detectors, '
+                        'zeroRate off)')
+    p.add_argument('--enms-thr', type=float, default=0.5,
+                   help='ENMS / DivProto pools: an object is dropped when its feature cosine to a picked object of its class exceeds this (default: 0.5)')
+    p.add_argument('--intra-thr', type=float, default=0.7,
+                   help='DivProto pool: an image is redundant when every one of its class prototypes has a cosine above this to a picked one (default: 0.7)')
+    p.add_argument('--inter-thr', type=float, default=0.3,
+                   help='DivProto pool: a class counts as present in an image when its largest detection score exceeds this (default: 0.3)')
+    p.add_argument('--minority-alpha', type=float, default=0.5,
+                   help='DivProto pool: the share of the classes, the least-held first, that count as minority classes, in (0, 1] (default: 0.5)')
+    p.add_argument('--minority-beta', type=float, default=0.75,
+                   help='DivProto pool: the share of the budget reserved for images that bring a minority class, in (0, 1] (default: 0.75)')
+    p.add_argument('--no-class-balance', action='store_true', help='DivProto pool: switch the minority-class stage off (intra-class check only)')
     p.add_argument('--class-difficulty', action='store_true',
                    help="track PPAL's per-class difficulty EMA while training (config key model.bbox_head.class_difficulty = dict(xi=0.6, "
                         'momentum=0.99, alpha=0.3, beta=0.2)); the Entropy / Margin / LeastConf / CCMS pools then weight every detection by its '
@@ -79,7 +96,8 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--candidate-factor', type=float, default=4.0,
                    help='CCMS pool: the candidate set holds ceil(factor x budget) of the most uncertain unlabelled images (default: 4)')
     p.add_argument('--max-objects', type=int, default=32,
-                   help='CCMS pool: objects described per image, the first K detections above --hua-score-thr (default: 32, at most 64)')
+                   help='CCMS / ENMS / DivProto pools: objects described per image, the first K detections above --hua-score-thr (default: 32, '
+                        'at most 64)')
     p.add_argument('--noise-levels', default='8,16,24,32,40,48',
                    help='noise strengths of the LocStability pools: up to 16 comma-separated standard deviations in 0..255 pixel units '
                         '(default: 8,16,24,32,40,48)')
@@ -137,6 +155,12 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
         consistency_views(args.consistency_view_names, '--consistency-views')
     except ValueError as e:
         p.error(str(e))
+    for flag, v in (('--minority-alpha', args.minority_alpha), ('--minority-beta', args.minority_beta)):
+        if not 0 < v <= 1:
+            p.error(f'{flag}: a share in (0, 1] is needed, got {v}')
+    for flag, v in (('--enms-thr', args.enms_thr), ('--intra-thr', args.intra_thr), ('--inter-thr', args.inter_thr)):
+        if v != v:
+            p.error(f'{flag} is NaN')
     if args.consistency_mode not in CONSISTENCY_MODES:
         p.error(f"--consistency-mode: {args.consistency_mode!r} is none of 'both', 'box', 'cls'")
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
@@ -320,10 +344,17 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             # X_S_size images, so the zero-score share of update_X_L is switched off for it; every other pool keeps its kwargs
             # CCMS (uncertainty pre-selection, then k-center greedy under the object-matching distance) is handled like them
             # PPAL is CCMS with the class-weighted first stage
-            coreset = cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS' or cfg.uncertainty_pool == 'PPAL'
+            # DivProto (sweep by ENMS score, progressive prototype pick) likewise; ENMS alone is an ordinary score
+            coreset = (cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS' or cfg.uncertainty_pool == 'PPAL'
+                       or cfg.uncertainty_pool == 'DivProto')
             pool_kw = dict(X_L=X_L) if coreset else {}
             if cfg.uncertainty_pool in ('CCMS', 'PPAL'):
                 pool_kw.update(candidate_factor=args.candidate_factor, max_obj=args.max_objects)
+            if cfg.uncertainty_pool in ('ENMS', 'DivProto'):
+                pool_kw.update(max_obj=args.max_objects, t_enms=args.enms_thr)
+            if cfg.uncertainty_pool == 'DivProto':
+                pool_kw.update(t_intra=args.intra_thr, t_inter=args.inter_thr, alpha=args.minority_alpha, beta=args.minority_beta,
+                               class_balance=not args.no_class_balance)
             if cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf'):    # the posterior pools: ordinary scores, zeroRate stays on
                 pool_kw = dict(unc_aggregate=args.unc_aggregate)
             if args.class_difficulty and cfg.uncertainty_pool in ('Entropy', 'Margin', 'LeastConf', 'CCMS'):
