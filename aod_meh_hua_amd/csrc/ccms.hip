@@ -31,7 +31,7 @@
 #include <limits.h>
 #include <math.h>
 #include "../../include/aod_hip.h"
-#include "common.h"
+#include "row_layout.h"
 
 #define OD_MAX_SEG 8
 #define OD_MAX_DET 1024
@@ -55,18 +55,6 @@ struct OdSegs {
   int na[OD_MAX_SEG];                  // anchors per cell
   int nseg;
 };
-
-__device__ __forceinline__ void od_load(const bf16_t* __restrict__ p, int x3, float (&v)[8]) {
-  const bf16x8 h = *reinterpret_cast<const bf16x8*>(p);
-  if (x3) {
-    const bf16x8 l = *reinterpret_cast<const bf16x8*>(p + 32);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (float)l[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
-  }
-}
 
 __global__ __launch_bounds__(256) void object_descriptors_kernel(const OdSegs s, int C, int x3, const int* __restrict__ cand_anchor, int n,
                                                                  const float* __restrict__ dets, const long long* __restrict__ labels,
@@ -138,8 +126,8 @@ __global__ __launch_bounds__(256) void object_descriptors_kernel(const OdSegs s,
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[m][u] = 0.f;
       if (o * 8 < C) {
-        const int col = x3 ? ((o >> 2) << 6) + ((o & 3) << 3) : o * 8;
-        od_load(p + col, x3, v[m]);
+        const int col = row_col(x3, o);
+        row_load(p + col, x3, v[m]);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) ss += v[m][u] * v[m][u];

@@ -9,7 +9,7 @@
 // bits alone and in any batch.  16-B loads, no atomics.
 #include <hip/hip_runtime.h>
 #include "../../include/aod_hip.h"
-#include "common.h"
+#include "row_layout.h"
 
 #define PD_MAX_SEG 8
 
@@ -18,18 +18,6 @@ struct PdSegs {
   int hw[PD_MAX_SEG];                // rows per image
   int nseg;
 };
-
-__device__ __forceinline__ void pd_load(const bf16_t* __restrict__ p, int x3, float (&v)[8]) {
-  const bf16x8 h = *reinterpret_cast<const bf16x8*>(p);
-  if (x3) {
-    const bf16x8 l = *reinterpret_cast<const bf16x8*>(p + 32);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (float)l[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
-  }
-}
 
 __global__ __launch_bounds__(256) void pool_descriptor_kernel(const bf16_t* __restrict__ base, const PdSegs s, int C, int x3, int groups,
                                                               float* __restrict__ out, long long out_stride) {
@@ -42,7 +30,7 @@ __global__ __launch_bounds__(256) void pool_descriptor_kernel(const bf16_t* __re
   const bool live = o * 8 < C;                                   // (C % 8 == 0: an octet is all channels or all pad; pad is never read)
   const int hw = s.hw[l];
   const long long pitch = x3 ? 2ll * ((C + 31) / 32 * 32) : (long long)C;
-  const int col = x3 ? ((o >> 2) << 6) + ((o & 3) << 3) : o * 8;
+  const int col = row_col(x3, o);
   const bf16_t* p = base + (s.row0[l] + (long long)b * hw) * pitch + col;
   float acc[8];
 #pragma unroll
@@ -51,16 +39,16 @@ __global__ __launch_bounds__(256) void pool_descriptor_kernel(const bf16_t* __re
     int m = r;
     for (; m + 96 < hw; m += 128) {                              // four rows in flight, added in row order
       float v0[8], v1[8], v2[8], v3[8];
-      pd_load(p + (long long)m * pitch, x3, v0);
-      pd_load(p + (long long)(m + 32) * pitch, x3, v1);
-      pd_load(p + (long long)(m + 64) * pitch, x3, v2);
-      pd_load(p + (long long)(m + 96) * pitch, x3, v3);
+      row_load(p + (long long)m * pitch, x3, v0);
+      row_load(p + (long long)(m + 32) * pitch, x3, v1);
+      row_load(p + (long long)(m + 64) * pitch, x3, v2);
+      row_load(p + (long long)(m + 96) * pitch, x3, v3);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = (((acc[j] + v0[j]) + v1[j]) + v2[j]) + v3[j];
     }
     for (; m < hw; m += 32) {
       float v[8];
-      pd_load(p + (long long)m * pitch, x3, v);
+      row_load(p + (long long)m * pitch, x3, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] += v[j];
     }

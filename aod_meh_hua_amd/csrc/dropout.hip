@@ -94,8 +94,9 @@ __global__ __launch_bounds__(256) void dropout2d_apply_kernel(bf16_t* __restrict
     }
     bf16_t* px = x + (sg.row0[s] + local) * CP + (X3 ? xoct(p) : 8 * p);
     if (X3) {
-      // xload / multiply / xstore of x3_ops.hip on one octet.  A factor of exactly 1 keeps the element's (head, tail) bits: re-splitting
-      // h + l is not idempotent (a tail that rounded up to half an ulp of its head makes h + l a bf16 tie, which may pick the other head)
+      // XRows::load / multiply / XRows::store of row_layout.h on one octet, by hand.  A factor of exactly 1 keeps the element's (head, tail)
+      // bits: re-splitting h + l is not idempotent (a tail that rounded up to half an ulp of its head makes h + l a bf16 tie, which may pick
+      // the other head)
       bf16x8 h = *reinterpret_cast<const bf16x8*>(px), l = *reinterpret_cast<const bf16x8*>(px + 32);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {

@@ -1,5 +1,6 @@
-// HBM-bound elementwise / reduction kernels around the conv stack (NHWC bf16, 16-B lanes).
-#include "tile_prims.h"
+// HBM-bound elementwise / reduction kernels around the conv stack (NHWC bf16, 16-B lanes), and the X-row entries of the FPN upsample-add,
+// whose body serves both row layouts (row_layout.h).
+#include "row_layout.h"
 
 // ---------------------------------------------------------------- NCHW fp32 -> NHWC bf16 (padded C)
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int B, int C, int HW, int Cpad) {
@@ -59,62 +60,30 @@ extern "C" int aod_nchw_f32_to_s2d_bf16(const float* src, void* dst, int B, int 
   return 0;
 }
 
-// ---------------------------------------------------------------- maxpool 3x3 s2 p1
-__global__ void maxpool_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int B, int H, int W, int C8, int OH, int OW) {
-  const long long n = (long long)B * OH * OW * C8;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = i % C8; long long r = i / C8;
-    const int ox = r % OW; r /= OW;
-    const int oy = r % OH; const int b = r / OH;
-    float m[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
-    for (int dy = 0; dy < 3; ++dy) {
-      const int y = oy * 2 - 1 + dy;
-      if ((unsigned)y >= (unsigned)H) continue;
-      for (int dx = 0; dx < 3; ++dx) {
-        const int x = ox * 2 - 1 + dx;
-        if ((unsigned)x >= (unsigned)W) continue;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + (((long long)b * H + y) * W + x) * C8 * 8 + c * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], (float)v[j]);
-      }
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)m[j];
-    *reinterpret_cast<bf16x8*>(dst + i * 8) = o;
-  }
-}
-extern "C" int aod_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
-  AOD_CHECK_ARG(src && dst && C % 8 == 0, "maxpool: C must be a multiple of 8");
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for<2048>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)src, (bf16_t*)dst, B, H, W, C / 8, OH, OW);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------- FPN nearest-upsample add (F.interpolate(size=..., 'nearest'))
+// ---------------------------------------------------------------- FPN nearest-upsample add (F.interpolate(size=..., 'nearest'); fpn.py:163-172)
+// One body for bf16 NHWC rows and X rows (L = Bf16Rows / XRows, row_layout.h); a work item is one octet of a destination pixel.
 // src index = floor(dst * h / H) (torch nearest); exact 2x when H == 2h.
 // (`lat` = the lateral the upsampled top is added to; it may alias `dst` -- element i is read before it is written by the same thread)
-__global__ void upsample_add_kernel(const bf16_t* __restrict__ src, const bf16_t* lat, bf16_t* dst, int B, int h, int w, int C8, int H, int W) {
-  const long long n = (long long)B * H * W * C8;
+template <class L>
+__global__ void upsample_add_kernel(const bf16_t* __restrict__ src, const bf16_t* lat, bf16_t* dst, int B, int h, int w, int Q, int H, int W) {
+  const long long n = (long long)B * H * W * Q;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = i % C8; long long r = i / C8;
+    const int q = i % Q; long long r = i / Q;
+    const long long pix = r;
     const int x = r % W; r /= W;
     const int y = r % H; const int b = r / H;
     const int sy = min((int)(((long long)y * h) / H), h - 1), sx = min((int)(((long long)x * w) / W), w - 1);
-    const bf16x8 s = *reinterpret_cast<const bf16x8*>(src + ((((long long)b * h + sy) * w + sx) * C8 + c) * 8);
-    bf16x8 d = *reinterpret_cast<const bf16x8*>(lat + i * 8);
+    float s[8], d[8];
+    L::load(src + L::at(((long long)b * h + sy) * w + sx, q, Q), s);
+    L::load(lat + L::at(pix, q, Q), d);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] = (bf16_t)((float)d[j] + (float)s[j]);
-    *reinterpret_cast<bf16x8*>(dst + i * 8) = d;
+    for (int j = 0; j < 8; ++j) d[j] += s[j];
+    L::store(dst + L::at(pix, q, Q), d);
   }
 }
 extern "C" int aod_upsample2x_add(const void* src, void* dst, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C % 8 == 0, "upsample_add: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_kernel<Bf16Rows>, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, (const bf16_t*)dst, (bf16_t*)dst, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -123,41 +92,50 @@ extern "C" int aod_upsample2x_add(const void* src, void* dst, int B, int h, int 
 // lateral conv's output): one pass less over the level
 extern "C" int aod_upsample2x_add_to(const void* top, const void* lateral, void* out, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(top && lateral && out && C % 8 == 0, "upsample_add_to: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample_add_kernel<Bf16Rows>, dim3(grid_for<2048>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)top, (const bf16_t*)lateral, (bf16_t*)out, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
 }
+// ... on X rows (C = the X-layout width: 16 bf16 columns per octet)
+extern "C" int aod_x3_upsample2x_add_to(const void* top, const void* lateral, void* out, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
+  AOD_CHECK_ARG(top && lateral && out && C % 64 == 0, "x3_upsample_add_to: the X-layout width must be a multiple of 64");
+  hipLaunchKernelGGL(upsample_add_kernel<XRows>, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)top,
+                     (const bf16_t*)lateral, (bf16_t*)out, B, h, w, C / 16, H, W);
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
 // adjoint: g_src[b,sy,sx,c] (+)= sum over dst pixels mapping to (sy,sx) of g_dst   (ACC: add to what g_src holds; else overwrite it)
-template <bool ACC>
-__global__ void upsample_add_bwd_kernel(const bf16_t* __restrict__ gd, bf16_t* __restrict__ gs, int B, int h, int w, int C8, int H, int W) {
-  const long long n = (long long)B * h * w * C8;
+template <class L, bool ACC>
+__global__ void upsample_add_bwd_kernel(const bf16_t* __restrict__ gd, bf16_t* __restrict__ gs, int B, int h, int w, int Q, int H, int W) {
+  const long long n = (long long)B * h * w * Q;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = i % C8; long long r = i / C8;
+    const int q = i % Q; long long r = i / Q;
+    const long long pix = r;
     const int sx = r % w; r /= w;
     const int sy = r % h; const int b = r / h;
     // dst rows y with floor(y*h/H) == sy  <=>  y in [ceil(sy*H/h), ceil((sy+1)*H/h))
     const int y0 = (int)(((long long)sy * H + h - 1) / h), y1 = min(H, (int)(((long long)(sy + 1) * H + h - 1) / h));
     const int x0 = (int)(((long long)sx * W + w - 1) / w), x1 = min(W, (int)(((long long)(sx + 1) * W + w - 1) / w));
     float a[8];
-    bf16x8 cur;
-    if (ACC) cur = *reinterpret_cast<bf16x8*>(gs + i * 8);
+    if (ACC) L::load(gs + L::at(pix, q, Q), a);
+    else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = ACC ? (float)cur[j] : 0.f;
+      for (int j = 0; j < 8; ++j) a[j] = 0.f;
+    }
     for (int y = y0; y < y1; ++y)
       for (int x = x0; x < x1; ++x) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(gd + ((((long long)b * H + y) * W + x) * C8 + c) * 8);
+        float v[8];
+        L::load(gd + L::at(((long long)b * H + y) * W + x, q, Q), v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] += (float)v[j];
+        for (int j = 0; j < 8; ++j) a[j] += v[j];
       }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) cur[j] = (bf16_t)a[j];
-    *reinterpret_cast<bf16x8*>(gs + i * 8) = cur;
+    L::store(gs + L::at(pix, q, Q), a);
   }
 }
 extern "C" int aod_upsample2x_add_bwd(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(g_dst && g_src && C % 8 == 0, "upsample_add_bwd: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_bwd_kernel<true>, dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((upsample_add_bwd_kernel<Bf16Rows, true>), dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)g_dst, (bf16_t*)g_src, B, h, w, C / 8, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
@@ -165,8 +143,16 @@ extern "C" int aod_upsample2x_add_bwd(const void* g_dst, void* g_src, int B, int
 // ... writing g_src instead of accumulating into it (no zero fill of the destination needed)
 extern "C" int aod_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(g_dst && g_src && C % 8 == 0, "upsample_add_bwd_set: C must be a multiple of 8");
-  hipLaunchKernelGGL(upsample_add_bwd_kernel<false>, dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((upsample_add_bwd_kernel<Bf16Rows, false>), dim3(grid_for<2048>((long long)B * h * w * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)g_dst, (bf16_t*)g_src, B, h, w, C / 8, H, W);
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+// ... on X rows (only the "set" form is exported)
+extern "C" int aod_x3_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
+  AOD_CHECK_ARG(g_dst && g_src && C % 64 == 0, "x3_upsample_add_bwd_set: the X-layout width must be a multiple of 64");
+  hipLaunchKernelGGL((upsample_add_bwd_kernel<XRows, false>), dim3(grid_for<2048>((long long)B * h * w * (C / 16))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)g_dst, (bf16_t*)g_src, B, h, w, C / 16, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
 }

@@ -1,14 +1,23 @@
-// Kernels specific to the SSD300-VGG16 + MEH variant (BASELINE config 0; reference: backbones/ssd_vgg.py,
-// necks/ssd_neck.py:105-128 L2Norm, dense_heads/My_L_ssd_head.py:182-224 losses).  Small tensors (300x300 inputs):
-// simple one-thread-per-output kernels; NHWC bf16 activations, fp32 logits.
-#include "tile_prims.h"
+// Max-pool for both row layouts, and the kernels specific to the SSD300-VGG16 + MEH variant (BASELINE config 0; reference:
+// backbones/ssd_vgg.py, necks/ssd_neck.py:105-128 L2Norm, dense_heads/My_L_ssd_head.py:182-224 losses).  Small tensors (300x300 inputs):
+// simple one-thread-per-output kernels; NHWC bf16 activations, fp32 logits.  The max-pool body serves bf16 and X rows and, with its window
+// fixed at compile time, the ResNet stem's 3x3 / s2 pool: all six max-pool entries sit here, next to it.
+#include "row_layout.h"
 
-// ---------------------------------------------------------------- generic max-pool (k x k, stride s, pad p), NHWC bf16
-// torch semantics: windows clipped to the image, -inf padding, first maximum in (dy, dx) scan order wins the gradient.
-__global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int B, int H, int W, int C8, int OH, int OW, int k, int s, int p) {
-  const long long n = (long long)B * OH * OW * C8;
+// ---------------------------------------------------------------- max-pool (k x k, stride s, pad p)
+// One body for bf16 NHWC rows and X rows (L = Bf16Rows / XRows, row_layout.h); a work item is one octet of an output pixel.
+// torch semantics (incl. ceil_mode output sizes computed by the caller): windows clipped to the image, -inf padding, first maximum in
+// (dy, dx) scan order wins the gradient.  The window travels as the last kernel argument: RunWin holds it, FixedWin is empty and makes
+// k, s, p compile-time constants (the loops unroll, and the kernel reads no argument it does not use).
+struct RunWin { int k, s, p; };
+template <int K, int S, int P> struct FixedWin { static constexpr int k = K, s = S, p = P; };
+template <class L, class Win>
+__global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int B, int H, int W, int Q, int OH, int OW, const Win win) {
+  const int k = win.k, s = win.s, p = win.p;
+  const long long n = (long long)B * OH * OW * Q;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = i % C8; long long r = i / C8;
+    const int q = i % Q; long long r = i / Q;
+    const long long pix = r;
     const int ox = r % OW; r /= OW;
     const int oy = r % OH; const int b = r / OH;
     float m[8];
@@ -20,27 +29,29 @@ __global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
       for (int dx = 0; dx < k; ++dx) {
         const int xx = ox * s - p + dx;
         if ((unsigned)xx >= (unsigned)W) continue;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + ((((long long)b * H + yy) * W + xx) * C8 + c) * 8);
+        // (pixel step, then octet step: the loads of a window wait for one another, and this spelling costs each one address
+        // multiply-add where x + at(pixel, q, Q) costs a multiply-add and a 64-bit shift-add)
+        float v[8];
+        L::load(x + L::at(((long long)b * H + yy) * W + xx, 0, Q) + L::col(q), v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], (float)v[j]);
+        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], v[j]);
       }
     }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)m[j];
-    *reinterpret_cast<bf16x8*>(y + i * 8) = o;
+    L::store(y + L::at(pix, q, Q), m);
   }
 }
-// backward as a gather: input pixel (yy, xx) receives g[oy, ox] from every window whose FIRST maximum it is
-__global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g, bf16_t* __restrict__ gx, int B, int H, int W, int C8,
+// backward as a gather: input pixel (yy, xx) receives g[oy, ox] from every window whose FIRST maximum (scan order) it is
+template <class L>
+__global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g, bf16_t* __restrict__ gx, int B, int H, int W, int Q,
                                    int OH, int OW, int k, int s, int p) {
-  const long long n = (long long)B * H * W * C8;
+  const long long n = (long long)B * H * W * Q;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = i % C8; long long r = i / C8;
+    const int q = i % Q; long long r = i / Q;
+    const long long pix = r;
     const int xx = r % W; r /= W;
     const int yy = r % H; const int b = r / H;
-    const bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + i * 8);
-    float acc[8];
+    float me[8], acc[8];
+    L::load(x + L::at(pix, q, Q), me);
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;
     // windows containing (yy, xx): oy in [ceil((yy + p - k + 1)/s), floor((yy + p)/s)]
@@ -59,37 +70,67 @@ __global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* _
           for (int dx = 0; dx < k; ++dx) {
             const int x2 = ox * s - p + dx;
             if ((unsigned)x2 >= (unsigned)W || (y2 == yy && x2 == xx)) continue;
-            const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + ((((long long)b * H + y2) * W + x2) * C8 + c) * 8);
+            float v[8];
+            L::load(x + L::at(((long long)b * H + y2) * W + x2, q, Q), v);
             const bool before = (y2 < yy) || (y2 == yy && x2 < xx);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float a = (float)v[j], me = (float)xv[j];
-              if (a > me || (before && a == me)) win[j] = false;
-            }
+            for (int j = 0; j < 8; ++j)
+              if (v[j] > me[j] || (before && v[j] == me[j])) win[j] = false;
           }
         }
-        const bf16x8 gv = *reinterpret_cast<const bf16x8*>(g + ((((long long)b * OH + oy) * OW + ox) * C8 + c) * 8);
+        float gv[8];
+        L::load(g + L::at(((long long)b * OH + oy) * OW + ox, q, Q), gv);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) if (win[j]) acc[j] += (float)gv[j];
+        for (int j = 0; j < 8; ++j) if (win[j]) acc[j] += gv[j];
       }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)acc[j];
-    *reinterpret_cast<bf16x8*>(gx + i * 8) = o;
+    L::store(gx + L::at(pix, q, Q), acc);
   }
 }
+// the ResNet stem's pool (resnet.py:610): 3x3 / s2 / p1 with the window known at compile time
+extern "C" int aod_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
+  AOD_CHECK_ARG(src && dst && C % 8 == 0, "maxpool: C must be a multiple of 8");
+  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
+  hipLaunchKernelGGL((maxpool_fwd_kernel<Bf16Rows, FixedWin<3, 2, 1>>), dim3(grid_for<2048>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)src, (bf16_t*)dst, B, H, W, C / 8, OH, OW, FixedWin<3, 2, 1>());
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int aod_x3_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
+  AOD_CHECK_ARG(src && dst && C % 64 == 0, "x3_maxpool: the X-layout width must be a multiple of 64");
+  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1, Q = C / 16;
+  hipLaunchKernelGGL((maxpool_fwd_kernel<XRows, FixedWin<3, 2, 1>>), dim3(grid_for<2048>((long long)B * OH * OW * Q)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)src, (bf16_t*)dst, B, H, W, Q, OH, OW, FixedWin<3, 2, 1>());
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+// the generic entries (X rows: C = the X-layout width, 16 bf16 columns per octet)
 extern "C" int aod_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int s, int p, aod_stream_t stream) {
   AOD_CHECK_ARG(x && y && C % 8 == 0 && k >= 1 && s >= 1, "maxpool_fwd: bad args");
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for<4096>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)y, B, H, W, C / 8, OH, OW, k, s, p);
+  hipLaunchKernelGGL((maxpool_fwd_kernel<Bf16Rows, RunWin>), dim3(grid_for<4096>((long long)B * OH * OW * (C / 8))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)y, B, H, W, C / 8, OH, OW, RunWin{k, s, p});
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int aod_x3_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int s, int p, aod_stream_t stream) {
+  AOD_CHECK_ARG(x && y && C % 64 == 0 && k >= 1 && s >= 1, "x3_maxpool_fwd: bad args");
+  hipLaunchKernelGGL((maxpool_fwd_kernel<XRows, RunWin>), dim3(grid_for<2048>((long long)B * OH * OW * (C / 16))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)y, B, H, W, C / 16, OH, OW, RunWin{k, s, p});
   AOD_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int aod_maxpool_bwd(const void* x, const void* g, void* gx, int B, int H, int W, int C, int OH, int OW, int k, int s, int p,
                                aod_stream_t stream) {
   AOD_CHECK_ARG(x && g && gx && C % 8 == 0, "maxpool_bwd: bad args");
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for<4096>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+  hipLaunchKernelGGL(maxpool_bwd_kernel<Bf16Rows>, dim3(grid_for<4096>((long long)B * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (const bf16_t*)g, (bf16_t*)gx, B, H, W, C / 8, OH, OW, k, s, p);
+  AOD_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int aod_x3_maxpool_bwd(const void* x, const void* g, void* gx, int B, int H, int W, int C, int OH, int OW, int k, int s, int p,
+                                  aod_stream_t stream) {
+  AOD_CHECK_ARG(x && g && gx && C % 64 == 0, "x3_maxpool_bwd: bad args");
+  hipLaunchKernelGGL(maxpool_bwd_kernel<XRows>, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                     (const bf16_t*)g, (bf16_t*)gx, B, H, W, C / 16, OH, OW, k, s, p);
   AOD_LAUNCH_CHECK();
   return 0;
 }

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const float v = (float)ch + (float)(bf16_t)(m[k] - (float)ch);
         h[k] = (bf16_t)v; l[k] = (bf16_t)(v - (float)h[k]);
       }
-      bf16_t* dst = p.y + (((long long)b * p.H4 + py) * p.W4 + px) * 128 + ((c8 >> 2) << 6) + ((c8 & 3) << 3);
+      bf16_t* dst = p.y + (((long long)b * p.H4 + py) * p.W4 + px) * 128 + xoct(c8);
       *reinterpret_cast<bf16x8*>(dst) = h;
       *reinterpret_cast<bf16x8*>(dst + 32) = l;
     }

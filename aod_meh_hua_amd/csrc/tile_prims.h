@@ -86,7 +86,7 @@ __device__ __forceinline__ float sum_lr(float v) {
   return v;
 }
 
-// ---------------------------------------------------------------- X layout (x3_ops.hip)
+// ---------------------------------------------------------------- X layout (row_layout.h)
 // physical column (elements) of logical octet q: 8 logical channels = a 16-B head piece and the 16-B tail piece 64 B behind it.  The row
 // kernels, the dropout pass and the conv epilogues all address X rows through this map.
 __device__ __forceinline__ int xoct(int q) { return ((q >> 2) << 6) + ((q & 3) << 3); }

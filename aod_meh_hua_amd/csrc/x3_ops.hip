@@ -1,22 +1,10 @@
-// Row kernels of the REFERENCE-PRECISION mode (aod_conv_desc_t.x3, conv.hip "X3"): the elementwise / reduction passes around the conv stack on
-// X-layout tensors.  An fp32 value v travels as head h = bf16(v) and tail l = bf16(v - h); a tensor of C logical channels is a bf16 row of
-// 2 * ceil32(C) columns [h(0..31) | l(0..31) | h(32..63) | l(32..63) | ...].  Every kernel here re-forms v = h + l in fp32, computes like its
-// bf16 twin in elementwise.hip and writes (h, l) again: nothing in this mode rounds an activation or a gradient to 8 significant bits.
-// Unit of work: one OCTET = 8 consecutive logical channels = a 16-B head piece and the 16-B tail piece 64 B behind it.
-#include "tile_prims.h"
-
-__device__ __forceinline__ void xload(const bf16_t* __restrict__ p, float (&v)[8]) {
-  const bf16x8 h = *reinterpret_cast<const bf16x8*>(p), l = *reinterpret_cast<const bf16x8*>(p + 32);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = (float)h[j] + (float)l[j];
-}
-__device__ __forceinline__ void xstore(bf16_t* __restrict__ p, const float (&v)[8]) {
-  bf16x8 h, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { h[j] = (bf16_t)v[j]; l[j] = (bf16_t)(v[j] - (float)h[j]); }
-  *reinterpret_cast<bf16x8*>(p) = h;
-  *reinterpret_cast<bf16x8*>(p + 32) = l;
-}
+// Row kernels of the REFERENCE-PRECISION mode (aod_conv_desc_t.x3, conv.hip "X3") that have no bf16 twin of the same body: the layout converters,
+// the gradient fan-in add, activation backward, the head-gradient pad / cast and L2Norm on X-layout tensors.  The layout itself -- head and
+// tail pieces, the octet as unit of work, XRows::at / load / store -- is row_layout.h.  Every kernel here re-forms v = h + l in fp32, computes
+// and writes (h, l) again: nothing in this mode rounds an activation or a gradient to 8 significant bits.  The kernels that ARE the same body
+// in both layouts (max-pool, FPN upsample-add and their backward passes) are templates over the layout next to their bf16 entries, in
+// elementwise.hip and ssd_ops.hip.
+#include "row_layout.h"
 
 // ---------------------------------------------------------------- fp32 rows <-> X-layout rows
 __global__ void x3_split_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long long M, int C, int Q) {
@@ -26,7 +14,7 @@ __global__ void x3_split_kernel(const float* __restrict__ src, bf16_t* __restric
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (q * 8 + j < C) ? src[m * C + q * 8 + j] : 0.f;
-    xstore(dst + m * (Q >> 2) * 64 + xoct(q), v);
+    XRows::store(dst + m * XRows::pitch(Q) + xoct(q), v);
   }
 }
 extern "C" int aod_x3_split(const float* src, void* dst, int64_t M, int C, aod_stream_t stream) {
@@ -42,7 +30,7 @@ __global__ void x3_merge_kernel(const bf16_t* __restrict__ src, float* __restric
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int q = (int)(i % Q); const long long m = i / Q;
     float v[8];
-    xload(src + m * (Q >> 2) * 64 + xoct(q), v);
+    XRows::load(src + m * XRows::pitch(Q) + xoct(q), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       if (q * 8 + j < C) dst[m * C + q * 8 + j] = v[j];
@@ -60,12 +48,12 @@ extern "C" int aod_x3_merge(const void* src, float* dst, int64_t M, int C, aod_s
 // ---------------------------------------------------------------- out = a + b (gradient fan-in: a tensor that feeds several consumers)
 __global__ void x3_add_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ o, long long nq) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
-    const long long off = (i >> 2) * 64 + ((i & 3) << 3);
+    const long long off = (i >> 2) * 64 + ((i & 3) << 3);          // xoct over the whole tensor (64-bit octet index: no rows here)
     float x[8], y[8];
-    xload(a + off, x); xload(b + off, y);
+    XRows::load(a + off, x); XRows::load(b + off, y);
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[j] += y[j];
-    xstore(o + off, x);
+    XRows::store(o + off, x);
   }
 }
 extern "C" int aod_x3_add(const void* a, const void* b, void* out, int64_t n, aod_stream_t stream) {
@@ -100,105 +88,13 @@ __global__ void x3_nchw_to_s2d_kernel(const float* __restrict__ src, bf16_t* __r
       float u[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) u[j] = v[q * 8 + j];
-      xstore(dst + i * 64 + q * 8, u);
+      XRows::store(dst + i * 64 + q * 8, u);
     }
   }
 }
 extern "C" int aod_x3_nchw_f32_to_s2d(const float* src, void* dst, int B, int C, int H, int W, aod_stream_t stream) {
   AOD_CHECK_ARG(src && dst && C >= 1 && C <= 4 && H % 2 == 0 && W % 2 == 0, "x3_nchw_to_s2d: C <= 4 and even H, W required (C %d, %d x %d)", C, H, W);
   hipLaunchKernelGGL(x3_nchw_to_s2d_kernel, dim3(grid_for<2048>((long long)B * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, C, H, W);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------- maxpool 3x3 s2 p1 (resnet.py:610)
-__global__ void x3_maxpool_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int B, int H, int W, int Q, int OH, int OW) {
-  const long long n = (long long)B * OH * OW * Q;
-  const int CP = (Q >> 2) * 64;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int q = i % Q; long long r = i / Q;
-    const int ox = r % OW; r /= OW;
-    const int oy = r % OH; const int b = r / OH;
-    float m[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
-    for (int dy = 0; dy < 3; ++dy) {
-      const int y = oy * 2 - 1 + dy;
-      if ((unsigned)y >= (unsigned)H) continue;
-      for (int dx = 0; dx < 3; ++dx) {
-        const int x = ox * 2 - 1 + dx;
-        if ((unsigned)x >= (unsigned)W) continue;
-        float v[8];
-        xload(src + (((long long)b * H + y) * W + x) * CP + xoct(q), v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], v[j]);
-      }
-    }
-    xstore(dst + (i / Q) * CP + xoct(q), m);
-  }
-}
-extern "C" int aod_x3_maxpool3x3s2(const void* src, void* dst, int B, int H, int W, int C, aod_stream_t stream) {
-  AOD_CHECK_ARG(src && dst && C % 64 == 0, "x3_maxpool: the X-layout width must be a multiple of 64");
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1, Q = C / 16;
-  hipLaunchKernelGGL(x3_maxpool_kernel, dim3(grid_for<2048>((long long)B * OH * OW * Q)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst,
-                     B, H, W, Q, OH, OW);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------- FPN nearest-upsample add (fpn.py:163-172) and its adjoint
-__global__ void x3_upsample_add_kernel(const bf16_t* __restrict__ src, const bf16_t* __restrict__ lat, bf16_t* __restrict__ dst, int B, int h, int w,
-                                       int Q, int H, int W) {
-  const long long n = (long long)B * H * W * Q;
-  const int CP = (Q >> 2) * 64;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int q = i % Q; long long r = i / Q;
-    const long long pix = r;
-    const int x = r % W; r /= W;
-    const int y = r % H; const int b = r / H;
-    const int sy = min((int)(((long long)y * h) / H), h - 1), sx = min((int)(((long long)x * w) / W), w - 1);
-    float s[8], d[8];
-    xload(src + (((long long)b * h + sy) * w + sx) * CP + xoct(q), s);
-    xload(lat + pix * CP + xoct(q), d);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] += s[j];
-    xstore(dst + pix * CP + xoct(q), d);
-  }
-}
-extern "C" int aod_x3_upsample2x_add_to(const void* top, const void* lateral, void* out, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
-  AOD_CHECK_ARG(top && lateral && out && C % 64 == 0, "x3_upsample_add_to: the X-layout width must be a multiple of 64");
-  hipLaunchKernelGGL(x3_upsample_add_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)top,
-                     (const bf16_t*)lateral, (bf16_t*)out, B, h, w, C / 16, H, W);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-__global__ void x3_upsample_add_bwd_kernel(const bf16_t* __restrict__ gd, bf16_t* __restrict__ gs, int B, int h, int w, int Q, int H, int W) {
-  const long long n = (long long)B * h * w * Q;
-  const int CP = (Q >> 2) * 64;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int q = i % Q; long long r = i / Q;
-    const long long pix = r;
-    const int sx = r % w; r /= w;
-    const int sy = r % h; const int b = r / h;
-    const int y0 = (int)(((long long)sy * H + h - 1) / h), y1 = min(H, (int)(((long long)(sy + 1) * H + h - 1) / h));
-    const int x0 = (int)(((long long)sx * W + w - 1) / w), x1 = min(W, (int)(((long long)(sx + 1) * W + w - 1) / w));
-    float a[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = 0.f;
-    for (int y = y0; y < y1; ++y)
-      for (int x = x0; x < x1; ++x) {
-        float v[8];
-        xload(gd + (((long long)b * H + y) * W + x) * CP + xoct(q), v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] += v[j];
-      }
-    xstore(gs + pix * CP + xoct(q), a);
-  }
-}
-extern "C" int aod_x3_upsample2x_add_bwd_set(const void* g_dst, void* g_src, int B, int h, int w, int C, int H, int W, aod_stream_t stream) {
-  AOD_CHECK_ARG(g_dst && g_src && C % 64 == 0, "x3_upsample_add_bwd_set: the X-layout width must be a multiple of 64");
-  hipLaunchKernelGGL(x3_upsample_add_bwd_kernel, dim3(grid_for<2048>((long long)B * h * w * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g_dst,
-                     (bf16_t*)g_src, B, h, w, C / 16, H, W);
   AOD_LAUNCH_CHECK();
   return 0;
 }
@@ -210,7 +106,7 @@ __global__ __launch_bounds__(256) void x3_act_bwd_kernel(const bf16_t* __restric
   __shared__ float sb[8][256 + 8];
   const int t = threadIdx.x, cc = t & 31, rl = t >> 5;
   const int q = blockIdx.x * 32 + cc;
-  const int CP = (Q >> 2) * 64;
+  const int CP = XRows::pitch(Q);
   const long long r0 = (long long)blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
   float s[8];
 #pragma unroll
@@ -219,7 +115,7 @@ __global__ __launch_bounds__(256) void x3_act_bwd_kernel(const bf16_t* __restric
     const int col = xoct(q);
     for (long long m = r0 + rl; m < r1; m += 8) {
       float v[8];
-      xload(g + m * CP + col, v);
+      XRows::load(g + m * CP + col, v);
       if (relu) {
         const bf16x8 av = *reinterpret_cast<const bf16x8*>(a + m * CP + col);      // (the head decides the sign)
 #pragma unroll
@@ -227,7 +123,7 @@ __global__ __launch_bounds__(256) void x3_act_bwd_kernel(const bf16_t* __restric
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) s[j] += v[j];
-      if (dz) xstore(dz + m * CP + col, v);
+      if (dz) XRows::store(dz + m * CP + col, v);
     }
   }
 #pragma unroll
@@ -335,7 +231,7 @@ __global__ __launch_bounds__(256) void x3_pad_cast_colsum_v8_kernel(const float*
         for (int j = 0; j < 8; ++j) nz = nz || !(v[j] == 0.f);
         if (nz) map[m >> 6] = 1;
       }
-      xstore(dz + m * 2 * Np + col, v);
+      XRows::store(dz + m * 2 * Np + col, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) s[j] += v[j];
     }
@@ -401,7 +297,7 @@ __global__ void x3_nchw_to_nhwc_kernel(const float* __restrict__ src, bf16_t* __
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { const int c = q * 8 + j; v[j] = c < C ? src[(b * C + c) * HW + px] : 0.f; }
-    xstore(dst + pix * 64 + q * 8, v);
+    XRows::store(dst + pix * 64 + q * 8, v);
   }
 }
 extern "C" int aod_x3_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, aod_stream_t stream) {
@@ -411,102 +307,16 @@ extern "C" int aod_x3_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C
   return 0;
 }
 
-// generic max-pool (k x k, stride s, pad p; torch semantics incl. ceil_mode output sizes computed by the caller) on X rows
-__global__ void x3_maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int B, int H, int W, int Q, int OH, int OW, int k, int s, int p) {
-  const long long n = (long long)B * OH * OW * Q;
-  const int CP = (Q >> 2) * 64;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int q = i % Q; long long r = i / Q;
-    const int ox = r % OW; r /= OW;
-    const int oy = r % OH; const int b = r / OH;
-    float m[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
-    for (int dy = 0; dy < k; ++dy) {
-      const int yy = oy * s - p + dy;
-      if ((unsigned)yy >= (unsigned)H) continue;
-      for (int dx = 0; dx < k; ++dx) {
-        const int xx = ox * s - p + dx;
-        if ((unsigned)xx >= (unsigned)W) continue;
-        float v[8];
-        xload(x + (((long long)b * H + yy) * W + xx) * CP + xoct(q), v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], v[j]);
-      }
-    }
-    xstore(y + (i / Q) * CP + xoct(q), m);
-  }
-}
-// backward as a gather: input pixel (yy, xx) receives g[oy, ox] from every window whose FIRST maximum (scan order) it is
-__global__ void x3_maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g, bf16_t* __restrict__ gx, int B, int H, int W, int Q,
-                                      int OH, int OW, int k, int s, int p) {
-  const long long n = (long long)B * H * W * Q;
-  const int CP = (Q >> 2) * 64;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int q = i % Q; long long r = i / Q;
-    const long long pix = r;
-    const int xx = r % W; r /= W;
-    const int yy = r % H; const int b = r / H;
-    float me[8], acc[8];
-    xload(x + pix * CP + xoct(q), me);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    int oy0 = yy + p - k + 1; oy0 = oy0 <= 0 ? 0 : (oy0 + s - 1) / s;
-    int ox0 = xx + p - k + 1; ox0 = ox0 <= 0 ? 0 : (ox0 + s - 1) / s;
-    const int oy1 = min((yy + p) / s, OH - 1), ox1 = min((xx + p) / s, OW - 1);
-    for (int oy = oy0; oy <= oy1; ++oy)
-      for (int ox = ox0; ox <= ox1; ++ox) {
-        bool win[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) win[j] = true;
-        for (int dy = 0; dy < k; ++dy) {
-          const int y2 = oy * s - p + dy;
-          if ((unsigned)y2 >= (unsigned)H) continue;
-          for (int dx = 0; dx < k; ++dx) {
-            const int x2 = ox * s - p + dx;
-            if ((unsigned)x2 >= (unsigned)W || (y2 == yy && x2 == xx)) continue;
-            float v[8];
-            xload(x + (((long long)b * H + y2) * W + x2) * CP + xoct(q), v);
-            const bool before = (y2 < yy) || (y2 == yy && x2 < xx);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (v[j] > me[j] || (before && v[j] == me[j])) win[j] = false;
-          }
-        }
-        float gv[8];
-        xload(g + (((long long)b * OH + oy) * OW + ox) * CP + xoct(q), gv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (win[j]) acc[j] += gv[j];
-      }
-    xstore(gx + pix * CP + xoct(q), acc);
-  }
-}
-extern "C" int aod_x3_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int s, int p, aod_stream_t stream) {
-  AOD_CHECK_ARG(x && y && C % 64 == 0 && k >= 1 && s >= 1, "x3_maxpool_fwd: bad args");
-  hipLaunchKernelGGL(x3_maxpool_fwd_kernel, dim3(grid_for<2048>((long long)B * OH * OW * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)y, B, H, W, C / 16, OH, OW, k, s, p);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int aod_x3_maxpool_bwd(const void* x, const void* g, void* gx, int B, int H, int W, int C, int OH, int OW, int k, int s, int p,
-                                  aod_stream_t stream) {
-  AOD_CHECK_ARG(x && g && gx && C % 64 == 0, "x3_maxpool_bwd: bad args");
-  hipLaunchKernelGGL(x3_maxpool_bwd_kernel, dim3(grid_for<2048>((long long)B * H * W * (C / 16))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (const bf16_t*)g, (bf16_t*)gx, B, H, W, C / 16, OH, OW, k, s, p);
-  AOD_LAUNCH_CHECK();
-  return 0;
-}
-
 // L2Norm (ssd_neck.py:105-128): y = w * x / (||x||_2 + eps) per pixel on X rows; one wavefront per pixel, octets strided over lanes
 __global__ __launch_bounds__(256) void x3_l2norm_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, bf16_t* __restrict__ y, long long rows,
                                                             int Q, float eps) {
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const int lane = threadIdx.x & 63, CP = (Q >> 2) * 64;
+  const int lane = threadIdx.x & 63, CP = XRows::pitch(Q);
   float ss = 0.f;
   for (int q = lane; q < Q; q += 64) {
     float v[8];
-    xload(x + r * CP + xoct(q), v);
+    XRows::load(x + r * CP + xoct(q), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) ss += v[j] * v[j];
   }
@@ -514,10 +324,10 @@ __global__ __launch_bounds__(256) void x3_l2norm_fwd_kernel(const bf16_t* __rest
   const float n = sqrtf(ss) + eps;
   for (int q = lane; q < Q; q += 64) {
     float v[8];
-    xload(x + r * CP + xoct(q), v);
+    XRows::load(x + r * CP + xoct(q), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = w[q * 8 + j] * v[j] / n;
-    xstore(y + r * CP + xoct(q), v);
+    XRows::store(y + r * CP + xoct(q), v);
   }
 }
 // (cs_ws: deterministic mode, see l2norm_bwd_kernel in ssd_ops.hip; Q * 8 <= 1024 logical channels there)
@@ -526,7 +336,7 @@ __global__ __launch_bounds__(256) void x3_l2norm_bwd_kernel(const bf16_t* __rest
                                                             float* __restrict__ cs_ws) {
   __shared__ float sm[4][1024];
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, CP = (Q >> 2) * 64;
+  const int lane = threadIdx.x & 63, CP = XRows::pitch(Q);
   if (cs_ws) {
     const int wv = threadIdx.x >> 6;
     float n = 1.f, kk = 0.f;
@@ -534,7 +344,7 @@ __global__ __launch_bounds__(256) void x3_l2norm_bwd_kernel(const bf16_t* __rest
       float ss = 0.f, dot = 0.f;
       for (int q = lane; q < Q; q += 64) {
         float v[8], gg[8];
-        xload(x + r * CP + xoct(q), v); xload(g + r * CP + xoct(q), gg);
+        XRows::load(x + r * CP + xoct(q), v); XRows::load(g + r * CP + xoct(q), gg);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { ss += v[j] * v[j]; dot += w[q * 8 + j] * gg[j] * v[j]; }
       }
@@ -548,10 +358,10 @@ __global__ __launch_bounds__(256) void x3_l2norm_bwd_kernel(const bf16_t* __rest
       for (int j = 0; j < 8; ++j) c8[j] = 0.f;
       if (r < rows) {
         float v[8], gg[8], o[8];
-        xload(x + r * CP + xoct(q), v); xload(g + r * CP + xoct(q), gg);
+        XRows::load(x + r * CP + xoct(q), v); XRows::load(g + r * CP + xoct(q), gg);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { o[j] = w[q * 8 + j] * gg[j] / n - kk * v[j]; c8[j] = gg[j] * v[j] / n; }
-        xstore(gx + r * CP + xoct(q), o);
+        XRows::store(gx + r * CP + xoct(q), o);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) sm[wv][q * 8 + j] = c8[j];
@@ -564,7 +374,7 @@ __global__ __launch_bounds__(256) void x3_l2norm_bwd_kernel(const bf16_t* __rest
   float ss = 0.f, dot = 0.f;
   for (int q = lane; q < Q; q += 64) {
     float v[8], gg[8];
-    xload(x + r * CP + xoct(q), v); xload(g + r * CP + xoct(q), gg);
+    XRows::load(x + r * CP + xoct(q), v); XRows::load(g + r * CP + xoct(q), gg);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { ss += v[j] * v[j]; dot += w[q * 8 + j] * gg[j] * v[j]; }
   }
@@ -573,10 +383,10 @@ __global__ __launch_bounds__(256) void x3_l2norm_bwd_kernel(const bf16_t* __rest
   const float kk = nrm > 0.f ? dot / (n * n * nrm) : 0.f;
   for (int q = lane; q < Q; q += 64) {
     float v[8], gg[8], o[8];
-    xload(x + r * CP + xoct(q), v); xload(g + r * CP + xoct(q), gg);
+    XRows::load(x + r * CP + xoct(q), v); XRows::load(g + r * CP + xoct(q), gg);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { o[j] = w[q * 8 + j] * gg[j] / n - kk * v[j]; atomicAdd(gw + q * 8 + j, gg[j] * v[j] / n); }
-    xstore(gx + r * CP + xoct(q), o);
+    XRows::store(gx + r * CP + xoct(q), o);
   }
 }
 extern "C" int aod_x3_l2norm_fwd(const void* x, const float* w, void* y, int64_t rows, int C, float eps, aod_stream_t stream) {

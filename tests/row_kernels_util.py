@@ -1,6 +1,6 @@
-"""Cases and helpers of tests/test_gpu_row_kernels.py: the row kernels under and around the FPN neck (csrc/elementwise.hip and their x3 twins
-in csrc/x3_ops.hip) at the shapes where an index or a grid-stride loop goes wrong -- 1x1 maps, one-column maps, H = 2h - 1, and one case each
-beyond the grid cap of 2048 blocks x 256 threads (CAP work items: the loop's second trip).
+"""Cases and helpers of tests/test_gpu_row_kernels.py: the row kernels under and around the FPN neck (csrc/elementwise.hip, csrc/ssd_ops.hip
+and csrc/x3_ops.hip; max-pool and upsample-add are one template each over the row layout of csrc/row_layout.h) at the shapes where an
+index or a grid-stride loop goes wrong -- 1x1 maps, one-column maps, H = 2h - 1, and one case each beyond the grid cap of 2048 blocks x 256 threads (CAP work items: the loop's second trip).
 
 Most expectations are bit for bit and carry no figure.  The adjoint of the upsample is bounded element by element on the scale
 S = the sum of the absolute values folded into the element (at most four, plus the old value when accumulating):
