@@ -207,6 +207,11 @@ _SIGS = {
     'aod_divproto_chunk': (C.c_int, []),
     'aod_divproto_ws_len': (SZ, [I64, I32, I64]),
     'aod_divproto_select': (C.c_int, [P, I64, I64, P, P, P, P, I32, I32, I32, I64, F32, F32, I32, I64, I64, I32, I32, P, P, P, P]),
+    'aod_object_posterior': (C.c_int, [P, P, P, P, I32, I32, I32, I32, I32, F32, P, P]),
+    'aod_badge_embedding': (C.c_int, [P, P, P, P, I32, I32, I32, I32, I32, P, I64, P]),
+    'aod_kmeanspp_block': (C.c_int, []),
+    'aod_kmeanspp_ws_len': (SZ, [I64]),
+    'aod_kmeanspp_seed': (C.c_int, [P, I64, I32, P, I64, I64, P, P, P, P, P, P, P]),
     'aod_loc_stability_max_levels': (C.c_int, []),
     'aod_pixel_noise': (C.c_int, [P, P, I32, I32, I32, I32, P, P, F32, I32, U64, P, P]),
     'aod_loc_stability': (C.c_int, [P, P, P, I32, I32, I32, F32, I32, I32, P, P, P]),

@@ -125,6 +125,22 @@ class Uncertainty_fns:
         return DivProto_uncertainty(cfg, model, dataloader, **_labelled_options('DivProto', kwargs), **own)
 
     @staticmethod
+    def BADGE(cfg, *args, **kwargs):
+        # gradient embeddings + k-means++ seeding (Ash et al., ICLR 2020): needs the labelled set (it is excluded from the
+        # seeding) and selects by rank like Coreset.  Of the HUA options only score_thr is read (the object gate); max_obj and seed are its own
+        model, dataloader = args
+        own = {k: kwargs[k] for k in ('max_obj', 'seed') if kwargs.get(k) is not None}
+        return BADGE_uncertainty(cfg, model, dataloader, **_labelled_options('BADGE', kwargs), **own)
+
+    @staticmethod
+    def KMeansPP(cfg, *args, **kwargs):
+        # k-means++ seeding on the Core-set descriptors: Core-set's randomised, density-following counterpart.  Needs the
+        # labelled set; like Coreset it reads none of the HUA options
+        model, dataloader = args
+        own = {k: kwargs[k] for k in ('seed',) if kwargs.get(k) is not None}
+        return KMeansPP_uncertainty(cfg, model, dataloader, **_labelled_options('KMeansPP', kwargs, score_thr=False), **own)
+
+    @staticmethod
     def _loc_stability(combine, cfg, *args, **kwargs):
         # localization stability (Kao et al., ACCV 2018): reads score_thr (the object gate, default 0.3), sigmas, seed and
         # same_class; the HUA options that calculate_uncertainty's callers pass for the Entropy_* pools have no meaning for it
@@ -780,6 +796,78 @@ def DivProto_uncertainty(cfg, model, data_loader, X_L=None, budget=None, max_obj
     picks, _ = divproto_select(order, pool['proto'], pool['pcls'], pool['pconf'], pool['pcnt'], n_cls, budget, t_intra=t_intra, t_inter=t_inter,
                                alpha=alpha, beta=beta, class_balance=class_balance)
     return _pick_scores(picks, pool['enms'].shape[0])
+
+
+@torch.no_grad()
+def single_gpu_badge_embeddings(model, data_loader, max_obj=32, score_thr=0.3, **kwargs):
+    """BADGE gradient embeddings of the whole pool on _PoolPass's loop: single_gpu_object_descriptors' pass -- sharded,
+    prefetched, the forward (isEval=True, _padded=True, objDesc=max_obj, objPost=True: the object descriptors and the posterior rows in
+    their slots) replayed from one captured graph of its own while the batch shape repeats -- with the embedding launch
+    (scoring.badge_embedding) run per batch behind the replay on the same stream, on the graph's static outputs, straight into the
+    preallocated [N, D] store, which parallel.gather_rows makes whole on every rank.  Only the RetinaNet detectors are supported (evidence
+    heads and the plain baseline); SSD raises NotImplementedError.
+
+    Returns a dict of device tensors: emb [N, D] fp32, D = num_classes * C (class-major; an image without an object has the zero row),
+    cnt [N] int32, missing [N] int32 (always 0).  The store is N * num_classes * C * 4 bytes: 339 MB for the 16 551 images of VOC07+12
+    trainval (20 x 256 columns), 9.7 GB for the 118 287 of COCO train2017 (80 x 256).  A row's bits depend on its image alone -- not on
+    the batch size, the rank count, or eager / replayed execution."""
+    from ..scoring import BADGE_MAX_CLASSES, CCMS_MAX_OBJ, badge_embedding
+    max_obj, score_thr = int(max_obj), float(score_thr)
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'single_gpu_badge_embeddings: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    if score_thr != score_thr:
+        raise ValueError('single_gpu_badge_embeddings: score_thr is NaN')
+    neck = _fpn_neck(model, 'single_gpu_badge_embeddings: BADGE gradient embeddings')
+    module = getattr(model, 'module', model)
+    n_cls = int(module.bbox_head.num_classes)
+    if not 1 <= n_cls <= BADGE_MAX_CLASSES:
+        raise ValueError(f'single_gpu_badge_embeddings: up to {BADGE_MAX_CLASSES} classes are supported, the head has {n_cls}')
+    N, Cc, dev = len(data_loader.dataset), int(neck.out_channels), next(model.parameters()).device
+    store = dict(emb=torch.zeros(N, n_cls * Cc, dtype=torch.float32, device=dev), cnt=torch.zeros(N, dtype=torch.int32, device=dev),
+                 missing=torch.zeros(N, dtype=torch.int32, device=dev))
+    kwargs.setdefault('isUnc', False)
+    fkw = dict(kwargs, objDesc=max_obj, objPost=True, score_thr=score_thr, unc_measure='entropy', unc_aggregate='sum')
+
+    def write(out, rows):
+        feat, cls, _, cnt, missing, post = out[4:10]
+        badge_embedding(feat, post, cls, cnt, n_cls, out=store['emb'][rows])
+        store['cnt'][rows].copy_(cnt)
+        store['missing'][rows].copy_(missing)
+    return _row_store_pass(model, data_loader, ('badge',), dict(isEval=True, _padded=True), fkw, store, write)
+
+
+def _seed_scores(desc, X_L, budget, seed):
+    """k-means++ seeding of `budget` rows of desc outside X_L (scoring.kmeanspp_seed; the draws come from np.random.default_rng(seed) on
+    the host, so every rank picks alike) in the form update_X_L takes"""
+    from ..scoring import kmeanspp_seed
+    return _pick_scores(kmeanspp_seed(desc, X_L, budget, seed=seed)[0], desc.shape[0])
+
+
+def BADGE_uncertainty(cfg, model, data_loader, X_L=None, budget=None, max_obj=32, score_thr=0.3, seed=0, **kwargs):
+    """BADGE acquisition (J. T. Ash, C. Zhang, A. Krishnamurthy, J. Langford, A. Agarwal, "Deep Batch Active Learning by
+    Diverse, Uncertain Gradient Lower Bounds", ICLR 2020; the reference has none) in the form update_X_L takes: the gradient embedding of
+    every image (single_gpu_badge_embeddings: per object the gradient of the cross-entropy under the detection's own label times the
+    neck row of its anchor's cell, summed over the image's objects), then k-means++ seeding on the unlabelled rows
+    (scoring.kmeanspp_seed): the first pick is the longest embedding, every later one is drawn in proportion to its squared distance
+    from the picks so far, so an uncertain image (a long row) far from the picks is likely.  The labelled images X_L are excluded, not
+    centres.  seed: of the host draws; every rank runs the seeding on the same matrix with the same draws and gets the same picks.
+    budget: default cfg.X_S_size.  Returns a CPU [N] fp32 vector: the image picked at step t = 0 .. budget - 1 scores budget - t, every
+    other image 0 -- with a falsy zeroRate update_X_L's arg[-X_S_size:] selects exactly the picks."""
+    if X_L is None:
+        raise TypeError('BADGE_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are excluded from the seeding')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    pool = single_gpu_badge_embeddings(model, data_loader, max_obj=max_obj, score_thr=score_thr, **kwargs)
+    return _seed_scores(pool['emb'], X_L, budget, seed)
+
+
+def KMeansPP_uncertainty(cfg, model, data_loader, X_L=None, budget=None, seed=0, **kwargs):
+    """k-means++ acquisition: BADGE's seeding on Core-set's descriptors (single_gpu_descriptors) -- pure diversity, and
+    Core-set's randomised counterpart: where k-center greedy takes the farthest row and so chases outliers, D^2 sampling follows the
+    density of the pool.  X_L, budget, seed and the returned vector as in BADGE_uncertainty."""
+    if X_L is None:
+        raise TypeError('KMeansPP_uncertainty(cfg, model, data_loader, X_L=...): the labelled indices X_L are excluded from the seeding')
+    budget = int(cfg.X_S_size if budget is None else budget)
+    return _seed_scores(single_gpu_descriptors(model, data_loader, **kwargs), X_L, budget, seed)
 
 
 def Posterior_uncertainty(cfg, model, data_loader, measure='entropy', aggregate='max', score_thr=0.3, class_weighted=False, **kwargs):

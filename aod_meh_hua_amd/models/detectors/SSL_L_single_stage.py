@@ -58,9 +58,12 @@ class SSL_L_SingleStageDetector(SSLBase_L_Detector):
             return self._just_feat(img)
         if kwargs.get('objUnc') and not kwargs.get('objDesc'):
             raise ValueError('objUnc is offered together with objDesc only: it appends the per-object measure in the descriptors\' slots')
+        if kwargs.get('objPost') and not kwargs.get('objDesc'):
+            raise ValueError('objPost is offered together with objDesc only: it appends the posterior rows in the descriptors\' slots')
         if kwargs['isEval'] and kwargs.get('objDesc'):
             # CCMS object descriptors (apis/test.py single_gpu_object_descriptors): the static (dets, labels, num, unc, feat, cls, w, cnt,
-            # missing) of the padded evaluation form, max_obj = objDesc; objUnc=True (ENMS / DivProto, single_gpu_enms) appends h
+            # missing) of the padded evaluation form, max_obj = objDesc; objUnc=True (ENMS / DivProto, single_gpu_enms) appends h,
+            # objPost=True (BADGE, single_gpu_badge_embeddings) post
             if not kwargs.get('_padded'):
                 raise ValueError('objDesc is offered with the padded evaluation outputs only (isEval=True, _padded=True)')
             self._check_obj_desc()

@@ -389,17 +389,18 @@ def kcenter_greedy(desc, labelled, budget, metric='sqeuclid'):
     return _kcenter_run('kcenter_greedy', 'aod_kcenter_greedy_ex', desc, (N, D), labelled, budget, KCENTER_METRICS[metric])
 
 
-def _index_array(name, idx, N, arg='labelled', distinct=True):
-    """`idx` (tensor, array or sequence of row indices) as a validated int64 array; the messages carry the caller's `name`"""
+def _index_array(name, idx, N, arg='labelled', distinct=True, noun='labelled'):
+    """`idx` (tensor, array or sequence of row indices) as a validated int64 array; the messages carry the caller's `name` (and `noun`,
+    what the range and duplicate messages call the set)"""
     lab = idx.detach().cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
     lab = lab.reshape(-1)
     if lab.size and not np.issubdtype(lab.dtype, np.integer):
         raise ValueError(f'{name}: {arg} must hold integer indices, got {lab.dtype}')
     lab = lab.astype(np.int64)
     if lab.size and (lab.min() < 0 or lab.max() >= N):
-        raise ValueError(f'{name}: labelled index outside [0, {N})')
+        raise ValueError(f'{name}: {noun} index outside [0, {N})')
     if distinct and np.unique(lab).size != lab.size:
-        raise ValueError(f'{name}: labelled holds a duplicated index')
+        raise ValueError(f'{name}: {noun} holds a duplicated index')
     return lab
 
 
@@ -799,6 +800,123 @@ def object_measure(obj_out, dets, num, obj_cand=None, max_obj=32, score_thr=0.3)
     return h
 
 
+BADGE_MAX_CLASSES = 128
+KMEANSPP_MAX_COLUMNS = 32768
+KMEANSPP_MAX_ROWS = 1 << 24
+
+
+def object_posterior(scores, dets, num, obj_cand, max_obj=32, score_thr=0.3):
+    """The candidate score row of every object in object_descriptors' slots (aod_object_posterior): post [B, max_obj, W] fp32 =
+    scores[b, obj_cand[b, j], :] (scores = cand.scores [B, n, W], W columns as they lie) at the detection rows j < num[b] whose score
+    exceeds score_thr (strict) and that have a candidate row, the first max_obj in row order -- object_measure's slot rule; zero rows
+    behind them (every word is written: a replayed graph never exposes stale rows).  Device tensors, no host sync."""
+    _check_tensors('object_posterior', (('scores', scores, torch.float32, 3), ('dets', dets, torch.float32, 3), ('num', num, torch.int32, 1),
+                                        ('obj_cand', obj_cand, torch.int32, 2)))
+    B, n, W = (int(v) for v in scores.shape)
+    max_num = int(dets.shape[1])
+    max_obj, score_thr = int(max_obj), float(score_thr)
+    if B < 1 or n < 1 or W < 1 or not 1 <= max_num <= UNC_MAX_DET or tuple(dets.shape) != (B, max_num, 5) or tuple(num.shape) != (B,):
+        raise ValueError(f'object_posterior: scores {tuple(scores.shape)}, dets {tuple(dets.shape)}, num {tuple(num.shape)}: expected (B, n, W), '
+                         f'(B, max_num, 5), (B,) with 1 <= max_num <= {UNC_MAX_DET}')
+    if tuple(obj_cand.shape) != (B, max_num):
+        raise ValueError(f'object_posterior: obj_cand has shape {tuple(obj_cand.shape)}, expected ({B}, {max_num})')
+    if not 1 <= max_obj <= CCMS_MAX_OBJ:
+        raise ValueError(f'object_posterior: max_obj must be in 1..{CCMS_MAX_OBJ}, got {max_obj}')
+    if score_thr != score_thr:
+        raise ValueError('object_posterior: score_thr is NaN')
+    _check_devices('object_posterior', [scores, dets, num, obj_cand])
+    post = torch.empty(B, max_obj, W, dtype=torch.float32, device=scores.device)
+    call('aod_object_posterior', ptr(scores), ptr(dets), ptr(num), ptr(obj_cand), B, n, W, max_num, max_obj, score_thr, ptr(post), stream())
+    return post
+
+
+def badge_embedding(feat, post, cls, cnt, n_cls, out=None):
+    """BADGE gradient embedding of every image of a batch (aod_badge_embedding; Ash et al., ICLR 2020): [B, n_cls * Cf] fp32,
+    class-major: G[b][c][j] = sum over the objects o < cnt[b], in ascending order, of (post[b, o, c] - [c == cls[b, o]]) * feat[b, o, j]
+    -- per object the gradient of the cross-entropy with respect to the logits under the detection's own label, times its feature row.
+    feat [B, K, Cf] fp32, cls [B, K] int32, cnt [B] int32 as object_descriptors writes them, post [B, K, W] fp32 (object_posterior), W >=
+    n_cls: a pad or background column >= n_cls is never read, nor is a row >= cnt.  K <= 64, Cf % 8 == 0, 8 <= Cf <= 256, n_cls <= 128.
+    out: a [B, n_cls * Cf] fp32 view with unit column stride (rows of the pool matrix) to write into.  A row's bits depend on its image
+    alone.  Device tensors, no host sync."""
+    _check_tensors('badge_embedding', (('feat', feat, torch.float32, 3), ('post', post, torch.float32, 3), ('cls', cls, torch.int32, 2),
+                                       ('cnt', cnt, torch.int32, 1)))
+    B, K, Cf = _check_obj_shape('badge_embedding', 'feat', feat.shape)
+    n_cls = int(n_cls)
+    if not 1 <= n_cls <= BADGE_MAX_CLASSES:
+        raise ValueError(f'badge_embedding: n_cls must be in 1..{BADGE_MAX_CLASSES}, got {n_cls}')
+    if tuple(post.shape[:2]) != (B, K) or int(post.shape[2]) < n_cls:
+        raise ValueError(f'badge_embedding: post has shape {tuple(post.shape)}, expected ({B}, {K}, W) with W >= n_cls = {n_cls}')
+    if tuple(cls.shape) != (B, K):
+        raise ValueError(f'badge_embedding: cls has shape {tuple(cls.shape)}, expected ({B}, {K})')
+    if tuple(cnt.shape) != (B,):
+        raise ValueError(f'badge_embedding: cnt has shape {tuple(cnt.shape)}, expected ({B},)')
+    D = n_cls * Cf
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (B, D) and out.stride(1) == 1
+                and (B == 1 or (out.stride(0) >= D and out.stride(0) % 4 == 0)) and out.data_ptr() % 16 == 0):
+            raise ValueError(f'badge_embedding: out must be a 16-B aligned [{B}, {D}] fp32 view with unit column stride and a row stride that is '
+                             'a multiple of 4')
+    _check_devices('badge_embedding', [feat, post, cls, cnt] + ([out] if out is not None else []))
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=feat.device)
+    call('aod_badge_embedding', ptr(feat), ptr(post), ptr(cls), ptr(cnt), B, K, Cf, int(post.shape[2]), n_cls, ptr(out),
+         int(out.stride(0)) if B > 1 else D, stream())
+    return out
+
+
+def kmeanspp_block():
+    """consecutive rows whose weights kmeanspp_seed adds into one fp64 block sum: with N, the one thing the association of its sums depends on"""
+    return int(_C.lib.aod_kmeanspp_block())
+
+
+def kmeanspp_seed(desc, excluded, budget, draws=None, seed=0):
+    """k-means++ D^2 seeding (Arthur & Vassilvitskii, SODA 2007) as BADGE uses it (Ash et al., ICLR 2020) on the aod_kmeanspp_seed kernels
+    (DESIGN 3t).  A row is eligible iff it is neither in `excluded` nor picked; excluded rows are NOT centres.  Pick 0 is the eligible row
+    with the largest squared norm (the lowest index on a tie).  Pick t >= 1 is drawn with probability proportional to w_i = the squared
+    Euclidean distance (kcenter_greedy's arithmetic) of eligible row i to its nearest pick: with T the fp64 sum of the w_i (blocks of
+    kmeanspp_block() rows in order), the first row with w_i > 0 whose running sum exceeds draws[t] * T; T == 0: the lowest eligible row.
+
+    desc: [N, D] fp32 contiguous device tensor (N <= 2^24, D <= 32768); excluded: distinct row indices in [0, N) (sequence, array or
+    tensor; may be empty); 1 <= budget <= number of eligible rows; draws: [budget] float64 in [0, 1) (draws[0] is not read), default
+    np.random.default_rng(seed).random(budget) -- a host input, so every rank draws alike.
+    Returns (picks [budget] int64, weight [budget] fp32: w of pick t when it was picked, the norm for t = 0; total [budget] fp64: T,
+    0 for t = 0) on the device.  All steps are enqueued on the current stream; no host sync.  The result is a function of (desc, the set
+    excluded, draws) alone."""
+    if not (torch.is_tensor(desc) and desc.dim() == 2 and desc.dtype == torch.float32 and desc.is_contiguous() and desc.numel() > 0):
+        raise ValueError('kmeanspp_seed: desc must be a non-empty contiguous 2-D fp32 tensor')
+    N, D = int(desc.shape[0]), int(desc.shape[1])
+    if D > KMEANSPP_MAX_COLUMNS:
+        raise ValueError(f'kmeanspp_seed: up to {KMEANSPP_MAX_COLUMNS} descriptor columns are supported, got {D}')
+    if N > KMEANSPP_MAX_ROWS:
+        raise ValueError(f'kmeanspp_seed: up to 2^24 rows are supported, got {N}')
+    exc = _index_array('kmeanspp_seed', excluded, N, arg='excluded', noun='excluded')
+    budget = int(budget)
+    if budget < 1:
+        raise ValueError(f'kmeanspp_seed: budget must be at least 1, got {budget}')
+    if budget > N - exc.size:
+        raise ValueError(f'kmeanspp_seed: budget {budget} exceeds the {N - exc.size} eligible rows')
+    if draws is None:
+        draws = np.random.default_rng(int(seed)).random(budget)
+    draws = np.ascontiguousarray(draws.detach().cpu().numpy() if torch.is_tensor(draws) else np.asarray(draws), dtype=np.float64).reshape(-1)
+    if draws.size != budget:
+        raise ValueError(f'kmeanspp_seed: draws holds {draws.size} values, expected budget = {budget}')
+    if not np.all((draws[1:] >= 0.0) & (draws[1:] < 1.0)):
+        raise ValueError('kmeanspp_seed: draws must lie in [0, 1)')
+    if not desc.is_cuda:
+        raise _cpu_refusal('kmeanspp_seed')
+    dev = desc.device
+    exc_d = torch.from_numpy(exc).to(dev) if exc.size else None
+    draws_d = torch.from_numpy(draws).to(dev)
+    picks = torch.empty(budget, dtype=torch.int64, device=dev)
+    weight = torch.empty(budget, dtype=torch.float32, device=dev)
+    total = torch.empty(budget, dtype=torch.float64, device=dev)
+    mind = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_C.lib.aod_kmeanspp_ws_len(N)), dtype=torch.uint8, device=dev)
+    call('aod_kmeanspp_seed', ptr(desc), N, D, ptr(exc_d), int(exc.size), budget, ptr(draws_d), ptr(picks), ptr(weight), ptr(total), ptr(mind),
+         ptr(ws), stream())
+    return picks, weight, total
+
+
 def enms_prototypes(feat, cls, w, h, cnt, t_enms=0.5, want_picks=False):
     """ENMS score and class prototypes of every image of a batch (aod_enms_prototypes; Wu et al., CVPR 2022).
 
@@ -1101,7 +1219,9 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                                         ValueError together with objDesc or detUnc
                  with _padded=True, objDesc=max_obj -> (dets, labels, num, unc, feat, cls, w, cnt, missing): the triple, the
                                         posterior score and object_descriptors' outputs; objUnc=True (with objDesc only)
-                                        appends h [B,max_obj] fp32, the per-object measure in the same slots (object_measure)
+                                        appends h [B,max_obj] fp32, the per-object measure in the same slots (object_measure);
+                                        objPost=True (with objDesc only) appends post [B,max_obj,W] fp32, the candidate score
+                                        row of every object in the same slots (object_posterior), behind h when both are asked for
                  with detUnc=True    -> list of (det_bboxes [k,5], det_labels [k], det_unc [k,2]): HUA runs after NMS (it needs L_scores)
                                         and det_unc holds (aleatoric, epistemic) of every detection, NaN for rows that are no HUA object.
     hua_estimator = 'mc' (default) | 'closed' selects the estimator of the Entropy_NMS / Entropy_ALL / Entropy_Avg / detUnc paths.
@@ -1131,6 +1251,8 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
     _class_weight(head, None, kwargs)          # (class_weighted on a head without the option: refused before the first launch)
     if kwargs.get('objUnc') and not kwargs.get('objDesc'):
         raise ValueError('objUnc is offered together with objDesc only: it appends the per-object measure in the descriptors\' slots')
+    if kwargs.get('objPost') and not kwargs.get('objDesc'):
+        raise ValueError('objPost is offered together with objDesc only: it appends the posterior rows in the descriptors\' slots')
     if isUnc and uPool == 'Entropy_NoNMS':
         raise NotImplementedError('uncertainty_pool=Entropy_NoNMS crashes in the reference too (ComputeScaleUnc with L_scores=None)')
     lam_mode = getattr(head, '_hua_lam', 'scaled')
@@ -1204,9 +1326,13 @@ def score_batch(head, mlvl_cls_scores, mlvl_bbox_preds, mlvl_anchors, img_shapes
                                                 class_w=_class_weight(head, cand, kwargs))
             desc = object_descriptors(feats, cand, dets, labels, num, obj_cand, list(na), int(kwargs['objDesc']), thr,
                                       channels=getattr(head, 'in_channels', None))
+            res = (dets, labels, num, unc) + desc
             if kwargs.get('objUnc'):
-                return (dets, labels, num, unc) + desc + (object_measure(obj_out, dets, num, obj_cand, int(kwargs['objDesc']), thr),)
-            return (dets, labels, num, unc) + desc
+                res += (object_measure(obj_out, dets, num, obj_cand, int(kwargs['objDesc']), thr),)
+            if kwargs.get('objPost'):
+                # BADGE (apis/test.py single_gpu_badge_embeddings): one more launch, the objects' posterior rows in the same slots
+                res += (object_posterior(cand.scores, dets, num, obj_cand, int(kwargs['objDesc']), thr),)
+            return res
         return dets, labels, num
     if isUnc and not kwargs.get('isEval') and uPool in POSTERIOR_POOLS:
         # posterior uncertainty pools: one launch behind the NMS kernel on what it and pre_nms left on the device; no lambda is

@@ -1027,6 +1027,45 @@ int aod_divproto_select(const int64_t* order, int64_t M, int64_t N, const float*
                         int64_t quota, int64_t n_free, int class_balance, int chunk, int64_t* picks, int32_t* stage, void* ws,
                         aod_stream_t stream);
 
+/* ------------------------------------------------------------------ BADGE acquisition (csrc/badge.hip, csrc/kmeanspp.hip): gradient
+ * embeddings whose length carries an image's uncertainty and whose direction its content, then k-means++ D^2 seeding on them (J. T. Ash,
+ * C. Zhang, A. Krishnamurthy, J. Langford, A. Agarwal, "Deep Batch Active Learning by Diverse, Uncertain Gradient Lower Bounds", ICLR 2020;
+ * the seeding: D. Arthur, S. Vassilvitskii, "k-means++: The Advantages of Careful Seeding", SODA 2007).  No reference call site; the
+ * semantics are fixed in DESIGN 3t.
+ *   aod_object_posterior: post [B][max_obj][W] fp32, slot-aligned with aod_object_descriptors' feat / cls: scores [B][n][W] (the candidate
+ *     score rows) at row obj_cand[b][j] of the detection rows j < num[b] with dets[b][j][4] > score_thr (strict) and 0 <= obj_cand[b][j] < n
+ *     (aod_object_measure's slot rule), the first max_obj in row order; zero rows behind them: every word is written.
+ *   aod_badge_embedding: out[b * out_stride + c * Cf + j] = sum over the objects o < cnt[b] in ascending order of a_o[c] * f_o[j], fp32, a
+ *     separate multiply and add per object; a_o[c] = post[b][o][c] - [c == cls[b][o]], c < n_cls <= W (the gradient of the cross-entropy with
+ *     respect to the logits under the detection's own label), f_o = feat[b][o][:].  feat [B][K][Cf] (16-B aligned), post [B][K][W],
+ *     cls [B][K], cnt [B]; K <= 64, Cf % 8 == 0, 8 <= Cf <= 256, n_cls <= 128; out 16-B aligned, out_stride % 4 == 0 and >= n_cls * Cf.
+ *     Columns >= n_cls of post and rows >= cnt[b] are never read; cnt[b] = 0 writes the zero row.  One workgroup per image, no atomics: a
+ *     row is a function of its image alone -- the same bits alone, in any batch, eager or replayed.
+ *   aod_kmeanspp_seed: desc [N][D] fp32 (1 <= N <= 2^24, 1 <= D <= 32768, 16-B aligned), excluded [n_excluded] int64 DEVICE indices
+ *     (distinct, in [0, N): the caller validates; an index outside the matrix is skipped, never dereferenced), 1 <= budget <=
+ *     N - n_excluded, draws [budget] fp64 DEVICE values in [0, 1) (draws[0] is not read).  A row is eligible iff it is neither excluded nor
+ *     picked; excluded rows are NOT centres.
+ *       d(i, c)  = sum_k (x_ik - x_ck)^2 in aod_kcenter_greedy's arithmetic, continued past column 2048: the same bits for D <= 2048
+ *       pick 0   : the eligible row with the largest |x_i|^2 = d(i, 0), the LOWEST index on a tie; weight[0] = that norm, total[0] = 0
+ *       pick t   : w_i = min over the picks so far of d(i, pick) for an eligible row, else 0.  S_b = the fp64 sum of w_i over block b of
+ *                  aod_kmeanspp_block() consecutive rows in row order, T = S_0 + S_1 + ... in block order.  T == 0: the lowest eligible
+ *                  row.  Else target = draws[t] * T (one fp64 product) and the pick is the first row with w_i > 0 whose running sum -- the
+ *                  blocks before it in order, then the rows of its block in order, fp64 -- exceeds target (strict); no such row (the
+ *                  product rounded up to T): the last row with w_i > 0.  weight[t] = w_pick, total[t] = T.
+ *     picks [budget] int64, weight [budget] fp32, total [budget] fp64, mind [N] fp32 (on return: the distance to the nearest picked row),
+ *     ws: aod_kmeanspp_ws_len(N) bytes (0: N outside 1 .. 2^24), 8-B aligned.  All steps are enqueued on `stream`, one launch per pick, which
+ *     first finds the pick from the per-block partials of the launch before it (every workgroup redundantly, in one fixed association that
+ *     depends on N and aod_kmeanspp_block() alone); no host sync, no cross-workgroup wait inside a launch, no atomics, no trip count that
+ *     depends on data.  NaN descriptors are the caller's error. */
+int aod_object_posterior(const float* scores, const float* dets, const int32_t* num, const int32_t* obj_cand, int B, int n, int W, int max_num,
+                         int max_obj, float score_thr, float* post, aod_stream_t stream);
+int aod_badge_embedding(const float* feat, const float* post, const int32_t* cls, const int32_t* cnt, int B, int K, int Cf, int W, int n_cls,
+                        float* out, int64_t out_stride, aod_stream_t stream);
+int aod_kmeanspp_block(void);
+size_t aod_kmeanspp_ws_len(int64_t N);
+int aod_kmeanspp_seed(const float* desc, int64_t N, int D, const int64_t* excluded, int64_t n_excluded, int64_t budget, const double* draws,
+                      int64_t* picks, float* weight, double* total, float* mind, void* ws, aod_stream_t stream);
+
 /* ------------------------------------------------------------------ reference-precision mode (aod_conv_desc_t.x3): row kernels on
  * X-layout tensors (csrc/x3_ops.hip).  The reference computes every one of these in fp32 (README.md:13-25); here a value is the fp32 sum of
  * its bf16 head and tail and is written back as such a pair.  `C` = PHYSICAL width (bf16 columns, multiple of 64) unless stated. */

@@ -72,7 +72,14 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
                         '| DivProto (ENMS + the progressive diversity pick of the same paper: sweep the images by ENMS score, pass over those '
                         'whose class prototypes repeat a pick, --intra-thr, and give the share --minority-beta of the budget to images that '
                         'bring one of the --minority-alpha least-held classes with a confidence above --inter-thr; RetinaNet detectors, '
-                        'zeroRate off)')
+                        'zeroRate off) '
+                        '| BADGE (Ash et al., ICLR 2020: the gradient embedding of every image -- per object the cross-entropy gradient under '
+                        'its own label times its neck feature, summed -- then k-means++ seeding on the unlabelled rows, --selection-seed; '
+                        'RetinaNet detectors, zeroRate off) '
+                        '| KMeansPP (the same k-means++ seeding on the Coreset descriptors: pure diversity that follows the density of the '
+                        'pool; RetinaNet detectors, zeroRate off)')
+    p.add_argument('--selection-seed', type=int, default=0,
+                   help='BADGE / KMeansPP pools: seed of the k-means++ draws; cycle c draws with seed + c (default: 0)')
     p.add_argument('--enms-thr', type=float, default=0.5,
                    help='ENMS / DivProto pools: an object is dropped when its feature cosine to a picked object of its class exceeds this (default: 0.5)')
     p.add_argument('--intra-thr', type=float, default=0.7,
@@ -96,7 +103,7 @@ def parse_args(default_config='configs/_base_/Config_RetinaNet.py', default_size
     p.add_argument('--candidate-factor', type=float, default=4.0,
                    help='CCMS pool: the candidate set holds ceil(factor x budget) of the most uncertain unlabelled images (default: 4)')
     p.add_argument('--max-objects', type=int, default=32,
-                   help='CCMS / ENMS / DivProto pools: objects described per image, the first K detections above --hua-score-thr (default: 32, '
+                   help='CCMS / ENMS / DivProto / BADGE pools: objects described per image, the first K detections above --hua-score-thr (default: 32, '
                         'at most 64)')
     p.add_argument('--noise-levels', default='8,16,24,32,40,48',
                    help='noise strengths of the LocStability pools: up to 16 comma-separated standard deviations in 0..255 pixel units '
@@ -345,9 +352,14 @@ def main(default_config='configs/_base_/Config_RetinaNet.py', default_size=512):
             # CCMS (uncertainty pre-selection, then k-center greedy under the object-matching distance) is handled like them
             # PPAL is CCMS with the class-weighted first stage
             # DivProto (sweep by ENMS score, progressive prototype pick) likewise; ENMS alone is an ordinary score
+            # BADGE and KMeansPP (k-means++ seeding on gradient embeddings / on the Coreset descriptors) likewise
             coreset = (cfg.uncertainty_pool in ('Coreset', 'CDAL') or cfg.uncertainty_pool == 'CCMS' or cfg.uncertainty_pool == 'PPAL'
-                       or cfg.uncertainty_pool == 'DivProto')
+                       or cfg.uncertainty_pool == 'DivProto' or cfg.uncertainty_pool in ('BADGE', 'KMeansPP'))
             pool_kw = dict(X_L=X_L) if coreset else {}
+            if cfg.uncertainty_pool in ('BADGE', 'KMeansPP'):                 # k-means++ seeding: the draws must not repeat from cycle to cycle
+                pool_kw.update(seed=args.selection_seed + cycle)
+            if cfg.uncertainty_pool == 'BADGE':
+                pool_kw.update(max_obj=args.max_objects)
             if cfg.uncertainty_pool in ('CCMS', 'PPAL'):
                 pool_kw.update(candidate_factor=args.candidate_factor, max_obj=args.max_objects)
             if cfg.uncertainty_pool in ('ENMS', 'DivProto'):
